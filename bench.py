@@ -2,6 +2,7 @@
 416x416, batch 8 clips per GPU (BASELINE.json configs[1]: fp32, synthetic data, random init).
 
     python bench.py --gpus 1 --steps 5 --warmup 2        (always through the interpreter — under rocprofv3: `-- python3 bench.py`)
+    python bench.py --gpus 1 --steps 5 --warmup 2 --full (+ roofline, alternative arithmetic, bf16s / fp8s legs, CPU baseline)
     python bench.py --gpus N ...                         (no launcher in the environment: spawns N ranks through
                                                           `python -m torch.distributed.run`, before this process touches a GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
@@ -12,10 +13,15 @@ A step = forward of the drop-in ``grounding_model`` on 64 images (= 8 clips x T 
 training losses, backward, RMSprop step — nothing skipped.  The timed region runs the step as ONE replayed hipGraph
 (dcnet_amd.graph.GraphedTrainStep; ``--graph off`` = the eager Python step) and contains no profiling.
 
-Rank 0 prints ONE compact JSON line (< 2 KB).  The per-kernel tables behind it — every conv-engine launch of an untimed
-profiled pass with a HIP event pair on its launch stream (dcn_prof_*) — go to ``profiles/bench_full_latest.json`` (and
-``gpurun_out/`` when present).  ``cpu_baseline`` times the CPU oracle (oracle/, a restatement pinned against the reference)
-on 1 clip of the same shape.
+A plain run sets up, warms up, times ``--steps`` steps and prints the line; nothing untimed runs after the timed steps.
+``--dump-outputs DIR`` writes what the last timed step computed (loss, its five parts, a fixed seeded sample of the updated
+parameters and of their gradients) as .npy files; the inputs are seeded, so two builds can be compared output for output.
+``--full`` adds the untimed passes after the timed region (every rank runs them): the held shader clock, a profiled pass, the
+alternative-arithmetic passes, the bf16s / fp8s legs and the CPU baseline.
+
+Rank 0 prints ONE compact JSON line (< 2 KB).  With ``--full``, the per-kernel tables behind it — every conv-engine launch of
+an untimed profiled pass with a HIP event pair on its launch stream (dcn_prof_*) — go to ``profiles/bench_full_latest.json``.
+``cpu_baseline`` times the CPU oracle (oracle/, a restatement pinned against the reference) on 1 clip of the same shape.
 """
 from __future__ import annotations
 
@@ -181,6 +187,40 @@ def compact_line(res: dict) -> str:
     return line
 
 
+DUMP_SAMPLE = 1 << 22      # elements per sampled array: parameters + gradients = 32 MB of float32, under the 64 MB of a dump
+
+
+def dump_outputs(out_dir: str, loss, parts: dict, named_params, sample: int = DUMP_SAMPLE, seed: int = 0) -> dict:
+    """What a caller of the timed step receives after its last step, as ``out_dir/<name>.npy``: ``loss`` and ``loss_<part>``
+    (float64 scalars), and the updated trainable parameters and their gradients as ``params_sample`` / ``grads_sample``
+    (float32).  The two arrays are the same elements of the parameters taken in ``named_params`` order and laid end to end:
+    all of them when there are at most ``sample``, else a fixed draw of ``sample`` positions (seeded, sorted, duplicates
+    dropped) — the same positions in every run of the same model.  Returns {name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.float64(float(loss.detach()))}
+    for k in sorted(parts):
+        arrays["loss_" + k] = np.float64(float(parts[k].detach()))
+    named_params = list(named_params)
+    sizes = np.array([p.numel() for _, p in named_params], dtype=np.int64)
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    total = int(offs[-1])
+    idx = np.arange(total) if total <= sample else np.unique(np.random.default_rng(seed).integers(0, total, size=sample))
+    ps, gs = [], []
+    for i, (_, p) in enumerate(named_params):
+        lo, hi = np.searchsorted(idx, offs[i]), np.searchsorted(idx, offs[i + 1])
+        if lo == hi:
+            continue
+        local = torch.from_numpy(idx[lo:hi] - offs[i]).to(p.device)
+        ps.append(p.detach().reshape(-1).index_select(0, local).float().cpu())
+        g = p.grad
+        gs.append(torch.zeros(hi - lo) if g is None else g.detach().reshape(-1).index_select(0, local).float().cpu())
+    arrays["params_sample"] = (torch.cat(ps) if ps else torch.zeros(0)).numpy()
+    arrays["grads_sample"] = (torch.cat(gs) if gs else torch.zeros(0)).numpy()
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {k: tuple(np.shape(a)) for k, a in arrays.items()}
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -189,6 +229,13 @@ def parse():
     ap.add_argument("--clips", type=int, default=8, help="clips per GPU per step")
     ap.add_argument("--frames", type=int, default=8, help="T")
     ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, the untimed passes: held shader clock, profiled pass (roofline), alternative "
+                         "arithmetic, bf16s / fp8s legs, CPU baseline, and profiles/bench_full_latest.json.  Without it "
+                         "--profile-steps, --alt-steps, --bf16s-leg, --clips32-legs and --cpu-steps have no effect")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the last timed step's loss, loss parts and a seeded sample of the updated parameters and their "
+                         "gradients as DIR/<name>.npy (rank 0; float32 / float64, about 32 MB in all)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--precision", choices=["fp32", "bf16", "bf16s", "fp8", "fp8s"], default="fp32",
                     help="arithmetic of the TIMED region (default fp32 = BASELINE configs[1]; bf16s = bf16 storage, configs[2] on one GPU; "
@@ -324,6 +371,10 @@ def main():
     args = parse()
     if args.gpus > 1 and "RANK" not in os.environ and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args))
+    if not args.full:          # a plain run: nothing untimed after the timed steps (--schedules is its own opt-in)
+        args.profile_steps = args.alt_steps = 0
+        args.bf16s_leg = args.clips32_legs = "off"
+        args.no_cpu_baseline = True
     # stdout carries exactly ONE line: libraries that print there (gloo's connection banner, RCCL without NCCL_DEBUG_FILE, ...) are
     # sent to stderr for the whole run; the JSON line goes to a duplicate of the original descriptor at the end
     sys.stdout.flush()
@@ -416,9 +467,13 @@ def main():
     import random
     random.seed(13 + rank)
 
+    eager_parts = {}           # the loss parts of the last eager step (--dump-outputs), detached: a step's autograd graph must not
+                               # outlive the step (the next backward would reuse its AccumulateGrad nodes)
+
     def eager_step():
         out = net(image, word_id, word_mask)
-        loss, _ = losses.total_loss(out, bbox, args.size)
+        loss, parts = losses.total_loss(out, bbox, args.size)
+        eager_parts.update({k: v.detach() for k, v in parts.items()})
         if flat is not None:
             flat.zero()
         else:
@@ -478,12 +533,16 @@ def main():
     last_loss = float(last.detach())
     main_sampler_ms = model.sampler_busy_s / args.steps * 1e3      # (CPU time of the worker thread's native draws; the legs below reset the counter)
     max_alloc = torch.cuda.max_memory_allocated(dev) / 2 ** 30
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last, eager_parts if step is eager_step else step.parts,
+                     [(n_, p_) for n_, p_ in model.named_parameters() if p_.requires_grad])
     sclk = None
-    for _ in range(3):                # the clock the card holds UNDER this load: three more (untimed) steps queued on every rank,
-        step()                        # rank 0 reads rocm-smi while they run
-    if rank == 0:
-        sclk = read_sclk_mhz(local_rank)
-    barrier()
+    if args.full:
+        for _ in range(3):            # the clock the card holds UNDER this load: three more (untimed) steps queued on every rank,
+            step()                    # rank 0 reads the shader clock while they run
+        if rank == 0:
+            sclk = read_sclk_mhz(local_rank)
+        barrier()
 
     # ---- untimed passes (every rank runs them, so collectives stay in step) -------------------------------------------
     # from here on the eager step: the profiler wraps each launch in a HIP event pair, which a captured graph cannot hold
@@ -816,14 +875,15 @@ def main():
                     m_ = cr.get("modes", {}).get(mode_)
                     if m_ and "criterion_met_frac" in m_:
                         res["roofline"][mode_ + "_criterion"] = "%d/%d" % (round(m_["criterion_met_frac"] * cr.get("images", 16)), cr.get("images", 16))
-        res["full"] = "profiles/bench_full_latest.json"
-        res["sclk_mhz"] = sclk
+        if args.full or sched:
+            res["full"] = "profiles/bench_full_latest.json"
+        if args.full:
+            res["sclk_mhz"] = sclk
         full["bench_line"] = res
-        for d in (os.path.join(ROOT, "profiles"), os.path.join(ROOT, "gpurun_out")):
+        if "full" in res:
             try:
-                if os.path.isdir(d):
-                    with open(os.path.join(d, "bench_full_latest.json"), "w") as f:
-                        json.dump(full, f, indent=1)
+                with open(os.path.join(ROOT, res["full"]), "w") as f:
+                    json.dump(full, f, indent=1)
             except OSError:
                 pass
         line = compact_line(res)

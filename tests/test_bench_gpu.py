@@ -27,7 +27,7 @@ def _run(args, timeout=420):
 
 
 def test_single_gpu_line_is_compact_and_complete():
-    res, _ = _run(["--steps", "2", "--warmup", "1", "--clips", "2", "--frames", "2", "--size", "256", "--alt-steps", "1", "--cpu-steps", "1"])
+    res, _ = _run(["--full", "--steps", "2", "--warmup", "1", "--clips", "2", "--frames", "2", "--size", "256", "--alt-steps", "1", "--cpu-steps", "1"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
               "data", "config", "roofline", "cpu_baseline"):
         assert k in res, k
@@ -62,7 +62,7 @@ def test_one_rank_rccl_group_behind_the_graph_replay():
     the run without a process group puts it; the flat reducer (gradients accumulated into views of one buffer) within 1e-4 — this
     2-image training is chaotic (an ulp grows a thousandfold per step), so an early step is compared."""
     common = ["--steps", "1", "--warmup", "0", "--clips", "1", "--frames", "2", "--size", "256", "--no-cpu-baseline", "--alt-steps", "0",
-              "--profile-steps", "0"]
+              "--profile-steps", "0", "--full"]
     base, _ = _run(common)
     flat, err = _run(common + ["--force-ddp", "--reducer", "flat", "--graph", "on"])
     assert flat["config"]["ranks_seen"] == 1 and flat["config"]["reducer"] == "flat" and "hipGraph" in flat["config"]["step"]
@@ -80,7 +80,7 @@ def test_bf16_storage_run_with_a_bf16_gradient_buffer_on_the_wire():
     RCCL group whose flat all-reduce moves a bf16 copy of the gradient buffer (cast, collective, cast back): the line says what ran,
     the loss stays of the order the un-reduced bf16 run puts it (the gradients are rounded to bf16 on the wire)."""
     common = ["--steps", "1", "--warmup", "0", "--clips", "1", "--frames", "2", "--size", "256", "--no-cpu-baseline", "--alt-steps", "0",
-              "--profile-steps", "0", "--precision", "bf16s"]
+              "--profile-steps", "0", "--full", "--precision", "bf16s"]
     base, _ = _run(common)
     assert base["dtype"] == "bf16" and "bf16 storage" in base["config"]["arith"] and "hipGraph" in base["config"]["step"]
     fp32, _ = _run(common[:-2])
@@ -89,3 +89,23 @@ def test_bf16_storage_run_with_a_bf16_gradient_buffer_on_the_wire():
     flat, _ = _run(common + ["--force-ddp", "--reducer", "flat", "--graph", "on"])
     assert flat["config"]["reducer"] == "flat" and flat["config"]["collectives"] >= 6 and flat["dtype"] == "bf16"
     assert 0.2 < flat["loss"] / base["loss"] < 5.0, (flat["loss"], base["loss"])
+
+
+def test_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full the run is the timed steps and the line: no untimed pass, no roofline, no CPU baseline, no full JSON.
+    --dump-outputs writes what the last timed step computed: the dumped loss is the line's loss, bit for bit."""
+    import numpy as np
+    out = tmp_path / "dump"
+    res, _ = _run(["--steps", "3", "--warmup", "1", "--clips", "1", "--frames", "2", "--size", "256", "--dump-outputs", str(out)])
+    assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and "hipGraph" in res["config"]["step"]
+    assert abs(res["value"] - 3 * 1000.0 / (3 * res["ms_per_step"])) < 1e-6 * res["value"] + 1e-9
+    for k in ("roofline", "cpu_baseline", "alt", "full", "sclk_mhz"):
+        assert k not in res, k
+    names = {p.stem for p in out.iterdir()}
+    assert names == {"loss", "loss_yolo", "loss_rank", "loss_interframe", "loss_cross", "loss_loc", "params_sample", "grads_sample"}, names
+    arrays = {n: np.load(out / (n + ".npy")) for n in names}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert sum(a.nbytes for a in arrays.values()) <= 64 * 2 ** 20
+    assert float(arrays["loss"]).hex() == res["loss_hex"]
+    assert arrays["params_sample"].shape == arrays["grads_sample"].shape and arrays["params_sample"].size > 2 ** 21
+    assert np.abs(arrays["grads_sample"]).max() > 0

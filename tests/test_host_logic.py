@@ -317,6 +317,31 @@ def test_bench_line_keeps_north_star_numbers_at_benchmark_size():
     assert out["roofline"]["bf16s_ms_per_step"] == 57.75
 
 
+def test_bench_dump_outputs_samples_fixed_positions(tmp_path):
+    """bench.dump_outputs: scalars as float64, parameters and gradients as float32; every element while they fit the sample, else
+    the same seeded positions in every call (sorted, within bounds), parameters and gradients taken at the same positions."""
+    import bench
+    torch.manual_seed(0)
+    m = torch.nn.Sequential(torch.nn.Linear(7, 5), torch.nn.Linear(5, 3))
+    m(torch.randn(4, 7)).sum().backward()
+    m[1].bias.grad = None                                       # a parameter without a gradient dumps zeros
+    named = list(m.named_parameters())
+    flat_p = torch.cat([p.detach().reshape(-1) for _, p in named]).numpy()
+    flat_g = torch.cat([torch.zeros(p.numel()) if p.grad is None else p.grad.reshape(-1) for _, p in named]).numpy()
+    loss, parts = torch.tensor(2.5, requires_grad=True) * 1, {"b": torch.tensor(1.0), "a": torch.tensor(1.5)}
+    shapes = bench.dump_outputs(str(tmp_path / "all"), loss, parts, named)
+    assert shapes == {"loss": (), "loss_a": (), "loss_b": (), "params_sample": (flat_p.size,), "grads_sample": (flat_p.size,)}
+    ld = lambda d, n: np.load(tmp_path / d / (n + ".npy"))
+    assert ld("all", "loss").dtype == np.float64 and float(ld("all", "loss")) == 2.5 and float(ld("all", "loss_a")) == 1.5
+    assert ld("all", "params_sample").dtype == np.float32 and np.array_equal(ld("all", "params_sample"), flat_p)
+    assert np.array_equal(ld("all", "grads_sample"), flat_g) and not ld("all", "grads_sample")[-3:].any()
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), loss, parts, named, sample=16)
+    idx = np.unique(np.random.default_rng(0).integers(0, flat_p.size, size=16))
+    for n, ref in (("params_sample", flat_p), ("grads_sample", flat_g)):
+        assert np.array_equal(ld("s1", n), ld("s2", n)) and np.array_equal(ld("s1", n), ref[idx])
+
+
 def test_graph_queue_model_on_a_small_dag(tmp_path):
     """tools/graph_sched.py on a hand-written dump in the runtime's format: depth first from the root, the first dependent of a node keeps
     its queue, the k-th gets queue + k (mod 4), a node reached twice keeps its first queue — the rule the captured step's stream
