@@ -8,7 +8,9 @@ to drive ``grounding_model`` without the reference's data pipeline (SURVEY.md §
   * ``save_checkpoint`` / ``load_checkpoint`` / ``load_pretrain``   the reference's ``.pth.tar`` dict
     (train_DCNet.py:255-263, 485-514) including the ``module.`` key prefix left by DDP wrappers
 
-``python -m dcnet_amd.train --steps 20`` runs a short synthetic-data training loop on one GPU.
+``python -m dcnet_amd.train --steps 20`` runs a short synthetic-data training loop on one GPU; with ``--raw-frames`` every step's
+``image`` / ``bbox`` come from synthetic uint8 frames of mixed sizes (1280x720 and 500x375) through the on-device clip
+preprocessing (``dcnet_amd.prep.prepare_clips``: flip, HSV, letterbox, affine, normalisation), as real decoded frames would.
 """
 from __future__ import annotations
 
@@ -134,6 +136,7 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     ap.add_argument("--frames", type=int, default=2)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--raw-frames", action="store_true", help="feed uint8 frames through dcnet_amd.prep every step")
     args = ap.parse_args(argv)
     from .model import grounding_model
     from .parallel import freeze_gradless
@@ -146,8 +149,20 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     n = args.clips * args.frames
     image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, args.size, seed=1))
     bbox = synth_boxes(n, args.size, seed=1).to(dev)
+    if args.raw_frames:
+        import numpy as np
+        from .prep import prepare_clips
+        rs = np.random.RandomState(1)
+        frames = [[rs.randint(0, 256, size=((720, 1280, 3) if (c + t) % 2 == 0 else (375, 500, 3)), dtype=np.uint8)
+                   for t in range(args.frames)] for c in range(args.clips)]
+        src_boxes = [[[60, 40, 300, 330]] * args.frames for _ in range(args.clips)]
+        phrases = [["the object on the left"] * args.frames for _ in range(args.clips)]
+        prep_rng = random.Random(1)               # the pipeline's own draws: Python's global stream stays the model's
     for it in range(args.steps):
         adjust_learning_rate(opt, it, args.lr, args.steps, 0.9)
+        if args.raw_frames:
+            res = prepare_clips(frames, src_boxes, phrases, args.size, True, rng=prep_rng, out=image)
+            bbox.copy_(res.bbox)
         loss, parts = train_step(model, opt, image, word_id, word_mask, bbox, args.size)
         if it % 5 == 0 or it == args.steps - 1:
             print(f"step {it:3d} loss {float(loss):9.4f}  " + " ".join(f"{k} {float(v):.4f}" for k, v in parts.items()))

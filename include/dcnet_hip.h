@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 308
+#define DCN_ABI_VERSION 309
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -552,6 +552,34 @@ int dcn_post_topk(const float* const* outbox, const float* const* feat, const in
  * :266-269).  fused [n][k] = sum_r softmax_r(max_i <c, ref_r,i>) * ref_score[r][argmax_i], best [n] = first arg-max of fused. */
 int dcn_post_fusion(const float* center, const float* ref, const float* ref_score, const unsigned char* valid, int n, int k, int r,
                     int e, float* fused, int64_t* best, void* stream);
+
+/* ---- clip preprocessing: letterbox, flip, HSV and affine warp of decoded frames (ABI 309) ---------------------------- */
+/* One record per frame of the batch (host-built by dcnet_amd/prep.py; dataset/vid_loader.py:333-395 draws the parameters,
+ * utils/transforms.py:123-137 letterbox, :139-185 random_affine, :236-275 wrap_points is box geometry and stays on the host).
+ * Plain old data, 96 bytes, no implicit padding. */
+typedef struct DcnPrepJob {
+  int64_t src_off;      /* byte offset of the frame in `src`: RGB, HWC, uint8, rows of 3*w bytes, no row padding */
+  int32_t h, w;         /* source frame size */
+  int32_t rh, rw;       /* letterboxed content size (round(h*ratio), round(w*ratio)); resized with the INTER_AREA rules */
+  int32_t top, left;    /* pad above / left of the content (round(dh - 0.1), round(dw - 0.1)) */
+  int32_t flip;         /* 1: mirror the source horizontally first (vid_loader.py:351-355) */
+  int32_t hsv;          /* 1: 8-bit RGB->HSV->RGB round trip with V scaled by a_v (vid_loader.py:357-373) */
+  float a_v;            /* V multiplier (float32 of the drawn value) */
+  int32_t warp;         /* 0: identity (evaluation: the output is the letterboxed frame); 1: affine warp through minv */
+  double minv[6];       /* inverse of random_affine's M, rows 0-1: output pixel (x, y) -> letterbox X = minv[0]x + minv[1]y + minv[2],
+                           Y = minv[3]x + minv[4]y + minv[5] */
+} DcnPrepJob;
+/* Workspace bytes of dcn_clip_prep: n * size * size * 4. */
+int64_t dcn_clip_prep_ws(int n, int size);
+/* n frames of any sizes -> out [n][3][size][size] fp32 NCHW (ToTensor + Normalize(mean .485/.456/.406, std .229/.224/.225),
+ * train_DCNet.py:420-425), frames of a clip consecutive.  Two launches whatever n: letterbox (flip, HSV, INTER_AREA resize, pad
+ * (124,116,104)) into ws as RGBx [n][size][size][4] uint8 — which the caller may read back as the letterbox stage — then
+ * warp (bilinear, 1/32-pixel source grid, 15-bit weights, border (124,116,104)) + normalisation.  u8_out: NULL or
+ * [n][size][size][3] uint8, the warped frames before normalisation.  jobs: device copy of the n records; jobs_host: the same
+ * records in host memory (validated here: sizes, pads, every frame inside src_bytes).  size: a multiple of 32.  The pixel
+ * rules are integer-specified (clip preprocessing); bit-exactness with OpenCV is not claimed. */
+int dcn_clip_prep(const uint8_t* src, int64_t src_bytes, const DcnPrepJob* jobs, const DcnPrepJob* jobs_host, int n, int size,
+                  uint8_t* ws, float* out, uint8_t* u8_out, void* stream);
 
 /* ---- location module core (rank-8 form of model/DCNet_model.py:581-594) ------------------------- */
 /* loc[n,i] = < normalize_c( relu( E[i,:8] . Mp[n,:8,:c] + bp[:c] ) ), q[n,:c] >   for i < p, c == 512.
