@@ -17,9 +17,9 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(HERE, "libdcnet_hip.so")
 SOURCES = ["igemm.hip", "conv3.hip", "conv3x.hip", "conv1.hip", "nconv.hip", "stem.hip", "conv.hip", "wgrad.hip", "wgrad3.hip", "wgrad9.hip", "bn.hip", "layout.hip", "coattn.hip", "gemm3.hip", "score.hip", "gemm.hip", "locmod.hip", "optim.hip", "wprep.hip", "phrase.hip", "head.hip", "sample.hip", "loss.hip", "lstm.hip", "fusion.hip", "post.hip", "b16.hip", "conv2b.hip", "prep.hip",
-           "sampling.cpp", "capi.cpp"]
+           "sampling.cpp", "capi.cpp", "tuning.cpp"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function", "-Werror=array-bounds"]
-FLAGS += os.environ.get("DCN_EXTRA_FLAGS", "").split()      # experiment builds, e.g. -DC3_ABL=1 (timing ablations of conv3.hip)
+FLAGS += os.environ.get("DCN_EXTRA_FLAGS", "").split()      # experiment builds, e.g. -DDCN_ABL=1 -DC3_ABL=1 (timing ablations: README.md, Experiments)
 if os.environ.get("DCN_WGRAD_KP"):          # experiment knob: pixels per K-step of the weight-gradient kernel
     FLAGS.append("-DWGRAD_KP=" + os.environ["DCN_WGRAD_KP"])
 
@@ -39,10 +39,11 @@ def flags_key() -> str:
     return hashlib.sha256(" ".join(FLAGS).encode()).hexdigest()[:12]
 
 
-def built_flags_key() -> str:
-    """The flags key of the objects libdcnet_hip.so was linked from ('' if never built by this script)."""
+def built_flags_key(objdir: str = os.path.join(HERE, "build")) -> str:
+    """The flags key of the objects libdcnet_hip.so was linked from ('' if never built by this script; 'building:<key>' if the
+    last build with that key failed or was interrupted: never equal to a ``flags_key()``)."""
     try:
-        with open(os.path.join(HERE, "build", "FLAGS.stamp")) as fh:
+        with open(os.path.join(objdir, "FLAGS.stamp")) as fh:
             return fh.read().strip()
     except OSError:
         return ""
@@ -55,15 +56,14 @@ def _stale(target: str, deps) -> bool:
     return any(os.path.getmtime(d) > t for d in deps)
 
 
-def build(force: bool = False, verbose: bool = True) -> str:
+def build(force: bool = False, verbose: bool = True, objdir: str = os.path.join(HERE, "build")) -> str:
     hipcc = _hipcc()
     srcs = [s for s in SOURCES if os.path.exists(os.path.join(CSRC, s))]
     headers = [os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h")]
     headers.append(os.path.join(os.path.dirname(HERE), "include", "dcnet_hip.h"))
-    objdir = os.path.join(HERE, "build")
     os.makedirs(objdir, exist_ok=True)
     stamp = os.path.join(objdir, "FLAGS.stamp")
-    if built_flags_key() != flags_key():        # other flags than the objects were compiled with: every object is stale
+    if built_flags_key(objdir) != flags_key():  # other flags than the objects were compiled with, or a build that did not finish: every object is stale
         force = True
     jobs = []
     for s in srcs:
@@ -82,6 +82,9 @@ def build(force: bool = False, verbose: bool = True) -> str:
             print(r.stderr, file=sys.stderr)
         return name
 
+    if jobs or force:                           # from here until the link succeeded the objects belong to no finished build
+        with open(stamp, "w") as fh:
+            fh.write("building:" + flags_key() + "\n")
     if jobs:
         with ThreadPoolExecutor(max_workers=4) as ex:
             for name in ex.map(run, jobs):

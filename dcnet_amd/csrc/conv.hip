@@ -59,7 +59,7 @@ int launch_presplit(const float* src, float* dst, int64_t numel, const uint32_t*
   return DCN_OK;
 }
 
-int g_merge_classes = 1;    // dcn_set_tuning("merge", 0): stride-2 data gradients as four launches again
+DCN_KNOB(g_merge_classes, "merge", 1, "conv.hip: parity classes of a stride-2 data gradient in one launch (0 = four launches)");
 
 void base_params(IgemmParams& p) {
   p = IgemmParams{};
@@ -68,11 +68,8 @@ void base_params(IgemmParams& p) {
 
 }  // namespace
 
-void conv_set_merge(int v) { g_merge_classes = v; }
-int g_n1_b16 = 1;           // dcn_set_tuning("Nb16", 0): bf16-storage 32 <-> 64 3x3 layers back on the gathered tiles of conv1.hip
-void conv_set_n1_b16(int v) { g_n1_b16 = v; }
-int g_d2_b16 = 1;           // dcn_set_tuning("Db16", 0): bf16-storage stride-2 data gradients of the narrow layers back on the gathered parity classes
-void conv_set_d2_b16(int v) { g_d2_b16 = v; }
+DCN_KNOB(g_n1_b16, "Nb16", 1, "conv.hip: bf16-storage 32 <-> 64 3x3 layers on the register-bank kernels of nconv.hip (0 = gathered tiles of conv1.hip)");
+DCN_KNOB(g_d2_b16, "Db16", 1, "conv.hip: bf16-storage stride-2 data gradients of the narrow layers on nconv.hip (0 = gathered parity classes)");
 
 extern "C" int dcn_conv2d_stats_rows(int n, int h, int wd, int cout, int ksize, int stride) {
   const int pad = (ksize - 1) / 2;

@@ -655,9 +655,10 @@ __global__ __launch_bounds__(256, 2) void conv1b_kernel(const IgemmParams p) {
     }
 }
 
-int g_conv1 = 1;          // dcn_set_tuning("1x1dma", 0): back on the implicit-GEMM tiles of igemm.hip; 2: 1x1 launches only
-int g_conv1_stages = 32;  // dcn_set_tuning("1stages", 10 * SA + SB): ring depths.  Default 3 activation + 2 filter K-steps = 40 KB at the 128 x 128 tile:
-                          // FOUR workgroups per CU (measured per layer, tools/bench_convs.py --set 1stages=..: 32 < 33 < 42 < 44 ~ 63 << 84: occupancy beats ring depth)
+DCN_KNOB(g_conv1, "1x1dma", 1, "conv1.hip: NT launches with a pre-split bank on the LDS-DMA kernel (0 = implicit-GEMM tiles of igemm.hip; 2 = 1x1 launches only)");
+DCN_KNOB(g_conv1_stages, "1stages", 32, "conv1.hip: ring depths of the 128 x 128 tile, 10 * SA + SB (32 | 33 | 42 | 44 | 63)");
+// Default 3 activation + 2 filter K-steps = 40 KB at the 128 x 128 tile:
+// FOUR workgroups per CU (measured per layer, tools/bench_convs.py --set 1stages=..: 32 < 33 < 42 < 44 ~ 63 << 84: occupancy beats ring depth)
 
 template <int SA, int SB, int NI, int MI>
 int launch1(const IgemmParams& p, hipStream_t stream) {
@@ -695,26 +696,17 @@ int launch1_ring(const IgemmParams& p, hipStream_t stream) {
 }
 
 // (MI, NI) for a launch, 0 = not on this kernel.  gran = rows per BatchNorm partial the caller sized its buffer for (128 | 256).
-int g_conv1_fill = 0;     // dcn_set_tuning("1fill", n): grids of fewer 128 x 128 workgroups than n take 128 x 64 tiles (twice the workgroups).
-                          // Measured on the 13x13 maps (340 workgroups for 1024 slots), tools/bench_convs.py --ab 1fill=0 --ab-default 512:
-                          // 1024->512 0.058 -> 0.064 ms, 512->512 data gradient 0.039 -> 0.048: half the MFMAs per barrier costs more than
-                          // the second round of workgroups brings; off.
+DCN_KNOB(g_conv1_wide, "1wide", 1024, "conv1.hip: 128 x 256 tiles from that many workgroups on (0 = off)");
+// (a wave owns 32 rows x 256 filters: half the split work and
+// 0.75 instead of 0.83 fragment reads per MFMA) where the filter count allows and that many workgroups remain.
+// tools/bench_convs.py --set 1wide=0|1, forward / data gradient: 1024->512 @52 0.806 -> 0.707 / 0.757 -> 0.691 ms,
+// 512->512 @52 0.419 -> 0.372 / 0.433 -> 0.397, 256->512 @52 0.267 -> 0.235 / 0.225 -> 0.205; the short grids lose
+// (512->256 @26, 338 workgroups: 0.062 -> 0.065; 1024->512 @13, 170: 0.070 -> 0.086): from 1024 workgroups on
 
-int g_conv1_wide = 1024;  // dcn_set_tuning("1wide", min workgroups; 0 = off): 128 x 256 tiles (a wave owns 32 rows x 256 filters: half the split work and
-                          // 0.75 instead of 0.83 fragment reads per MFMA) where the filter count allows and that many workgroups remain.
-                          // tools/bench_convs.py --set 1wide=0|1, forward / data gradient: 1024->512 @52 0.806 -> 0.707 / 0.757 -> 0.691 ms,
-                          // 512->512 @52 0.419 -> 0.372 / 0.433 -> 0.397, 256->512 @52 0.267 -> 0.235 / 0.225 -> 0.205; the short grids lose
-                          // (512->256 @26, 338 workgroups: 0.062 -> 0.065; 1024->512 @13, 170: 0.070 -> 0.086): from 1024 workgroups on
-
-int g_conv1_tall = 0;      // dcn_set_tuning("1tall", min workgroups; 0 = off): 256 x 128 tiles on FOUR waves (a wave owns 64 rows x 128 filters: 6 KB of fragment
-                          // reads per 12 MFMAs instead of 10, two workgroups per CU) for launches without BatchNorm partials
 int conv1_shape(const IgemmParams& p, int gran) {
   int ni = p.Co % 128 == 0 ? 4 : (p.Co % 64 == 0 ? 2 : (p.Co % 32 == 0 ? 1 : 0));
   if (!ni) return 0;
-  if (g_conv1_tall && ni == 4 && !p.stats && (long long)cdiv(p.M, 256) * (p.Co / 128) >= g_conv1_tall) return 24;
   if (g_conv1_wide && p.Co % 256 == 0 && (!p.stats || gran == 128) && (long long)cdiv(p.M, 128) * (p.Co / 256) >= g_conv1_wide) return 18;
-  // (experiment knob, off by default — see g_conv1_fill)
-  if (ni == 4 && (!p.stats || gran == 128) && (long long)cdiv(p.M, 128) * (p.Co / 128) < g_conv1_fill) ni = 2;
   int mi;
   if (p.stats) { mi = gran == 128 ? 1 : (gran == 256 ? 2 : 0); }
   else mi = ni == 4 ? 1 : 2;
@@ -723,12 +715,10 @@ int conv1_shape(const IgemmParams& p, int gran) {
 }
 
 // bf16 storage: (MI, NI) of a launch; 0 = no tile (Co not a multiple of 32).  One BatchNorm partial row per 128 MI output rows.
-int g_conv1b_wide = 1024; // dcn_set_tuning("bwide", min workgroups; 0 = off): 128 x 256 tiles from that many workgroups on
-int g_conv1b_tall = 0;    // dcn_set_tuning("btall", min workgroups; 0 = off): 256 x 128 tiles (a wave owns 64 rows x 128 filters)
+DCN_KNOB(g_conv1b_wide, "bwide", 1024, "conv1.hip: bf16- / fp8-storage 128 x 256 tiles from that many workgroups on (0 = off)");
 int conv1b_shape(int M, int Co) {
   if (Co % 32 != 0) return 0;
   if (g_conv1b_wide && Co % 256 == 0 && (long long)cdiv(M, 128) * (Co / 256) >= g_conv1b_wide) return 18;
-  if (g_conv1b_tall && Co % 128 == 0 && (long long)cdiv(M, 256) * (Co / 128) >= g_conv1b_tall) return 24;
   if (Co % 128 == 0) return 14;
   if (Co % 64 == 0) return 12;
   return 21;
@@ -755,12 +745,6 @@ int launch1b(const IgemmParams& p, hipStream_t stream) {
 }
 
 }  // namespace
-
-void conv1_set_tuning(int key, int value) {
-  if (key == 6) { g_conv1_tall = value; return; }
-  if (key == 0) g_conv1 = value; else if (key == 1) g_conv1_stages = value; else if (key == 3) g_conv1_wide = value;
-  else if (key == 4) g_conv1b_wide = value; else if (key == 5) g_conv1b_tall = value; else g_conv1_fill = value;
-}
 
 // shape part of the decision.  The kernel only takes launches that igemm.hip would run on its f16-split tiles WITH the pre-split
 // bank (b_scale set by conv.hip under igemm_will_presplit): the arithmetic — which products, in which order — is then the same and
@@ -791,7 +775,6 @@ int conv1_launch(const IgemmParams& p, int gran, hipStream_t stream) {
   switch (conv1_shape(p, gran)) {
     case 18: return launch1_ring<8, 1>(p, stream);
     case 14: return launch1_ring<4, 1>(p, stream);
-    case 24: return launch1_ring<4, 2>(p, stream);
     case 12: return launch1_ring<2, 1>(p, stream);
     case 22: return launch1_ring<2, 2>(p, stream);
     case 21: return launch1_ring<1, 2>(p, stream);
@@ -819,7 +802,7 @@ int conv1b_launch(const IgemmParams& p, int out_f32, hipStream_t stream) {
   if (conv3b_takes(p)) return conv3b_launch(p, out_f32, stream);                          // 3x3 stride 1: the strip kernel (every row staged once, not nine times)
   // conv1b_grid_m() sized the caller's BatchNorm partial rows from conv3b_bm() alone: a stride-1 3x3 launch that conv3b_bm accepts and
   // conv3b_takes then rejects (a tensor beyond the 2 GiB window) must not fall through to a 128-row tile writing cdiv(M, 128) rows into a
-  // buffer sized for cdiv(M, 256) (round-5 advice; reachable only with dcn_set_tuning("3h16", 1))
+  // buffer sized for cdiv(M, 256) (round-5 advice; reachable only with "3h16" = 1)
   if (p.stats && p.ntaps == 9 && p.isy == 1 && p.isx == 1 && p.osy == 1 && p.osx == 1 && p.dense_out && conv3b_bm(p.M, p.Co, p.Wi) != 0) {
     dcn_set_error("conv1b: the strip kernel sized this launch's BatchNorm partials but cannot take it (tensor beyond its 2 GiB window)");
     return DCN_ERR_ARG;
@@ -828,7 +811,6 @@ int conv1b_launch(const IgemmParams& p, int out_f32, hipStream_t stream) {
   switch (conv1b_shape(p.M, p.Co)) {
     case 18: return out_f32 ? launch1b<8, 1, true>(p, stream) : launch1b<8, 1, false>(p, stream);
     case 14: return out_f32 ? launch1b<4, 1, true>(p, stream) : launch1b<4, 1, false>(p, stream);
-    case 24: return out_f32 ? launch1b<4, 2, true>(p, stream) : launch1b<4, 2, false>(p, stream);
     case 12: return out_f32 ? launch1b<2, 1, true>(p, stream) : launch1b<2, 1, false>(p, stream);
     case 21: return out_f32 ? launch1b<1, 2, true>(p, stream) : launch1b<1, 2, false>(p, stream);
     default: dcn_set_error("conv1b: Co=%d is not a multiple of 32", p.Co); return DCN_ERR_ARG;
@@ -854,7 +836,6 @@ int conv1q_launch(const IgemmParams& p, int out_f32, hipStream_t stream) {
   switch (conv1b_shape(p.M, p.Co)) {
     case 18: return out_f32 ? launch1b<8, 1, true, true>(p, stream) : launch1b<8, 1, false, true>(p, stream);
     case 14: return out_f32 ? launch1b<4, 1, true, true>(p, stream) : launch1b<4, 1, false, true>(p, stream);
-    case 24: return out_f32 ? launch1b<4, 2, true, true>(p, stream) : launch1b<4, 2, false, true>(p, stream);
     case 12: return out_f32 ? launch1b<2, 1, true, true>(p, stream) : launch1b<2, 1, false, true>(p, stream);
     case 21: return out_f32 ? launch1b<1, 2, true, true>(p, stream) : launch1b<1, 2, false, true>(p, stream);
     default: dcn_set_error("conv1q: Co=%d is not a multiple of 32", p.Co); return DCN_ERR_ARG;

@@ -261,7 +261,7 @@ __global__ __launch_bounds__(512, 1) void conv2b_kernel(const IgemmParams p) {
     }
 }
 
-int g_conv2b = 256;       // dcn_set_tuning("2btile", min tiles; 0 = off; negative: also the 1-tap launches): multi-tap launches with that many 256 x 256 tiles run here
+DCN_KNOB(g_conv2b, "2btile", 256, "conv2b.hip: multi-tap bf16-storage launches with at least that many 256 x 256 tiles run here (0 = off; negative = the 1-tap launches too)");
 
 template <bool O32>
 int launch2b(const IgemmParams& p, hipStream_t stream) {
@@ -280,8 +280,6 @@ int launch2b(const IgemmParams& p, hipStream_t stream) {
 }
 
 }  // namespace
-
-void conv2b_set_tuning(int v) { g_conv2b = v; }
 
 // does a bf16-storage launch of M rows x Co filters run on the 256 x 256 tile?  (a function of the shape and the knob only: the caller
 // sizes its BatchNorm partial rows with it)

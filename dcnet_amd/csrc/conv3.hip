@@ -52,7 +52,7 @@ __device__ __forceinline__ int row32(int pos, int half) { return pos * 32 + (((h
 // NP = 2: fp32-accurate f16 two-piece split (pre-split filter bank, three MFMAs per product).  NP = 1: bf16 operands, one plane,
 // one MFMA per product — the bf16-operand mode (BASELINE.json configs[2]); the filter bank arrives converted to bf16
 // (IgemmParams::wt16, dcn_prepare_filters), activations are rounded when the strip is staged.
-// ABL (builds with -DC3_ABL=1 only, dcn_set_tuning("3abl", bits); results are WRONG, timing experiments): 1 = no filter loads in the loop,
+// ABL (builds with -DC3_ABL=1 only, "3abl" = bits; results are WRONG, timing experiments): 1 = no filter loads in the loop,
 // 2 = no strip loads in the loop, 4 = no filter / strip LDS stores in the loop, 8 = no epilogue, 16 = one of the three MFMA terms
 #ifndef C3_ABL
 #define C3_ABL 0
@@ -543,11 +543,10 @@ __global__ __launch_bounds__(64 * WM * WN, 2) void conv3_kernel(const IgemmParam
   }
 }
 
-int g_conv3 = 1;          // dcn_set_tuning("3x3strip", 0): 3x3 stride-1 layers back on the implicit-GEMM tile
-int g_conv3_bm = 0;       // dcn_set_tuning("3bm", 128|256): force the strip kernel's M tile (0 = automatic)
-int g_conv3_abl = 0;      // dcn_set_tuning("3abl", bits): timing ablations (C3_ABL builds only)
-int g_conv3_m16 = 1;      // dcn_set_tuning("3m16", 0|1|2): conv3x.hip (16x16x32 MFMAs) for the launches that take the 256-row tile (1) / for every strip launch it fits (2)
-int g_conv3_ls = 1;       // dcn_set_tuning("3ls", 0): every global load of an iteration at its start again (A/B switch; LS = 1 measured 1-6 % faster per layer)
+DCN_KNOB(g_conv3, "3x3strip", 1, "conv3.hip: 3x3 stride-1 layers on the strip kernel (0 = implicit-GEMM tile)");
+DCN_KNOB(g_conv3_bm, "3bm", 0, "conv3.hip: force the strip kernel's M tile (128 | 256; 0 = automatic)");
+DCN_KNOB(g_conv3_abl, "3abl", 0, "conv3.hip: timing ablations of the strip kernel, bits (results WRONG)", nullptr, "-DC3_ABL=1", C3_ABL != 0);
+DCN_KNOB(g_conv3_m16, "3m16", 1, "conv3.hip: conv3x.hip (16x16x32 MFMAs) for the launches that take the 256-row tile (0 = never; 2 = every strip launch it fits)");
 
 template <int WM, int WN, int A_LD, int NP = 2, int ABL = 0, int LS = 0, bool IN16 = false, bool O32 = false>
 int launch3(const IgemmParams& p, int gran, hipStream_t stream) {
@@ -586,8 +585,7 @@ int launch3_ld(const IgemmParams& p, int gran, hipStream_t stream) {
     default: break;
   }
 #endif
-  if (g_conv3_ls) return launch3<WM, WN, A_LD_MAX, 2, 0, 1>(p, gran, stream);
-  return launch3<WM, WN, A_LD_MAX>(p, gran, stream);
+  return launch3<WM, WN, A_LD_MAX, 2, 0, 1>(p, gran, stream);     // LS = 1: loads spread over the iteration (1-6 % faster per layer than all at its start)
 }
 
 // tile choice: 256 pixels x 128 filters (8 waves, one workgroup per CU) or 128 x 128 (4 waves, two per CU), see below
@@ -608,11 +606,6 @@ int conv3_tile(const IgemmParams& p, int gran, int* a_need) {
 }
 
 }  // namespace
-
-void conv3_set_tuning(int key, int value) {
-  if (key == 0) g_conv3 = value; else if (key == 1) g_conv3_bm = value; else if (key == 2) g_conv3_abl = value; else if (key == 4) g_conv3_m16 = value;
-  else g_conv3_ls = value;
-}
 
 // can this launch run on the strip kernel?  (gran = rows per statistics partial the caller sized its buffer for)
 bool conv3_applicable(const IgemmParams& p, int precision, int gran) {
@@ -644,8 +637,7 @@ bool conv3_applicable(const IgemmParams& p, int precision, int gran) {
 // 0.148 / 0.139 -> 0.159, 512->1024 @13 0.137 -> 0.155 / 0.173 -> 0.172, 64->128 @104 0.184 -> 0.253 / 0.227 -> 0.229, 512->512 @52 0.851 -> 0.927 /
 // 0.845 -> 0.906 — it LOSES: with one MFMA per product (not three) the strip loop's 12 MFMAs per wave between barriers and its register-staged
 // loads cost more than the nine-fold gather of conv1b's LDS-DMA rings, which mostly hits L2.  Kept behind the knob with its exact-model tests.
-int g_conv3b = 0;         // dcn_set_tuning("3h16", 1): bf16-storage 3x3 stride-1 launches on the strip kernel
-void conv3b_set_tuning(int v) { g_conv3b = v; }
+DCN_KNOB(g_conv3b, "3h16", 0, "conv3.hip: 1 = bf16-storage 3x3 stride-1 launches on the strip kernel (0 = gathered tiles)");
 
 // M-tile (pixels) of a bf16-storage strip launch, 0 = not on this kernel.  A function of the shape and the knob only: the caller sizes its
 // BatchNorm partial rows (one per M-tile) with it.  Wi = map width of the (stride-1, 3x3) launch.

@@ -484,9 +484,6 @@ bool conv3x_takes(const IgemmParams& p, int gran) {
   return (long long)S * p.ldi * 4 < 0x7FFFFFF0LL && (long long)p.Co * p.ldw * 4 < 0x7FFFFFF0LL;
 }
 
-int g_conv3x_dma = 1;     // dcn_set_tuning("3dma", 0): filter tiles through registers again (A/B switch)
-void conv3x_set_tuning(int v) { g_conv3x_dma = v; }
-
 int conv3x_launch(const IgemmParams& p, int gran, hipStream_t stream) {
   const int S = XBM + 2 * p.Wi + 2;
   const size_t lds = (size_t)4 * XPA + (size_t)2 * XSTAGE;
@@ -494,14 +491,12 @@ int conv3x_launch(const IgemmParams& p, int gran, hipStream_t stream) {
   static DcnPerDeviceFlag attr_once;
   if (attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
   }
   const int gm = cdiv(p.M, XBM), gn = cdiv(p.Co, XBN);
   const double k_alg = 9.0 * p.Ci;
   const double alg_bytes = 4.0 * ((double)p.N * p.Hi * p.Wi * p.Ci + (double)p.Co * k_alg + (double)p.M * p.Co * epilogue_reads(p));
   const int pid = prof_begin(51, 2.0 * (double)p.M * p.Co * k_alg, stream, alg_bytes);
-  if (g_conv3x_dma) hipLaunchKernelGGL(conv3x_kernel<true>, dim3(gm * gn), dim3(XNT), lds, stream, p, S, gran);
-  else hipLaunchKernelGGL(conv3x_kernel<false>, dim3(gm * gn), dim3(XNT), lds, stream, p, S, gran);
+  hipLaunchKernelGGL(conv3x_kernel<true>, dim3(gm * gn), dim3(XNT), lds, stream, p, S, gran);
   prof_end(pid, stream);
   DCN_CHECK_LAUNCH("conv3x");
   return DCN_OK;

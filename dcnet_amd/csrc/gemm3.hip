@@ -26,7 +26,9 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
 typedef __attribute__((address_space(3))) void lds_void;
 
-#define G3_ABL 0                                 // 1: the timing-only ablations of dcn_set_tuning("Gemm3", 1 + 16 * bits) are compiled in
+#ifndef G3_ABL
+#define G3_ABL 0                                 // -DG3_ABL=1: the timing-only ablations of "Gemm3" = 1 + 16 * bits are compiled in (results WRONG)
+#endif
 constexpr unsigned G3_OOB = 0x80000000u;
 constexpr int G3_BM = 256, G3_BN = 256, G3_STAGES = 4;
 constexpr int G3_TILE = 256 * 64;                 // bytes of one operand tile of a K-slice (R: [256 rows][64 B]; T: [16 k][1024 B])
@@ -53,7 +55,7 @@ struct G3Params {
   int accumulate;
   const unsigned* amax_a; const unsigned* amax_b;
   unsigned* amax_out;                             // optional: abs-max word of what is stored
-  int var;                                        // schedule variant (dcn_set_tuning("Gemm3", 1 + 256 * v))
+  int var;                                        // schedule variant ("Gemm3" = 1 + 256 * v)
   int abl;                                        // timing-only ablations (wrong results): 1 no DMA, 2 no fragment reads, 4 no MFMAs
 };
 
@@ -319,9 +321,9 @@ __global__ __launch_bounds__(256) void presplit_kernel(const float* __restrict__
   }
 }
 
-int g_gemm3 = 1;          // dcn_set_tuning("Gemm3", 0): the co-attention products back on the implicit-GEMM / weight-gradient tiles
-
-int g_gemm3_h1 = 1;       // dcn_set_tuning("H1gemm3", 0): the bf16 precision modes multiply both pieces as well (fp32-accurate co-attention)
+DCN_KNOB(g_gemm3, "Gemm3", 1, "gemm3.hip: the co-attention products on pre-split operands (0 = implicit-GEMM / weight-gradient tiles; + 256 * v = schedule variant v; + 16 * bits = timing ablations, results WRONG)",
+         nullptr, "-DG3_ABL=1", G3_ABL != 0, [](int v) { return (v & 0xF0) != 0; });
+DCN_KNOB(g_gemm3_h1, "H1gemm3", 1, "gemm3.hip: one f16 piece per operand in the bf16 precision modes (0 = both pieces, fp32-accurate co-attention)");
 
 template <bool AT, bool BT, bool H1>
 int launch3g_(const G3Params& p, int grid, hipStream_t stream) {
@@ -340,9 +342,6 @@ int launch3g(const G3Params& p, int grid, hipStream_t stream) {
 }
 
 }  // namespace
-
-void gemm3_set_tuning(int v) { g_gemm3 = v; }
-void gemm3_set_h1(int v) { g_gemm3_h1 = v; }
 
 // shapes the kernel takes: rows of 16-byte granularity everywhere, the T operands' tile columns inside their rows
 bool gemm3_applicable(int M, int N, int K, int batch) {

@@ -71,23 +71,19 @@ bool igemm_will_presplit(long long rows, int Co, int ntaps, int Ci);
 // conv3.hip: the 3x3 stride-1 strip kernel (f16 split, pre-split filter bank).  gran = output rows per statistics partial.
 bool conv3_applicable(const IgemmParams& p, int precision, int gran);
 int conv3_launch(const IgemmParams& p, int gran, hipStream_t stream);
-void conv3_set_tuning(int key, int value);
 // conv3x.hip: the same launches on v_mfma_f32_16x16x32_f16 (256 x 128 tile, two taps per MFMA)
 bool conv3x_takes(const IgemmParams& p, int gran);
 int conv3x_launch(const IgemmParams& p, int gran, hipStream_t stream);
-void conv3x_set_tuning(int v);
 // ... and its bf16-storage form (conv1b_launch hands it the 3x3 stride-1 launches): conv3b_bm = pixels per M-tile = rows per BatchNorm
 // partial (0: the launch stays on the gathered tiles)
 int conv3b_bm(int M, int Co, int Wi);
 bool conv3b_takes(const IgemmParams& p);
 int conv3b_launch(const IgemmParams& p, int out_f32, hipStream_t stream);
-void conv3b_set_tuning(int v);
 
 // conv1.hip: NT launches with both tiles by LDS-DMA (f16 split, pre-split filter bank): 1x1 layers, stride-2 layers, the parity
 // classes of their data gradients, narrow 3x3 layers.  gran = output rows per BatchNorm partial row (128 | 256).
 bool conv1_applicable(const IgemmParams& p, int precision, int gran);
 int conv1_launch(const IgemmParams& p, int gran, hipStream_t stream);
-void conv1_set_tuning(int key, int value);
 // ... and its bf16-storage form (activations, gradients and filter banks bf16 in HBM): every forward / data-gradient launch with
 // Ci % 32 == 0.  conv1b_grid_m = BatchNorm partial rows (M-tiles) of a launch.
 int conv1b_grid_m(int M, int Co, int ntaps, int s1_w = 0);      // s1_w: map width when the launch is a 3x3 stride-1 convolution, else 0
@@ -98,13 +94,11 @@ int conv1q_launch(const IgemmParams& p, int out_f32, hipStream_t stream);
 // conv2b.hip: the same on 256 x 256 tiles (eight waves, gemm3.hip's two-group schedule) for launches with Co % 256 == 0 and enough tiles
 bool conv2b_takes(int M, int Co, int ntaps);
 int conv2b_launch(const IgemmParams& p, int out_f32, hipStream_t stream);
-void conv2b_set_tuning(int v);
 
 
 // stem.hip: the 4-channel 3x3 stride-1 stem directly on the vector ALU (forward).  scratch: >= 27*32 floats.
 bool stem_applicable(const IgemmParams& p, const float* scratch);
 int stem_launch(const IgemmParams& p, float* scratch, hipStream_t stream);
-void stem_set_tuning(int v);
 
 // nconv.hip: the data gradients of the 32 -> 64 and 64 -> 128 3x3 stride-2 layers with the filter bank in registers (persistent workgroups, f16 split)
 bool dgrad2_applicable(int n, int h, int wd, int cin, int cout, int ksize, int stride, int accumulate);
@@ -117,10 +111,7 @@ int dgrad2_launch_b16(const void* dy, int lddy, const void* wt16, void* dx, int 
 int dgrad2_grid(int n, int h, int wd, int cin);      // workgroups (= statistics rows of a tap) of a launch, -1: device query failed
 int dgrad2_launch(const float* dy, int lddy, const float* wt, float* dx, int n, int h, int wd, int cin, int accumulate,
                   const uint32_t* amax_dy, const uint32_t* amax_w, const DcnBnTap* tap, hipStream_t stream);
-void nconv_set_tuning(int v);
 // gemm3.hip: batched GEMM on pre-split operands (the co-attention products)
-void gemm3_set_tuning(int v);
-void gemm3_set_h1(int v);
 bool gemm3_applicable(int M, int N, int K, int batch);
 int gemm3_presplit(const float* src, int ld, long long bs, float* dst, int ldd, long long bsd, int batch, int rows, int c,
                    const unsigned* amax, hipStream_t stream);
@@ -128,7 +119,9 @@ int gemm3_launch(const float* A, int lda, long long a_bs, int at, const float* B
                  float* C, int ldc, long long c_bs, const float* row_scale, long long rs_bs,
                  int M, int N, int K, int batch, int accumulate, const unsigned* amax_a, const unsigned* amax_b, hipStream_t stream,
                  unsigned* amax_out = nullptr);
-int igemm_precision();       // dcn_set_tuning("precision"): 4 = f16 two-piece split (the default)
+int igemm_precision();       // the "precision" knob: 4 = f16 two-piece split (the default)
+extern int g_abl;            // igemm.hip: the "abl" knob, read by wgrad.hip as well (DCN_ABL builds)
+extern int g_wsplit;         // wgrad.hip: the "wsplit" knob, which "precision" drives too
 // ... and the 3x3 layers between 32 and 64 channels: mode 0 = forward 32 -> 64 (stride 1 | 2, BatchNorm partial sums), mode 1 = data
 // gradient of the stride-1 layer (64 -> 32)
 // loader-side activation: the gathered tensor is the raw output of a conv + BatchNorm layer; x' = act(x * scale[c] + shift[c])

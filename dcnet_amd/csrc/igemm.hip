@@ -642,20 +642,24 @@ int launch_bk(const IgemmParams& p0, hipStream_t stream) {
 // K-step choice (measured per layer, tools/bench_convs.py): 16 floats per step keeps the LDS footprint at
 // ~40 KB so three workgroups share a CU — better latency hiding on the long-M layers (+3..+60 %, most on the
 // narrow early layers) — while the short grids of the 13x13 maps (M <= 16 K rows) prefer fewer, longer steps.
-int g_force_bk = 0;       // experiment knob (dcn_set_tuning("k", 16|32))
-int g_split = 0;          // dcn_set_tuning("split", 16|32): force every NT tile onto the split-bf16 pipe (bench_convs A/B)
-int g_nn_split = 1;       // dcn_set_tuning("nnsplit", 0): NN products back on the fp32 MFMA
-int g_occ3 = 1 << 30;     // dcn_set_tuning("occ3", n): split launches of <= n K-steps use the 3-waves/SIMD build (A/B: 0 = never)
-int g_abl = 0;            // dcn_set_tuning("abl", 1|2): timing-only ablations of the split kernel (results are wrong)
-int g_precision = 4;      // dcn_set_tuning("precision", 0..4): 0 = fp32 MFMA everywhere; 1 = wide NT tiles of >= 1024 rows on the
-                          // split-bf16 pipe (fp32 accuracy, six MFMAs per product); 2 = those tiles with plain bf16 operands
-                          // (configs[2], reduced precision); 3 = fp8 operands (configs[4]); 4 (default) = the f16 two-piece split
-                          // (fp32 accuracy, three MFMAs per product) wherever the operands carry their abs-max, else as 1
-int g_h2_occ3 = 0;        // dcn_set_tuning("h2occ", 0): f16-split 128x128 tile built for 2 instead of 3 waves/SIMD
-int g_h2_k32 = 128;       // dcn_set_tuning("gk32", n): the 256x32 tile takes the f16 split from this K on
-int g_h2_narrow = 0;      // dcn_set_tuning("rnarrow", 1): the narrow NT tiles (128x64, 256x32, 64x128) on the f16 split as well
-int g_h2_bk = 16;         // dcn_set_tuning("qbk", 32): K-step of the f16-split tiles
-int g_h2_presplit = 1;    // dcn_set_tuning("ypresplit", 0): filter banks split inside every workgroup again
+DCN_KNOB(g_force_bk, "k", 0, "igemm.hip: force the K-step of the fp32-pipe tiles (16 | 32; 0 = automatic)");
+DCN_KNOB(g_split, "split", 0, "igemm.hip: force every NT tile onto the split-bf16 pipe with that K-step (16 | 32; 0 = off)");
+DCN_KNOB(g_nn_split, "nnsplit", 1, "igemm.hip: NN products on the split pipe (0 = fp32 MFMA)");
+DCN_KNOB(g_occ3, "occ3", 1 << 30, "igemm.hip: split launches of <= n K-steps use the 3-waves/SIMD build (0 = never)");
+}  // namespace
+// timing-only ablations of the split kernels here and in wgrad.hip (results are WRONG; -DDCN_ABL=1 builds only)
+DCN_KNOB(g_abl, "abl", 0, "igemm.hip / wgrad.hip: timing-only ablations of the split kernels, 1..4 (results WRONG)", nullptr, "-DDCN_ABL=1", DCN_ABL != 0);
+namespace {
+// 0 = fp32 MFMA everywhere; 1 = wide NT tiles of >= 1024 rows on the split-bf16 pipe (fp32 accuracy, six MFMAs per product); 2 = those
+// tiles with plain bf16 operands (configs[2], reduced precision); 3 = fp8 operands (configs[4]); 4 (default) = the f16 two-piece split
+// (fp32 accuracy, three MFMAs per product) wherever the operands carry their abs-max, else as 1
+int set_precision(int v) { g_wsplit = v == 3 ? 2 : v; return v; }       // (3, fp8: weight gradient with bf16 operands)
+DCN_KNOB(g_precision, "precision", 4, "arithmetic of the wide tiles: 0 fp32 MFMA, 1 bf16 three-piece split, 2 bf16 operands, 3 fp8 operands, 4 f16 two-piece split; also sets wsplit", set_precision);
+DCN_KNOB(g_h2_occ3, "h2occ", 0, "igemm.hip: 1 = the f16-split 128x128 tile built for 3 instead of 2 waves/SIMD");
+DCN_KNOB(g_h2_k32, "gk32", 128, "igemm.hip: the 256x32 tile takes the f16 split from this K on");
+DCN_KNOB(g_h2_narrow, "rnarrow", 0, "igemm.hip: 1 = the narrow NT tiles (128x64, 256x32, 64x128) on the f16 split as well");
+DCN_KNOB(g_h2_bk, "qbk", 16, "igemm.hip: K-step of the f16-split tiles without a pre-split bank (16 | 32)");
+DCN_KNOB(g_h2_presplit, "ypresplit", 1, "igemm.hip: filter banks pre-split once per step (0 = inside every workgroup)");
 
 template <int BM, int BN, int WM, int WN, int BMODE, bool C4 = false>
 int launch_variant(const IgemmParams& p, hipStream_t stream) {
@@ -672,11 +676,13 @@ int launch_variant(const IgemmParams& p, hipStream_t stream) {
     if (g_precision == 4 && p.amax_a && (p.amax_b || p.b_scale) && rows >= 1024 &&
         ((BM == 128 && BN == 128) || (BM == 256 && BN == 64) || (BM == 256 && BN == 32 && p.ntaps * p.Ci >= g_h2_k32) || g_h2_narrow)) {
       // f16 two-piece split (fp32 accuracy, three MFMAs per product): launches whose operands carry their abs-max
+#if DCN_ABL
       if constexpr (BM == 128 && BN == 128) {
         if (p.b_scale && g_abl == 2) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 2, 2, 1, false, true>(p, stream);
         if (p.b_scale && g_abl == 3) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 3, 2, 1, false, true>(p, stream);
         if (p.b_scale && g_abl == 4) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 4, 2, 1, false, true>(p, stream);
       }
+#endif
       if (p.b_scale) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 2, 1, false, true>(p, stream);    // pre-split filter bank
       if (g_h2_bk == 32) return launch_bk<BM, BN, WM, WN, BMODE, C4, 32, true, 0, 2>(p, stream);
       if (BM == 128 && BN == 128 && g_h2_occ3) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 2, 3>(p, stream);
@@ -686,8 +692,10 @@ int launch_variant(const IgemmParams& p, hipStream_t stream) {
       return launch_bk<BM, BN, WM, WN, BMODE, C4, 32, true, 0, 1>(p, stream);     // bf16 operands: 8 MFMAs per 32-wide K-step
     if (g_split || ((g_precision == 1 || g_precision == 4) && ((BM == 128 && BN == 128) || (BM == 256 && BN == 64)) && rows >= 1024)) {
       if (g_split == 32) return launch_bk<BM, BN, WM, WN, BMODE, C4, 32, true>(p, stream);
+#if DCN_ABL
       if (g_abl == 1) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 1>(p, stream);   // ablation: no split arithmetic (wrong results)
       if (g_abl == 2) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 2>(p, stream);   // ablation: 1 of 6 MFMA groups (wrong results)
+#endif
       if (BM == 128 && BN == 128 && (p.c4 ? 4 : p.ntaps * (p.Ci / 16)) <= g_occ3)     // (256x64 tile: 10-25 % slower at 3)
         return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 3, 3>(p, stream);
       return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true>(p, stream);
@@ -707,8 +715,8 @@ int launch_variant(const IgemmParams& p, hipStream_t stream) {
 // resident workgroups) empty: the 13x13 and 26x26 maps give 340-680 tiles of 128 rows, i.e. 66 % fill, and a
 // 64x128 tile (measured ~0.9x the per-tile efficiency) doubles the workgroup count.
 inline double fill(long long blocks, long long slots) { return (double)blocks / (double)(((blocks + slots - 1) / slots) * slots); }
-int g_force_bm = 0;       // experiment knob, set through dcn_set_tuning (tools/bench_convs.py)
-int g_tile64 = 1;         // dcn_set_tuning("tile64", 0): 64-channel layers back on the fp32-pipe 128x64 tile
+DCN_KNOB(g_force_bm, "bm", 0, "igemm.hip: force the M tile of the wide layers (64 | 128; 0 = automatic)");
+DCN_KNOB(g_tile64, "tile64", 1, "igemm.hip: 64-channel layers on the 256x64 split tile (0 = fp32-pipe 128x64 tile)");
 
 // (A/B per layer, tools/bench_convs.py --ab tile64=0: the 256x64 split tile wins 10-30 % where the K loop is long —
 //  3x3 layers and their data gradients — and loses on 1-tap problems with K <= 128, which stay on the fp32 pipe.)
@@ -718,7 +726,7 @@ inline int tile_bm(int M, int Co, int ntaps, int Ci) {
   if (g_force_bm) return g_force_bm;
   // In-process A/B (tools/bench_convs.py --ab bm=64 / bm=128): with the current K-steps the 64-row tile only
   // wins by 3-4 % on the 3x3 layers of the 13x13 maps and loses 10-70 % everywhere else, so it is kept as a
-  // knob (dcn_set_tuning("bm", 64)) but not selected automatically.
+  // knob ("bm" = 64) but not selected automatically.
   (void)M;
   return 128;
 }
@@ -726,78 +734,6 @@ inline int tile_bm(int M, int Co, int ntaps, int Ci) {
 }  // namespace
 
 int igemm_grid_m(int M, int Co, int ntaps) { return cdiv(M, tile_bm(M, Co, ntaps, 32)); }   // Ci >= 32 on every multi-tap path
-
-void wgrad_set_split(int v);
-void wgrad_set_lds_pad(int kb);
-void wgrad_set_abl(int v);
-void wgrad_set_target(int v);
-void wgrad_set_wide64(int v);
-void wgrad_set_target_small(int v);
-void wgrad_set_w3_b16(int v);
-void wgrad_set_w9_b16(int v);
-void wgrad_set_target_b16(int v, int small);
-void wgrad3_set_tuning(int key, int value);
-void wgrad_set_w1x(int v);
-void bn_set_pc(int v);
-void conv_set_merge(int v);
-void conv_set_d2_b16(int v);
-void conv_set_n1_b16(int v);
-void score_set_tuning(int key, int value);
-void bn_set_tuning(int v);
-void wgrad9_set_tuning(int key, int value);
-void wgrad_set_slab_fold(int v);
-
-extern "C" int dcn_set_tuning(const char* key, int value) {
-  const char k = key ? key[0] : 0;
-  if (k == 'S' && key[1] == 'l') { wgrad_set_slab_fold(value); return DCN_OK; }         // "Slabfold": split-K slabs summed by the last-arriving workgroup (slabsum.h; 0 = reduce_slabs_kernel behind the launch)
-  if (k == '2') { conv2b_set_tuning(value); return DCN_OK; }                             // "2btile": min 256 x 256 tiles for conv2b.hip (0 = off)
-  if (k == 'H') { gemm3_set_h1(value); return DCN_OK; }                                  // "H1gemm3": one f16 piece per operand in the bf16 modes (gemm3.hip)
-  if (k == 'q' && key[1] == 't') { wgrad_set_target_b16(value, 0); return DCN_OK; }     // "qtargetb16": workgroups a bf16-storage 3x3 stride-1 weight gradient aims for
-  if (k == 'q' && key[1] == 's') { wgrad_set_target_b16(value, 1); return DCN_OK; }     // "qsmallb16": the same for its 1x1 / stride-2 layers
-  if (k == 'w' && key[1] == '3') { wgrad_set_w3_b16(value); return DCN_OK; }           // "w3b16": bf16-storage 3x3 weight gradients by filter rows (wgrad3.hip)
-  if (k == 'b' && key[1] == 'w') { conv1_set_tuning(4, value); return DCN_OK; }       // "bwide": conv1b 128 x 256 tiles from n workgroups on
-  if (k == 'b' && key[1] == 't') { conv1_set_tuning(5, value); return DCN_OK; }       // "btall": conv1b 256 x 128 tiles from n workgroups on
-  if (k == '1') { conv1_set_tuning(key[1] == 's' ? 1 : (key[1] == 'f' ? 2 : (key[1] == 'w' ? 3 : (key[1] == 't' ? 6 : 0))), value); return DCN_OK; }   // "1x1dma" (0/1/2), "1stages" (10 SA + SB), "1fill"
-  if (k == '3') { if (key[1] == 'h') { conv3b_set_tuning(value); return DCN_OK; }
-    if (key[1] == 'd') { conv3x_set_tuning(value); return DCN_OK; }      // "3dma": conv3x.hip's filter tiles by LDS-DMA (1) / through registers (0)      // "3h16": bf16-storage strip kernel (0 = gathered tiles)
-    conv3_set_tuning(key[1] == 'b' ? 1 : key[1] == 'a' ? 2 : key[1] == 'l' ? 3 : key[1] == 'm' ? 4 : 0, value); return DCN_OK; }   // "3x3strip" (0/1), "3bm" (0/128/256), "3abl", "3ls", "3m16"
-  if (k == 'N' && key[1] == 'b') { conv_set_n1_b16(value); return DCN_OK; }           // "Nb16": bf16-storage register-bank forward / data gradient 32 <-> 64 (nconv.hip)
-  if (k == 'D') { conv_set_d2_b16(value); return DCN_OK; }                            // "Db16": bf16-storage register-bank stride-2 data gradient (nconv.hip)
-  if (k == '9' && key[1] == 'b') { wgrad_set_w9_b16(value); return DCN_OK; }          // "9b16": bf16-storage nine-tap weight gradient (wgrad9.hip)
-  if (k == '9') { wgrad9_set_tuning(key[1] == 't' && key[2] == 'a' && key[3] == 'r' ? 1 : 0, value); return DCN_OK; }   // "9tap" (0/1), "9target"
-  if (k == 'G') { gemm3_set_tuning(value); return DCN_OK; }       // "Gemm3": the co-attention products on pre-split operands (gemm3.hip)
-  if (k == 'N') { nconv_set_tuning(value); return DCN_OK; }       // "Nconv": register-bank kernels of the 32 <-> 64 channel layers (nconv.hip)
-  if (k == 'd') { bn_set_tuning(value); return DCN_OK; }          // "dbnrev": sweep direction of the BatchNorm streaming passes (bn.hip)
-  if (k == 'e') { score_set_tuning(0, value); return DCN_OK; }    // "e2rpw": rows per wave of l2norm_score_fwd
-  if (k == 'f') { score_set_tuning(1, value); return DCN_OK; }    // "f2nt": non-temporal loads there
-  if (k == 'l') { wgrad_set_lds_pad(value); return DCN_OK; }      // "lwgpad": KB of LDS a weight-gradient launch reserves at least (occupancy experiment)
-  if (k == 'j') { stem_set_tuning(value); return DCN_OK; }        // "jstem": the stem directly on the vector ALU (stem.hip)
-  if (k == 'm') { conv_set_merge(value); return DCN_OK; }         // "merge": parity classes of a stride-2 data gradient in one launch
-  if (k == 'Y') { wgrad_set_w1x(value); return DCN_OK; }          // "Y1wide": 1x1 stride-1 weight gradients on the 256-wide tile (wgrad.hip wgrad1x_kernel; 0 = off, n > 1: workgroups aimed for)
-  if (k == 'U') { wgrad3_set_tuning(2, value); return DCN_OK; }   // "U3m16": wgrad3.hip on 16x16x32 MFMAs (1) / 32x32x16 (0)
-  if (k == 'u') { wgrad3_set_tuning(0, value); return DCN_OK; }   // "u3row": 3x3 stride-1 weight gradient by filter rows (wgrad3.hip)
-  if (k == 'v') { wgrad3_set_tuning(1, value); return DCN_OK; }   // "v3target"
-  if (k == 'B') { bn_set_pc(value); return DCN_OK; }              // "Bpc": BatchNorm apply passes with the channel fixed per thread (bn.hip; 0 = grid-stride forms)
-  if (k == 'z') { wgrad_set_target_small(value); return DCN_OK; }   // "zwgsmall"
-  if (k == 'c') { wgrad_set_wide64(value); return DCN_OK; }        // "cwide64"
-  if (k == 'x') { wgrad_set_target(value); return DCN_OK; }   // "xwgtarget"
-  if (k == 'w') { wgrad_set_split(value); return DCN_OK; }   // "wsplit": weight-gradient 128x128 tiles on the split-bf16 pipe
-  if (k == 'p') { g_precision = value; wgrad_set_split(value == 3 ? 2 : value); return DCN_OK; }   // 3 (fp8): weight gradient with bf16 operands   // "precision": 0 native fp32 MFMA, 1 split-bf16 on the wide tiles
-  if (k == 'b') g_force_bm = value;          // "bm": force the M tile (0 = automatic)
-  else if (k == 'k') g_force_bk = value;     // "k": force the K-step (16 or 32, 0 = automatic)
-  else if (k == 'n') g_nn_split = value;     // "nnsplit"
-  else if (k == 'o') g_occ3 = value;         // "occ3"
-  else if (k == 'h') g_h2_occ3 = value;      // "h2occ"
-  else if (k == 'g') g_h2_k32 = value;       // "gk32"
-  else if (k == 'r') g_h2_narrow = value;    // "rnarrow"
-  else if (k == 'q') g_h2_bk = value;        // "qbk"
-  else if (k == 'y') g_h2_presplit = value;  // "ypresplit"
-  else if (k == 't') g_tile64 = value;       // "tile64"
-  else if (k == 'a') { g_abl = value; wgrad_set_abl(value); }         // "abl"
-  else if (k == 's') g_split = value;        // "split": 0 = fp32 MFMA, 16 / 32 = split-bf16 MFMA with that K-step
-  else { dcn_set_error("set_tuning: unknown key"); return DCN_ERR_ARG; }
-  return DCN_OK;
-}
 
 int igemm_precision() { return g_precision; }
 

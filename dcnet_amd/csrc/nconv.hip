@@ -654,11 +654,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   }
 }
 
-int g_nconv = 1;          // dcn_set_tuning("Nconv", 0): these layers back on the implicit-GEMM tiles
+DCN_KNOB(g_nconv, "Nconv", 1, "nconv.hip: register-bank kernels of the 32 <-> 64 channel layers (0 = implicit-GEMM tiles; 2 = the 32 -> 64 stride-2 data gradient only; 3 = dgrad2 only)");
 
 }  // namespace
-
-void nconv_set_tuning(int v) { g_nconv = v; }
 
 // data gradients of the 32 -> 64 and 64 -> 128 3x3 stride-2 layers (dY 64 | 128 channels -> dX 32 | 64 channels), dense dX
 bool dgrad2_applicable(int n, int h, int wd, int cin, int cout, int ksize, int stride, int accumulate) {

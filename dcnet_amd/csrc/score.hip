@@ -91,8 +91,8 @@ __global__ __launch_bounds__(256) void l2norm_score_fwd_kernel(const float* __re
   }
 }
 
-int g_l2_rpw = 2;      // dcn_set_tuning("e2rpw", 1|2|4|8): rows per wave of l2norm_score_fwd (tools/bench_score.py)
-int g_l2_nt = 1;       // dcn_set_tuning("f2nt", 0|1): non-temporal loads of x
+DCN_KNOB(g_l2_rpw, "e2rpw", 2, "score.hip: rows per wave of l2norm_score_fwd (1 | 2 | 4 | 8; tools/bench_score.py)");
+DCN_KNOB(g_l2_nt, "f2nt", 1, "score.hip: non-temporal loads of x in l2norm_score_fwd (0 | 1)");
 
 template <int V4>
 void launch_l2fwd(const float* x, int ldx, float* out, int ldo, float* norm, const float* q, float* score, float* score_flip,
@@ -267,4 +267,3 @@ extern "C" int dcn_rowdot_bwd(const float* x, int ldx, const float* q, int flip,
   return DCN_OK;
 }
 
-void score_set_tuning(int key, int value) { if (key == 0) g_l2_rpw = value; else g_l2_nt = value; }

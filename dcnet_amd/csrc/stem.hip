@@ -119,11 +119,9 @@ __global__ __launch_bounds__(256) void stem_kernel(const StemParams p) {
   }
 }
 
-int g_stem_direct = 1;    // dcn_set_tuning("jstem", 0): the stem back on the implicit-GEMM c4 tile
+DCN_KNOB(g_stem_direct, "jstem", 1, "stem.hip: the stem forward directly on the vector ALU (0 = implicit-GEMM c4 tile)");
 
 }  // namespace
-
-void stem_set_tuning(int v) { g_stem_direct = v; }
 
 // can this forward launch run on the direct kernel?  (the caller's statistics buffer is sized for 256-row partials: Co <= 32)
 bool stem_applicable(const IgemmParams& p, const float* scratch) {

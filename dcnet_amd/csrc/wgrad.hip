@@ -668,11 +668,11 @@ __global__ __launch_bounds__(256) void reduce_slabs_kernel(const float* __restri
 }
 
 struct Plan { int tm, tn, tiles_co, tiles_ci, T, splits, kchunk, M, ld_out; };
-int g_wide64 = 1;           // dcn_set_tuning("cwide64", 0): 64-channel sides back on the narrow fp32-pipe tiles
-int g_wg_target = 1024;    // dcn_set_tuning("xwgtarget", n): workgroups a 3x3 stride-1 weight-gradient launch aims for (split-K sizing)
-int g_wg_target_small_b16 = 512;   // ("qsmallb16")
-int g_wg_target_b16 = 768;     // dcn_set_tuning("qtargetb16", n): the same for the bf16-storage 3x3 stride-1 layers (make_plan_b16)
-int g_wg_target_small = 512;   // dcn_set_tuning("zwgsmall", n): the same for 1x1 and stride-2 layers
+DCN_KNOB(g_wide64, "cwide64", 1, "wgrad.hip: layers with one 64-channel side on the half-empty 128x128 split tile (0 = narrow fp32-pipe tiles)");
+DCN_KNOB(g_wg_target, "xwgtarget", 1024, "wgrad.hip: workgroups a 3x3 stride-1 weight gradient aims for (split-K sizing; <= 0 = default)", [](int v) { return v > 0 ? v : 1024; });
+DCN_KNOB(g_wg_target_small, "zwgsmall", 512, "wgrad.hip: the same for the 1x1 and stride-2 layers (<= 0 = default)", [](int v) { return v > 0 ? v : 512; });
+DCN_KNOB(g_wg_target_b16, "qtargetb16", 768, "wgrad.hip: workgroups a bf16-storage 3x3 stride-1 weight gradient aims for (<= 0 = default)", [](int v) { return v > 0 ? v : 768; });
+DCN_KNOB(g_wg_target_small_b16, "qsmallb16", 512, "wgrad.hip: the same for its 1x1 / stride-2 layers (<= 0 = default)", [](int v) { return v > 0 ? v : 512; });
 int dispatch_wgrad(const WgradParams& p, int tm, int tn, int grid, int batch, hipStream_t stream);
 
 Plan make_plan(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
@@ -711,19 +711,16 @@ Plan make_plan(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   return pl;
 }
 
-int g_wabl = 0;            // timing-only ablations of the split kernel (wrong results): dcn_set_tuning("abl", v)
-int g_wsplit = 4;          // 128x128 weight-gradient / TN tiles: 0 native fp32 MFMA, 1 bf16 three-piece split, 2 bf16 operands,
-                           // 4 f16 two-piece split where the operands carry their abs-max (else as 1)   (dcn_set_tuning("precision"|"wsplit"))
-
-int g_slab_fold = 0;       // dcn_set_tuning("Slabfold", KB): split-K slabs are summed by the last-arriving workgroup of a tile (slabsum.h) when that workgroup
-                           // has at most this much to read; 0 = always reduce_slabs_kernel behind the launch.  OFF: measured in the replayed step
-                           // (profiles/r06_experiments.md) 91.15 ms without, 91.70 / 91.80 at 2.5 / 4.2 MB, 100.06 with every launch folded
-int g_wg_lds_pad = 0;      // dcn_set_tuning("lwgpad", KB): dynamic LDS the weight-gradient launches ask for at least (81+ = one workgroup per CU)
-}
-int wgrad_lds_pad() { return g_wg_lds_pad; }
+}  // namespace
+// 128x128 weight-gradient / TN tiles: 0 native fp32 MFMA, 1 bf16 three-piece split, 2 bf16 operands, 4 f16 two-piece split where the
+// operands carry their abs-max (else as 1).  "precision" sets it as well.
+DCN_KNOB(g_wsplit, "wsplit", 4, "wgrad.hip: arithmetic of the 128x128 weight-gradient / TN tiles (0 fp32 MFMA, 1 bf16 split, 2 bf16 operands, 4 f16 split); precision sets it too");
+// Split-K slabs are summed by the last-arriving workgroup of a tile (slabsum.h) when that workgroup has at most this much to read.
+// OFF: measured in the replayed step (profiles/r06_experiments.md) 91.15 ms without, 91.70 / 91.80 at 2.5 / 4.2 MB, 100.06 with every
+// launch folded.  < 0 (-DDCN_ABL=1 builds only): no slab pass at all, dw is NOT written.
+DCN_KNOB(g_slab_fold, "Slabfold", 0, "wgrad.hip: KB a tile's last workgroup may read to sum the split-K slabs itself (0 = reduce_slabs_kernel behind the launch; < 0 = no slab pass, results WRONG)",
+         nullptr, "-DDCN_ABL=1", DCN_ABL != 0, [](int v) { return v < 0; });
 int wgrad_slab_fold() { return g_slab_fold; }
-void wgrad_set_slab_fold(int v) { g_slab_fold = v; }
-void wgrad_set_lds_pad(int kb) { g_wg_lds_pad = kb * 1024; }
 namespace {
 template <int TM, int TN, bool SP = false, int ABL = 0, int NP = 3, bool IN16 = false>
 int launch_wgrad(const WgradParams& p, int grid, int batch, hipStream_t stream) {
@@ -732,7 +729,6 @@ int launch_wgrad(const WgradParams& p, int grid, int batch, hipStream_t stream) 
   size_t lds = SP ? (size_t)2 * 2 * NP * 4096 : (size_t)2 * KP * (TM + TN) * sizeof(float);
   const size_t red = (size_t)(WK - 1) * TM * TN * sizeof(float);
   if (red > lds) lds = red;
-  if ((size_t)wgrad_lds_pad() > lds) lds = (size_t)wgrad_lds_pad();      // (occupancy experiment: "lwgpad")
   static DcnPerDeviceSize attr_lds;
   if (attr_lds.raise(lds)) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad_kernel<TM, TN, KP, SP, ABL, NP, IN16>),
@@ -747,9 +743,11 @@ int launch_wgrad(const WgradParams& p, int grid, int batch, hipStream_t stream) 
 }
 
 int dispatch_wgrad(const WgradParams& p, int tm, int tn, int grid, int batch, hipStream_t stream) {
-  if (tm == 128 && tn == 128 && g_wabl && g_wsplit && !p.c4 && p.M >= 1024)
-    return g_wabl == 1 ? launch_wgrad<128, 128, true, 1>(p, grid, batch, stream)
+#if DCN_ABL
+  if (tm == 128 && tn == 128 && g_abl && g_wsplit && !p.c4 && p.M >= 1024)
+    return g_abl == 1 ? launch_wgrad<128, 128, true, 1>(p, grid, batch, stream)
          : launch_wgrad<128, 128, true, 2>(p, grid, batch, stream);
+#endif
   if (tm == 128 && tn == 128 && g_wsplit == 2 && !p.c4 && p.M >= 1024) return launch_wgrad<128, 128, true, 0, 1>(p, grid, batch, stream);
   if (tm == 128 && tn == 128 && g_wsplit == 4 && p.amax_dy && p.amax_x && !p.c4 && p.M >= 1024)
     return launch_wgrad<128, 128, true, 0, 2>(p, grid, batch, stream);                  // f16 two-piece split
@@ -768,7 +766,9 @@ int dispatch_wgrad(const WgradParams& p, int tm, int tn, int grid, int batch, hi
 }  // namespace
 
 int wgrad_reduce_slabs(const float* ws, float* dw, int64_t n4, int splits, hipStream_t stream) {
-  if (g_slab_fold < 0) return DCN_OK;          // timing-only ablation (dcn_set_tuning("Slabfold", -1)): no slab pass at all, dw is NOT written
+#if DCN_ABL
+  if (g_slab_fold < 0) return DCN_OK;          // timing-only ablation ("Slabfold" = -1): no slab pass at all, dw is NOT written
+#endif
   const int blocks = (int)((n4 + 255) / 256 < 4096 ? (n4 + 255) / 256 : 4096);
   const int pid = prof_begin(30, (double)(splits + 1) * n4 * 16.0, stream);     // HBM-priced: slabs read + dw written
   hipLaunchKernelGGL(reduce_slabs_kernel, dim3(blocks), dim3(256), 0, stream, ws, dw, n4, splits);
@@ -777,13 +777,6 @@ int wgrad_reduce_slabs(const float* ws, float* dw, int64_t n4, int splits, hipSt
   return DCN_OK;
 }
 int wgrad_split_mode() { return g_wsplit; }
-
-void wgrad_set_split(int v) { g_wsplit = v; }
-void wgrad_set_abl(int v) { g_wabl = v; }
-void wgrad_set_wide64(int v) { g_wide64 = v; }
-void wgrad_set_target(int v) { g_wg_target = v > 0 ? v : 1024; }
-void wgrad_set_target_small(int v) { g_wg_target_small = v > 0 ? v : 512; }
-void wgrad_set_w3_b16(int v);
 
 // C[b][m][n] (+)= row_scale[b][m] * sum_k A[b][k][m] * B[b][k][n]   ("TN" GEMM: K is the strided dim of
 // both operands).  A may be loaded up to column m_ld (zero padded by its producer).  No split-K.
@@ -819,7 +812,7 @@ int wgrad9_launch(const float* x, int ldx, const float* dy, int lddy, float* dw,
                   const uint32_t* amax_x, const uint32_t* amax_dy, const DcnPreAct* pre, hipStream_t stream);
 
 // wgrad1x_kernel: which layers, and its split-K plan
-int g_w1x = 1;            // dcn_set_tuning("Y1wide", 0): 1x1 stride-1 weight gradients back on the 128 x 128 tile; n > 1: workgroups a launch aims for
+DCN_KNOB(g_w1x, "Y1wide", 1, "wgrad.hip: 1x1 stride-1 weight gradients on the 256-wide tile (0 = 128x128 tile; n > 1 = workgroups a launch aims for)");
 struct Plan1x { int mi, tiles_co, tiles_ci, splits, kchunk; };
 static bool wgrad1x_shape_ok(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   // (128 filters — the 128 x 256 build, MI = 2 — measured level with the 128 x 128 tile: 256 -> 128 @52 0.080-0.086 against 0.080 ms; left there)
@@ -866,7 +859,6 @@ static int wgrad1x_launch(const float* x, int ldx, const float* dy, int lddy, fl
   if (pl.splits > 1 && !fold) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * cin / 4, pl.splits, stream);
   return DCN_OK;
 }
-void wgrad_set_w1x(int v) { g_w1x = v; }
 
 extern "C" int64_t dcn_conv2d_bwd_weight_ws(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   const Plan pl = make_plan(n, h, wd, cin, cout, ksize, stride);
@@ -894,7 +886,7 @@ extern "C" int dcn_conv2d_bwd_weight_pre(const float* x, int ldx, const float* d
                                          const float* pre_scale, const float* pre_shift, int pre_act, float pre_slope,
                                          const uint32_t* amax_x, const uint32_t* amax_dy, void* stream_) {
   DCN_CHECK_ARG(x && dy && dw && pre_scale && pre_shift && amax_x && amax_dy, "conv2d_bwd_weight_pre: null pointer (the abs-max words are required)");
-  DCN_CHECK_ARG(g_wsplit == 4 && !g_wabl && cin == 32 && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride),
+  DCN_CHECK_ARG(g_wsplit == 4 && !g_abl && cin == 32 && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride),
                 "conv2d_bwd_weight_pre: no loader-side activation for this shape / precision");
   DCN_CHECK_ARG(pre_act == DCN_ACT_NONE || pre_act == DCN_ACT_LEAKY, "conv2d_bwd_weight_pre: pre_act=%d", pre_act);
   const int lx = ldx > 0 ? ldx : cin, ly = lddy > 0 ? lddy : cout;
@@ -903,7 +895,7 @@ extern "C" int dcn_conv2d_bwd_weight_pre(const float* x, int ldx, const float* d
   return wgrad9_launch(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, stride, amax_x, amax_dy, &pre, (hipStream_t)stream_);
 }
 extern "C" int dcn_conv2d_bwd_weight_pre_supported(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
-  return (g_wsplit == 4 && !g_wabl && cin == 32 && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride)) ? 1 : 0;
+  return (g_wsplit == 4 && !g_abl && cin == 32 && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride)) ? 1 : 0;
 }
 
 extern "C" int64_t dcn_conv2d_geom_size(int n, int h, int wd, int ksize, int stride) {
@@ -940,12 +932,12 @@ extern "C" int dcn_conv2d_bwd_weight(const float* x, int ldx, const float* dy, i
     const int lx = ldx > 0 ? ldx : cin, ly = lddy > 0 ? lddy : cout;
     const long long npix = (long long)n * h * wd;
     const bool f16 = g_wsplit == 4 && amax_x && amax_dy, b16 = g_wsplit == 2;      // (2: the bf16- and fp8-operand modes)
-    if (f16 && !g_wabl && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride) && lx % 4 == 0 && ly % 4 == 0)
+    if (f16 && !g_abl && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride) && lx % 4 == 0 && ly % 4 == 0)
       return wgrad9_launch(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, stride, amax_x, amax_dy, nullptr, stream);
-    if ((f16 || b16) && !g_wabl && wgrad3_shape_ok(n, h, wd, cin, cout, ksize, stride) &&
+    if ((f16 || b16) && !g_abl && wgrad3_shape_ok(n, h, wd, cin, cout, ksize, stride) &&
         npix * lx * 4 < 0x7FFFFFF0LL && npix * ly * 4 < 0x7FFFFFF0LL && lx % 4 == 0 && ly % 4 == 0)
       return wgrad3_launch(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, amax_x, amax_dy, f16 ? 2 : 1, stream);
-    if (f16 && !g_wabl && wgrad1x_shape_ok(n, h, wd, cin, cout, ksize, stride) && lx % 4 == 0 && ly % 4 == 0 &&
+    if (f16 && !g_abl && wgrad1x_shape_ok(n, h, wd, cin, cout, ksize, stride) && lx % 4 == 0 && ly % 4 == 0 &&
         npix * lx * 4 < 0x7FFFFFF0LL && npix * ly * 4 < 0x7FFFFFF0LL)
       return wgrad1x_launch(x, lx, dy, ly, dw, ws, counters, (int)npix, cin, cout, amax_x, amax_dy, stream);
   }
@@ -1007,14 +999,15 @@ Plan make_plan_b16(int n, int h, int wd, int cin, int cout, int ksize, int strid
 bool wgrad3_b16_ok(int n, int h, int wd, int cin, int cout, int ksize, int stride);
 int wgrad3_launch_b16(const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout,
                       hipStream_t stream);
-int g_w3_b16 = 0;         // dcn_set_tuning("w3b16", 1): bf16-storage 3x3 stride-1 weight gradients by filter rows (wgrad3.hip, bf16 inputs).  Measured
-                          // (tools/bench_b16.py --set w3b16=0 --ab w3b16=1, N = 64): it LOSES to the per-tap tile here — 128->256 @52 0.170 -> 0.207 ms,
-                          // 256->512 @26 0.167 -> 0.204, 512->512 @52 1.22 -> 1.50: with one MFMA per product both are bound by the bytes they stage per
-                          // FLOP, and the filter-row form stages more (a 16-position step per 3 x 8 MFMAs); off
+DCN_KNOB(g_w3_b16, "w3b16", 0, "wgrad.hip: 1 = bf16-storage 3x3 stride-1 weight gradients by filter rows (wgrad3.hip)");
+// w3b16 measured
+// (tools/bench_b16.py --set w3b16=0 --ab w3b16=1, N = 64): it LOSES to the per-tap tile here — 128->256 @52 0.170 -> 0.207 ms,
+// 256->512 @26 0.167 -> 0.204, 512->512 @52 1.22 -> 1.50: with one MFMA per product both are bound by the bytes they stage per
+// FLOP, and the filter-row form stages more (a 16-position step per 3 x 8 MFMAs); off
 
 int wgrad9_launch_b16(const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout, int stride,
                       hipStream_t stream);
-int g_w9_b16 = 1;         // dcn_set_tuning("9b16", 0): the 32 -> 64 / 64 -> 128 3x3 layers of the bf16-storage mode back on the per-tap tile
+DCN_KNOB(g_w9_b16, "9b16", 1, "wgrad.hip: the 32 -> 64 / 64 -> 128 3x3 layers of the bf16-storage mode on wgrad9.hip (0 = per-tap tile)");
 
 extern "C" int64_t dcn_conv2d_bwd_weight_ws_b16(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   const Plan pl = make_plan_b16(n, h, wd, cin, cout, ksize, stride);
@@ -1059,7 +1052,3 @@ extern "C" int dcn_conv2d_bwd_weight_b16(const void* x, int ldx, const void* dy,
   if (pl.splits > 1 && !fold) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * pl.ld_out / 4, pl.splits, stream);
   return DCN_OK;
 }
-
-void wgrad_set_w3_b16(int v) { g_w3_b16 = v; }
-void wgrad_set_w9_b16(int v) { g_w9_b16 = v; }
-void wgrad_set_target_b16(int v, int small) { if (small) g_wg_target_small_b16 = v > 0 ? v : 512; else g_wg_target_b16 = v > 0 ? v : 768; }

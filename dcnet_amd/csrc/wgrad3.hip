@@ -521,9 +521,9 @@ __global__ __launch_bounds__(512, 2) void wgrad3x_kernel(const W3Params p) {
 // --schedule-tunes "U3m16=0=1;...": 92.08 / 92.23 against 91.63 / 91.54; 93.27 against 92.79 / 92.88; 92.32 against 91.65).  What differs
 // beside another queue: 219 registers against 190 (two of its waves leave a SIMD 64 registers instead of 128 for a wave of the chain's
 // kernels) and 66 KB of LDS against 34.
-int g_w3x = 0;            // dcn_set_tuning("U3m16", 1): 3x3 stride-1 weight gradients on the 16x16x32 build
-int g_w3 = 1;             // dcn_set_tuning("u3row", 0): 3x3 stride-1 weight gradients back on the per-tap kernel
-int g_w3_target = 512;    // dcn_set_tuning("v3target", n): workgroups a launch aims for (split-K sizing; 512 threads, 1-2 per CU)
+DCN_KNOB(g_w3x, "U3m16", 0, "wgrad3.hip: 1 = 3x3 stride-1 weight gradients on the 16x16x32 MFMA build (0 = 32x32x16)");
+DCN_KNOB(g_w3, "u3row", 1, "wgrad3.hip: 3x3 stride-1 weight gradients by filter rows (0 = per-tap kernel of wgrad.hip)");
+DCN_KNOB(g_w3_target, "v3target", 512, "wgrad3.hip: workgroups a launch aims for (split-K sizing; 512 threads, 1-2 per CU; <= 0 = default)", [](int v) { return v > 0 ? v : 512; });
 
 struct Plan3 { int tiles_co, tiles_ci, splits, kchunk, Mp; };
 Plan3 plan3(int n, int h, int wd, int cin, int cout) {
@@ -542,8 +542,6 @@ Plan3 plan3(int n, int h, int wd, int cin, int cout) {
 
 }  // namespace
 
-void wgrad3_set_tuning(int key, int value) { if (key == 0) g_w3 = value; else if (key == 2) g_w3x = value; else g_w3_target = value > 0 ? value : 512; }
-
 // shape test only (the workspace is sized without knowing whether the abs-max words will be there)
 bool wgrad3_shape_ok(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   if (!g_w3 || ksize != 3 || stride != 1 || cin < 64 || cout < 64 || (cin < 128 && cout < 128) || cin % 4 || cout % 4 || wd < 8 || h < 2) return false;
@@ -558,8 +556,6 @@ int64_t wgrad3_ws(int n, int h, int wd, int cin, int cout) {
   const Plan3 pl = plan3(n, h, wd, cin, cout);
   return pl.splits > 1 ? (int64_t)pl.splits * cout * 9 * cin : 0;
 }
-
-int wgrad_lds_pad();
 
 // bf16 storage: x, dy bf16 tensors (strides in elements), dw / slabs fp32
 int wgrad_slab_fold();
@@ -602,12 +598,11 @@ int wgrad3_launch(const float* x, int ldx, const float* dy, int lddy, float* dw,
   const bool fold = slab_fold_ok(counters, pl.tiles_co * pl.tiles_ci * 3, pl.splits, 128LL * 3 * 128 * 4, wgrad_slab_fold());
   if (fold) p.fold = SlabFold{counters, dw};
   p.amax_dy = amax_dy; p.amax_x = amax_x;
-  size_t lds = (size_t)2 * np * (A_PLANE + B_PLANE);
-  if ((size_t)wgrad_lds_pad() > lds) lds = (size_t)wgrad_lds_pad();       // (occupancy experiment: "lwgpad")
-  static DcnPerDeviceSize attr_lds;
-  if (attr_lds.raise(lds)) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds > 2 * 2 * (A_PLANE + B_PLANE) ? lds : 2 * 2 * (A_PLANE + B_PLANE)));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds > 2 * (A_PLANE + B_PLANE) ? lds : 2 * (A_PLANE + B_PLANE)));
+  const size_t lds = (size_t)2 * np * (A_PLANE + B_PLANE);
+  static DcnPerDeviceFlag attr_once;
+  if (attr_once.first()) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * (A_PLANE + B_PLANE));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (A_PLANE + B_PLANE));
   }
   const int grid = pl.tiles_co * pl.tiles_ci * 3 * pl.splits;
   const int pid = prof_begin(np == 2 ? 32 : 20, 2.0 * (double)n * h * wd * cout * 9.0 * cin, stream);

@@ -308,9 +308,8 @@ void wgrad9_kernel(const W9Params p) {
   }
 }
 
-int g_w9 = 2;             // dcn_set_tuning("9tap", 0): these layers back on the kernels of wgrad.hip / wgrad3.hip; 1: 32 -> 64 only;
-                          // 2: + 64 -> 128 at stride 1; 3: + 64 -> 128 at stride 2 (54 spilled registers)
-int g_w9_target = 512;    // dcn_set_tuning("9target", n): workgroups (= split-K slabs) per launch
+DCN_KNOB(g_w9, "9tap", 2, "wgrad9.hip: nine-tap weight gradient (0 = off; 1 = 32 -> 64 only; 2 = + 64 -> 128 at stride 1; 3 = + 64 -> 128 at stride 2, 54 spilled registers)");
+DCN_KNOB(g_w9_target, "9target", 512, "wgrad9.hip: workgroups (= split-K slabs) per launch (<= 0 = default)", [](int v) { return v > 0 ? v : 512; });
 
 struct Plan9 { int splits, kchunk, Mp; };
 Plan9 plan9(int n, int ho, int wo) {
@@ -340,7 +339,6 @@ int launch9(const W9Params& p, int splits, hipStream_t stream) {
 
 }  // namespace
 
-void wgrad9_set_tuning(int key, int value) { if (key == 0) g_w9 = value; else g_w9_target = value > 0 ? value : 512; }
 
 // shape test only (the workspace is sized without knowing whether the abs-max words will be there): 32 -> 64 (stride 1 | 2) and
 // 64 -> 128 (g_w9 = 2: stride 1 only; 1: neither — the half-empty 128 x 128 tiles of wgrad3.hip / wgrad.hip keep them)

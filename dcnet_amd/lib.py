@@ -121,6 +121,7 @@ SIGNATURES = {
     "dcn_embedding_fwd": (I, [P, P, P, I, I, I, P]),
     "dcn_embedding_bwd": (I, [P, P, P, I, I, I, P]),
     "dcn_set_tuning": (I, [c_char_p, I]),
+    "dcn_tuning_info": (I, [I, P, P, P, P, P]),
     "dcn_stream_create": (P, [I]),
     "dcn_stream_destroy": (I, [P]),
     "dcn_stream_priority_range": (I, [P, P]),
@@ -161,7 +162,7 @@ SIGNATURES = {
 _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap_rows", "dcn_conv2d_pre_supported",
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",
                 "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes"}
-ABI_VERSION = 309        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
+ABI_VERSION = 310        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
 
 
 class DcnError(RuntimeError):
@@ -190,7 +191,7 @@ class _Lib:
         for kv in [t for t in os.environ.get("DCN_TUNE", "").split(",") if t]:
             k_, v_ = kv.split("=")
             if self._dll.dcn_set_tuning(k_.encode(), int(v_)) != 0:
-                raise DcnError(f"DCN_TUNE: unknown knob {k_!r}")
+                raise DcnError(f"DCN_TUNE: {self._dll.dcn_last_error().decode()}")
         if self._dll.dcn_version() != ABI_VERSION:
             raise DcnError(f"{path} has ABI version {self._dll.dcn_version()}, this binding was written for {ABI_VERSION}: "
                            "rebuild the library (python -m dcnet_amd.build --force)")
@@ -202,6 +203,22 @@ class _Lib:
                 raise DcnError(f"{name} failed ({rc}): {self._dll.dcn_last_error().decode()}")
         call.__name__ = name
         return call
+
+
+def tuning(L: "_Lib" = None) -> dict:
+    """Every knob of dcn_set_tuning: name -> {"value", "default", "desc", "ablation"} (dcn_tuning_info; ablation 0 = ordinary knob,
+    1 = exists only in ablation builds and is not in this one, 2 = compiled in)."""
+    dll = (L or lib())._dll
+    out = {}
+    name, desc, val, dflt, abl = c_char_p(), c_char_p(), c_int(), c_int(), c_int()
+    while dll.dcn_tuning_info(len(out), ctypes.byref(name), ctypes.byref(val), ctypes.byref(dflt), ctypes.byref(desc), ctypes.byref(abl)) == 0:
+        out[name.value.decode()] = {"value": val.value, "default": dflt.value, "desc": desc.value.decode(), "ablation": abl.value}
+    return out
+
+
+def ablation_build() -> bool:
+    """True if the loaded library was built with -DDCN_ABL=1 (its "abl" knob is compiled in): results may be wrong on request."""
+    return tuning()["abl"]["ablation"] == 2
 
 
 _lib = None

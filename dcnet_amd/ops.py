@@ -12,7 +12,7 @@ import os
 
 import torch
 
-from .lib import DcnError, lib
+from .lib import DcnError, ablation_build, lib
 
 ACT_NONE, ACT_LEAKY = 0, 1
 
@@ -617,7 +617,7 @@ def conv2d_bwd_weight_b16(x, dy, ksize, stride, slot: int = 0):
     if not (_b16(x) and _b16(dy)):
         raise ValueError("conv2d_bwd_weight_b16: bf16 tensors only")
     dw = torch.empty((cout, ksize, ksize, cin), dtype=torch.float32, device=x.device)
-    if STEP_ABL & 1:
+    if STEP_ABL and _step_abl(1):
         return dw
     nws = lib().conv2d_bwd_weight_ws_b16(n, h, wd, cin, cout, ksize, stride)
     ws = scratch(nws, x.device, slot=slot) if nws > 0 else None
@@ -738,6 +738,15 @@ def conv_geom(device, n: int, h: int, wd: int, ksize: int, stride: int) -> torch
 STEP_ABL = 0           # timing-only ablations of a whole step (results WRONG; bench.py --schedule-tunes "ops.STEP_ABL=1=0"): bit 1 = no weight-gradient
                        # launch at all (dw comes back uninitialised) — what the weight-gradient queue costs the step's wall time; bit 2 = no
                        # persistent BiLSTM backward (it holds 64 KB of LDS on half the CUs for 2.3 ms beside the backbone's backward)
+                       # Honoured only by a library built with -DDCN_ABL=1 (DCN_EXTRA_FLAGS): a default build refuses wrong results.
+
+
+def _step_abl(bit: int) -> bool:
+    """Is ablation `bit` of a non-zero STEP_ABL on?  Raises unless the loaded library is an ablation build."""
+    if not ablation_build():
+        raise RuntimeError(f"ops.STEP_ABL = {STEP_ABL} makes results wrong by construction and is honoured only by an ablation build "
+                           "of the library: DCN_EXTRA_FLAGS=-DDCN_ABL=1 python -m dcnet_amd.build")
+    return bool(STEP_ABL & bit)
 
 
 def conv2d_bwd_weight(x, dy, ksize, stride, cout=None, slot: int = 0, amax_x=None, amax_dy=None):
@@ -749,7 +758,7 @@ def conv2d_bwd_weight(x, dy, ksize, stride, cout=None, slot: int = 0, amax_x=Non
     n, h, wd, cin = x.shape
     cout = dy.shape[3] if cout is None else cout
     dw = torch.empty((cout, 64) if cin == 4 else (cout, ksize, ksize, cin), dtype=torch.float32, device=x.device)
-    if STEP_ABL & 1:
+    if STEP_ABL and _step_abl(1):
         return dw
     nws = lib().conv2d_bwd_weight_ws(n, h, wd, cin, cout, ksize, stride)
     ws = scratch(nws, x.device, slot=slot) if nws > 0 else None
@@ -1729,7 +1738,7 @@ def bilstm_bwd(dout, whh_f, whh_r, acts, cprev, lens):
     _, n, L, H = cprev.shape
     dxg = torch.empty((2, n, L, 4 * H), dtype=torch.float32, device=dout.device)
     _chk(dout, "bilstm_bwd dout")
-    if STEP_ABL & 2:             # timing-only ablation: the persistent BiLSTM backward is not launched (dxg uninitialised)
+    if STEP_ABL and _step_abl(2):    # timing-only ablation: the persistent BiLSTM backward is not launched (dxg uninitialised)
         return dxg.zero_()
     lib().bilstm_bwd(dout.data_ptr(), whh_f.data_ptr(), whh_r.data_ptr(), acts.data_ptr(), cprev.data_ptr(), _p(lens), dxg.data_ptr(),
                      _bilstm_sync(dout.device).data_ptr(), n, L, H, _s())

@@ -25,7 +25,8 @@ def kernel_sources_hash() -> str:
         with open(path, "rb") as fh:
             h.update(fh.read())
     # the compile flags the library was built with (dcnet_amd/build.py writes the stamp): an experiment build
-    # (DCN_EXTRA_FLAGS=-D..._ABL) must not carry the hash of the default build of the same sources
+    # (DCN_EXTRA_FLAGS=-D..._ABL) must not carry the hash of the default build of the same sources, nor must a build that did not
+    # finish (the stamp then reads "building:<key>")
     try:
         with open(os.path.join(_PKG, "build", "FLAGS.stamp"), "rb") as fh:
             h.update(b"flags:" + fh.read().strip())

@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 309
+#define DCN_ABI_VERSION 310
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -640,13 +640,14 @@ int dcn_upsample2_nhwc_bwd(const float* ddst, int ldd, float* dsrc, int lds, int
 int dcn_copy_slice(const float* src, int lds, float* dst, int ldd, int64_t rows, int c, int accumulate, void* stream);
 
 /* Experiment knobs (in-process A/B runs: tools/bench_convs.py --ab, bench.py --schedule-tunes, the DCN_TUNE environment variable).
- * The key's first characters select the knob; the ones that switch a kernel family off and on (1 = default):
- *   "precision" 0..4 (see above) | "1x1dma" conv1.hip | "3x3strip" conv3.hip | "Nconv" nconv.hip (0 off, 2: 32 -> 64 stride-2 data
- *   gradient only, 3: dgrad2 only) | "9tap" wgrad9.hip | "u3row" wgrad3.hip | "jstem" the stem's direct forward | "merge" parity
- *   classes of a stride-2 data gradient in one launch | "bm" force the M tile (64 / 128, 0 = automatic).
- * Sizing knobs: "1stages", "9target", "v3target", "xwgtarget", "zwgsmall", "e2rpw" / "f2nt" (scoring pass), "dbnrev" (sweep
- * direction of the BatchNorm passes).  Unknown keys are ignored by design of the A/B tools; none changes results beyond rounding. */
+ * The key is matched exactly; an unknown key fails with DCN_ERR_ARG and a message that names it.  README.md ("Experiments") holds the
+ * table of all knobs, dcn_tuning_info the same list at run time.  Values that make results wrong by construction (timing ablations)
+ * are refused unless the library was built with the flag the message names. */
 int dcn_set_tuning(const char* key, int value);
+/* Knob number `index` in name order (DCN_ERR_ARG past the last): its name, current value, default, one-line description, and
+ * ablation = 0 for an ordinary knob, 1 for one that exists only in ablation builds and is not compiled into this one, 2 for one that
+ * is.  Strings are static; any output pointer may be NULL. */
+int dcn_tuning_info(int index, const char** name, int* value, int* def, const char** desc, int* ablation);
 
 /* ---- optimiser ---------------------------------------------------------------------------------
  * One fused RMSprop step over `count` fp32 tensors (host arrays of device pointers and element counts):

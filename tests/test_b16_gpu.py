@@ -6,6 +6,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from util import tuning
+
 pytestmark = pytest.mark.gpu
 
 
@@ -64,13 +66,8 @@ def test_b16_conv_forward_dgrad_wgrad_match_their_exact_model(case, tile2b):
         pytest.skip("no launch of this case has a multiple of 256 filters")
     if tile2b == 2 and not (case[5] == 3 and case[6] == 1 and max(case[3], case[4]) > 64):
         pytest.skip("no 3x3 stride-1 launch with more than 64 filters in this case")
-    lib().set_tuning(b"2btile", -1 if tile2b == 1 else 0)
-    lib().set_tuning(b"3h16", 1 if tile2b == 2 else 0)
-    try:
+    with tuning({"2btile": -1 if tile2b == 1 else 0, "3h16": 1 if tile2b == 2 else 0}):
         _conv_case(case)
-    finally:
-        lib().set_tuning(b"2btile", 256)
-        lib().set_tuning(b"3h16", 0)
 
 
 def _conv_case(case):
@@ -100,15 +97,12 @@ def _conv_case(case):
     assert y32.dtype == torch.float32 and float((y32.double().cpu() - ref_y).abs().max()) <= 3e-5 * max(1.0, float(ref_y.abs().max()))
     again, _ = ops.conv2d_fwd_b16(x, wt.reshape(-1), cout, k, st)
     assert torch.equal(again, y)                                                      # bitwise repeatable
-    lib().set_tuning(b"Nb16", 0)               # (the register-bank kernel of the 32 <-> 64 layers off: conv1.hip's gathered tiles)
-    try:
+    with tuning({"Nb16": 0}):                  # (the register-bank kernel of the 32 <-> 64 layers off: conv1.hip's gathered tiles)
         y0, stats0 = ops.conv2d_fwd_b16(x, wt.reshape(-1), cout, k, st, want_stats=True)
         _ulp_close(y0, ref_y, "fwd, gathered tiles")
         assert torch.allclose(stats0.double().sum(0).cpu()[0], yf.sum(0), rtol=1e-5, atol=1e-4 * float(yf.abs().sum(0).max())) or not torch.equal(y0, y)
         _ulp_close(ops.conv2d_bwd_data_b16(_bf(_rand(n, ho, wo, cout, seed=3) / 8).to(dev), wt.reshape(cout, T, cin).permute(2, 1, 0).contiguous().reshape(-1),
                                            (h, w), cin, k, st), xd.grad.permute(0, 2, 3, 1), "dgrad, gathered tiles")
-    finally:
-        lib().set_tuning(b"Nb16", 1)
     # ---- epilogue: scale / shift / LeakyReLU / shortcut (bf16) ----
     sc = (_rand(cout, seed=4).abs() + 0.5).to(dev); sh = _rand(cout, seed=5).to(dev)
     res = _bf(_rand(n, ho, wo, cout, seed=6)).to(dev)
@@ -124,31 +118,25 @@ def _conv_case(case):
     acc = base.clone()
     ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st, out=acc, accumulate=True)
     _ulp_close(acc, ref_dx + base.double().cpu(), "dgrad accumulate")
-    lib().set_tuning(b"Db16", 0)               # (the register-bank stride-2 kernel off: the gathered parity classes)
-    try:
+    with tuning({"Db16": 0}):                  # (the register-bank stride-2 kernel off: the gathered parity classes)
         _ulp_close(ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st), ref_dx, "dgrad, gathered classes")
-    finally:
-        lib().set_tuning(b"Db16", 1)
     assert torch.equal(ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st), dx)      # bitwise repeatable
     dx32 = ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st, out_f32=True)
     assert float((dx32.double().cpu() - ref_dx).abs().max()) <= 3e-5 * max(1.0, float(ref_dx.abs().max()))
     # ---- weight gradient: fp32 out, fp32 accumulation of exact bf16 products ----
     from dcnet_amd.lib import lib
     ref_dw = wd.grad.permute(0, 2, 3, 1)
-    try:
+    with tuning() as tune:
         for knob in (0, 1):                    # the per-tap tile (default) and the filter-row kernel on bf16 inputs (where its shape test admits the layer)
-            lib().set_tuning(b"w3b16", knob)
+            tune({"w3b16": knob})
             dw = ops.conv2d_bwd_weight_b16(x, dy, k, st)
             assert dw.dtype == torch.float32 and dw.shape == (cout, k, k, cin)
             assert float((dw.double().cpu() - ref_dw).abs().max()) <= 5e-5 * max(1.0, float(ref_dw.abs().max())), knob
             assert torch.equal(ops.conv2d_bwd_weight_b16(x, dy, k, st), dw)
-        lib().set_tuning(b"w3b16", 0)
-        lib().set_tuning(b"9b16", 0)           # (the nine-tap kernel off: the per-tap tile for the narrow layers too)
+        tune({"w3b16": 0})
+        tune({"9b16": 0})           # (the nine-tap kernel off: the per-tap tile for the narrow layers too)
         dw0 = ops.conv2d_bwd_weight_b16(x, dy, k, st)
         assert float((dw0.double().cpu() - ref_dw).abs().max()) <= 5e-5 * max(1.0, float(ref_dw.abs().max()))
-    finally:
-        lib().set_tuning(b"w3b16", 0)
-        lib().set_tuning(b"9b16", 1)
 
 
 @pytest.mark.parametrize("shape", [(2, 26, 26, 128, 256, 3), (3, 13, 13, 256, 128, 1), (1, 20, 12, 64, 64, 3)])
@@ -291,15 +279,16 @@ def test_coattention_on_one_f16_piece_in_the_bf16_modes():
     fv0 = torch.nn.functional.normalize(_rand(n, h, w, c, seed=1), dim=3).to(dev)
     g = (_rand(n, h, w, 2 * c, seed=2) / (h * w) ** 0.5).to(dev)
     res = {}
-    try:
-        for tag, mode, knob in (("fp32", "fp32", 1), ("h1", "bf16s", 1), ("two", "bf16s", 0)):
-            ops.set_precision(mode); lib().set_tuning(b"H1gemm3", knob)
-            fv = fv0.clone().requires_grad_(True)
-            out = CoAttentionPairs.apply(fv, 10.0)
-            out.backward(g)
-            res[tag] = (out.detach().clone(), fv.grad.clone())
-    finally:
-        ops.set_precision("fp32"); lib().set_tuning(b"H1gemm3", 1)
+    with tuning() as tune:
+        try:
+            for tag, mode, knob in (("fp32", "fp32", 1), ("h1", "bf16s", 1), ("two", "bf16s", 0)):
+                ops.set_precision(mode); tune({"H1gemm3": knob})
+                fv = fv0.clone().requires_grad_(True)
+                out = CoAttentionPairs.apply(fv, 10.0)
+                out.backward(g)
+                res[tag] = (out.detach().clone(), fv.grad.clone())
+        finally:
+            ops.set_precision("fp32")
     assert lib().gemm3_supported(h * w, c, h * w, n // 2) == 1
     for k_ in (0, 1):
         assert torch.equal(res["two"][k_], res["fp32"][k_])                          # the two-piece path is the fp32 one

@@ -5,6 +5,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from util import tuning
+
 pytestmark = pytest.mark.gpu
 
 
@@ -93,13 +95,11 @@ def test_stem_direct_kernel(dev, n, h, w, cout):
         out["buf"] = buf; out["amax"] = am.clone()
         return out
 
-    try:
-        lib().set_tuning(b"jstem", 0)
+    with tuning() as tune:
+        tune({"jstem": 0})
         old = run()
-        lib().set_tuning(b"jstem", 1)
+        tune({"jstem": 1})
         new = run()
-    finally:
-        lib().set_tuning(b"jstem", 1)
     for r, name in ((old, "c4 tile"), (new, "direct")):
         _close(ops.nhwc_to_nchw(r["y"]), raw, 2e-5, f"stem {name}")
         tot = r["stats"].sum(0).cpu().double()
@@ -449,16 +449,14 @@ def test_split_pipe_is_fp32_accurate(dev, case):
     wt_p = torch.zeros(cout_p, k, k, cin, device=dev); wt_p[:cout] = wt
     dy_p = torch.zeros(*dy.shape[:3], cout_p, device=dev); dy_p[..., :cout] = dy
     err = {}
-    try:
+    with tuning() as tune:
         for mode in (0, 1, 4):
-            lib().set_tuning(b"precision", mode)
+            tune({"precision": mode})
             got = {"fwd": ops.conv2d_fwd(x, wt, k, st)[0],
                    "dgrad": ops.conv2d_bwd_data(dy_p, wt_p, (h, w), k, st),
                    "wgrad": ops.conv2d_bwd_weight(x, dy, k, st)}
             for name, t in got.items():
                 err[(name, mode)] = float((t.double().cpu().reshape(ref[name].shape) - ref[name]).abs().max())
-    finally:
-        lib().set_tuning(b"precision", 4)
     for name in ref:
         scale = float(ref[name].abs().max())
         for mode in (1, 4):
@@ -474,23 +472,21 @@ def test_f16_split_is_live_and_survives_extreme_operands(dev):
     n, h, w, cin, cout = 2, 32, 32, 128, 128
     base = _rand(n, h, w, cin, seed=11)
     wt = (_rand(cout, 3, 3, cin, seed=12) / 34).to(dev)
-    try:
+    with tuning() as tune:
         for mag in (1.0, 1e30, 1e-30):
             x = (base * mag).to(dev)
             ref = F.conv2d(x.permute(0, 3, 1, 2).double().cpu(), wt.permute(0, 3, 1, 2).double().cpu(), padding=1).permute(0, 2, 3, 1)
-            lib().set_tuning(b"precision", 4)
+            tune({"precision": 4})
             y4 = ops.conv2d_fwd(x, wt, 3, 1)[0]
-            lib().set_tuning(b"precision", 1)
+            tune({"precision": 1})
             y1 = ops.conv2d_fwd(x, wt, 3, 1)[0]
             assert torch.isfinite(y4).all()
             _close(y4 / mag, ref / mag, 3e-6, f"f16 split at magnitude {mag}")
             if mag == 1.0:
                 assert not torch.equal(y4, y1), "precision 4 did not select the f16-split kernel"
-        lib().set_tuning(b"precision", 4)
+        tune({"precision": 4})
         z = ops.conv2d_fwd(torch.zeros_like(base).to(dev), wt, 3, 1)[0]
         assert float(z.abs().max()) == 0.0
-    finally:
-        lib().set_tuning(b"precision", 4)
 
 
 def test_split_pipe_forced_on_every_nt_tile(dev):
@@ -499,18 +495,15 @@ def test_split_pipe_forced_on_every_nt_tile(dev):
     from dcnet_amd import ops
     from dcnet_amd.lib import lib
     x = _rand(2, 20, 20, 64, seed=4).to(dev)
-    try:
+    with tuning() as tune:
         for cout in (32, 64, 128):
             wt = (_rand(cout, 3, 3, 64, seed=5) / 24).to(dev)
             ref = F.conv2d(x.permute(0, 3, 1, 2).double().cpu(), wt.permute(0, 3, 1, 2).double().cpu(), padding=1).permute(0, 2, 3, 1)
             for mode in (16, 32):
-                lib().set_tuning(b"precision", 1)          # the forced split is the bf16 three-piece one
-                lib().set_tuning(b"split", mode)
+                tune({"precision": 1})          # the forced split is the bf16 three-piece one
+                tune({"split": mode})
                 y = ops.conv2d_fwd(x, wt, 3, 1)[0]
                 _close(y, ref, 1e-5, f"cout {cout} split {mode}")
-    finally:
-        lib().set_tuning(b"split", 0)
-        lib().set_tuning(b"precision", 4)
 
 
 @pytest.mark.parametrize("case", SPLIT_CASES)
@@ -569,13 +562,11 @@ def test_gemm_nn_split_pipe(dev, m, n, k, kvalid):
     kv = kvalid or k
     ref = a.double().cpu()[:, :kv] @ b.double().cpu()[:kv]
     err = {}
-    try:
+    with tuning() as tune:
         for mode in (0, 1):
-            lib().set_tuning(b"nnsplit", mode)
+            tune({"nnsplit": mode})
             out = ops.gemm_nn(a, b, kvalid=kvalid)
             err[mode] = float((out.double().cpu() - ref).abs().max())
-    finally:
-        lib().set_tuning(b"nnsplit", 1)
     scale = max(1.0, float(ref.abs().max()))
     assert err[1] <= 2 * err[0] + 1e-6 * scale and err[1] <= 3e-5 * scale, err
 
@@ -740,14 +731,14 @@ def test_conv3_strip_kernel(dev, case):
         out["dx_acc"] = dx2
         return out
 
-    try:
-        lib().set_tuning(b"3x3strip", 0)
+    with tuning() as tune:
+        tune({"3x3strip": 0})
         old = run()
         ran16 = False
         # (bm, m16): both M tiles of conv3.hip forced (m16 = 0: 32x32x16 MFMAs), then conv3x.hip (16x16x32 MFMAs, two taps per MFMA) where the
         # 256-row tile is the choice (1, the default) and for every launch it fits (2)
         for bm, m16 in ((0, 0), (128, 0), (256, 0), (0, 1), (0, 2)):
-            lib().set_tuning(b"3x3strip", 1); lib().set_tuning(b"3bm", bm); lib().set_tuning(b"3m16", m16)
+            tune({"3x3strip": 1}); tune({"3bm": bm}); tune({"3m16": m16})
             new = run()
             if m16 == 0:
                 new32 = new
@@ -770,8 +761,6 @@ def test_conv3_strip_kernel(dev, case):
             assert not torch.equal(new["y"], old["y"]) or not torch.equal(new["dx"], old["dx"]), "the strip kernel did not run"
         if cout >= 128 and cout % 4 == 0 and w <= 104:
             assert ran16, "conv3x.hip did not run"
-    finally:
-        lib().set_tuning(b"3x3strip", 1); lib().set_tuning(b"3bm", 0); lib().set_tuning(b"3m16", 1)
 
 
 @pytest.mark.parametrize("case", [(2, 26, 26, 512, 256, 1, 1), (8, 13, 13, 1024, 512, 1, 1), (1, 37, 29, 32, 128, 1, 1), (2, 52, 52, 256, 128, 1, 1),
@@ -829,13 +818,13 @@ def test_conv1_lds_dma_kernel(dev, case):
         lib().prof_collect(ctypes.addressof(c), ctypes.addressof(m), ctypes.addressof(wk), 0)
         return c[35]
 
-    try:
-        lib().set_tuning(b"1x1dma", 0)
+    with tuning() as tune:
+        tune({"1x1dma": 0})
         old = run()
         assert launches() == 0
-        lib().set_tuning(b"1x1dma", 1)
+        tune({"1x1dma": 1})
         for stages in (32, 33, 44, 63):
-            lib().set_tuning(b"1stages", stages)
+            tune({"1stages": stages})
             new = run()
             _close(new["y"], ref, 2e-5, f"conv1 fwd epilogue stages={stages}")
             _close(new["stats"][:, 0].double().sum(0), rawl.reshape(-1, cout).sum(0), 1e-4, "conv1 stats sum")
@@ -855,8 +844,6 @@ def test_conv1_lds_dma_kernel(dev, case):
         if cout % 128 == 0 and (k == 1 or st == 2):
             assert launches() >= 3, "the LDS-DMA kernel did not take the forward launches"
         # (32 / 64 filters on the fp32-pipe narrow tiles and 3x3 stride-1 launches stay where they were: csrc/conv1.hip conv1_will_take)
-    finally:
-        lib().set_tuning(b"1x1dma", 1); lib().set_tuning(b"1stages", 32)
 
 
 @pytest.mark.parametrize("case", [(8, 13, 13, 64, 128), (2, 52, 52, 32, 128), (2, 40, 24, 96, 160), (5, 17, 31, 64, 136),
@@ -887,30 +874,30 @@ def test_conv3_strip_kernel_bf16_operands(dev, case):
     b = fb.get(0, w_oihw)
     assert torch.equal(b["b16"].view(cout_p, 3, 3, cin), w_oihw.permute(0, 2, 3, 1).to(torch.bfloat16))
     assert torch.equal(b["tb16"].view(cin, 3, 3, cout_p), w_oihw.permute(1, 2, 3, 0).to(torch.bfloat16))
-    try:
-        ops.set_precision("bf16")
-        lib().set_tuning(b"3x3strip", 0)
-        y0, _ = ops.conv2d_fwd(x, b["ohwi"], 3, 1, scale, shift, ops.ACT_LEAKY, 0.1, want_stats=True, w_b16=b["b16"])
-        d0 = ops.conv2d_bwd_data(dy, b["ohwi"], (h, w), 3, 1, wt_ready=(b["t"], b["tsplit"]), wt_b16=b["tb16"])
-        lib().set_tuning(b"3x3strip", 1)
-        for bm in (0, 128, 256):
-            lib().set_tuning(b"3bm", bm)
-            y1, st = ops.conv2d_fwd(x, b["ohwi"], 3, 1, scale, shift, ops.ACT_LEAKY, 0.1, want_stats=True, w_b16=b["b16"])
-            d1 = ops.conv2d_bwd_data(dy, b["ohwi"], (h, w), 3, 1, wt_ready=(b["t"], b["tsplit"]), wt_b16=b["tb16"])
-            _close(y1, ref, 2e-5, f"bf16 strip fwd bm={bm}")
-            _close(st[:, 0].double().sum(0), rawl.reshape(-1, cout_p).sum(0), 1e-4, "bf16 strip stats")
-            # (a data gradient with <= 64 input channels runs on the narrow fp32-operand tiles in every mode: closer to fp32 than
-            #  to the bf16 model)
-            _close(d1, xd.grad.permute(0, 2, 3, 1), 2e-5 if cin > 64 else 1e-2, f"bf16 strip dgrad bm={bm}")
-            _close(y1, y0, 2e-6, "bf16 strip vs tile fwd"); _close(d1, d0, 2e-6, "bf16 strip vs tile dgrad")
-        if w <= 64:
-            assert not torch.equal(y1, y0) or not torch.equal(d1, d0), "the strip kernel did not run"
-        # without the bf16 bank the mode stays on the implicit-GEMM tile: same exact model
-        y2, _ = ops.conv2d_fwd(x, b["ohwi"], 3, 1, scale, shift, ops.ACT_LEAKY, 0.1)
-        assert torch.equal(y2, y0)
-    finally:
-        lib().set_tuning(b"3x3strip", 1); lib().set_tuning(b"3bm", 0)
-        ops.set_precision("fp32")
+    with tuning() as tune:
+        try:
+            ops.set_precision("bf16")
+            tune({"3x3strip": 0})
+            y0, _ = ops.conv2d_fwd(x, b["ohwi"], 3, 1, scale, shift, ops.ACT_LEAKY, 0.1, want_stats=True, w_b16=b["b16"])
+            d0 = ops.conv2d_bwd_data(dy, b["ohwi"], (h, w), 3, 1, wt_ready=(b["t"], b["tsplit"]), wt_b16=b["tb16"])
+            tune({"3x3strip": 1})
+            for bm in (0, 128, 256):
+                tune({"3bm": bm})
+                y1, st = ops.conv2d_fwd(x, b["ohwi"], 3, 1, scale, shift, ops.ACT_LEAKY, 0.1, want_stats=True, w_b16=b["b16"])
+                d1 = ops.conv2d_bwd_data(dy, b["ohwi"], (h, w), 3, 1, wt_ready=(b["t"], b["tsplit"]), wt_b16=b["tb16"])
+                _close(y1, ref, 2e-5, f"bf16 strip fwd bm={bm}")
+                _close(st[:, 0].double().sum(0), rawl.reshape(-1, cout_p).sum(0), 1e-4, "bf16 strip stats")
+                # (a data gradient with <= 64 input channels runs on the narrow fp32-operand tiles in every mode: closer to fp32 than
+                #  to the bf16 model)
+                _close(d1, xd.grad.permute(0, 2, 3, 1), 2e-5 if cin > 64 else 1e-2, f"bf16 strip dgrad bm={bm}")
+                _close(y1, y0, 2e-6, "bf16 strip vs tile fwd"); _close(d1, d0, 2e-6, "bf16 strip vs tile dgrad")
+            if w <= 64:
+                assert not torch.equal(y1, y0) or not torch.equal(d1, d0), "the strip kernel did not run"
+            # without the bf16 bank the mode stays on the implicit-GEMM tile: same exact model
+            y2, _ = ops.conv2d_fwd(x, b["ohwi"], 3, 1, scale, shift, ops.ACT_LEAKY, 0.1)
+            assert torch.equal(y2, y0)
+        finally:
+            ops.set_precision("fp32")
     # it IS reduced precision: the fp32-mode result differs from the bf16 model by far more than the tolerance above
     yf, _ = ops.conv2d_fwd(x, b["ohwi"], 3, 1, scale, shift, ops.ACT_LEAKY, 0.1)
     assert float((yf.double().cpu() - ref).abs().max()) > 1e-4
@@ -987,20 +974,21 @@ def test_dgrad2_register_bank_kernel(dev, case):
     fb = ops.FilterBanks([wdev], dev); fb.refresh()
     b = fb.get(0, wdev)
     base = _rand(n, h, w, cin, seed=63).to(dev)
-    try:
-        lib().set_tuning(b"Nconv", 0)
-        old = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
-        lib().set_tuning(b"Nconv", 1)
-        lib().prof_enable(1)
-        new = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
-        lib().prof_enable(0)
-        ran = _prof_launches(37)
-        new_c = ops.conv2d_bwd_data(dy.contiguous(), w_ohwi, (h, w), 3, 2)
-        new_b = ops.conv2d_bwd_data(dy, b["ohwi"], (h, w), 3, 2, amax_w=b["amax"], wt_ready=(b["t"], b["tsplit"]))
-        acc = base.clone()
-        ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2, out=acc, accumulate=True)
-    finally:
-        lib().set_tuning(b"Nconv", 1); lib().prof_enable(0)
+    with tuning() as tune:
+        try:
+            tune({"Nconv": 0})
+            old = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
+            tune({"Nconv": 1})
+            lib().prof_enable(1)
+            new = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
+            lib().prof_enable(0)
+            ran = _prof_launches(37)
+            new_c = ops.conv2d_bwd_data(dy.contiguous(), w_ohwi, (h, w), 3, 2)
+            new_b = ops.conv2d_bwd_data(dy, b["ohwi"], (h, w), 3, 2, amax_w=b["amax"], wt_ready=(b["t"], b["tsplit"]))
+            acc = base.clone()
+            ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2, out=acc, accumulate=True)
+        finally:
+            lib().prof_enable(0)
     assert ran == 1, "the register-bank kernel did not run"
     _close(new, ref, 2e-5, "dgrad2")
     _close(old, ref, 2e-5, "implicit-GEMM classes")
@@ -1141,31 +1129,30 @@ def test_bn_tap_on_stride1_data_gradients(dev, case, m16):
     n, h, w, cin, cout, k = case
     if m16 and k != 3:
         pytest.skip("conv3x.hip only takes 3x3 launches")
-    lib().set_tuning(b"3m16", m16)           # conv3.hip (0) / conv3x.hip wherever it fits (2)
-    wgt = (_rand(cout, cin, k, k, seed=101) / (3 * k)).to(dev)
-    w_ohwi = wgt.permute(0, 2, 3, 1).contiguous()
-    dy = _rand(n, h, w, cout, seed=102).to(dev)
-    y_prev = (_rand(n, h, w, cin, seed=103) * 2).to(dev)
-    gamma = (_rand(cin, seed=104)).to(dev); beta = (_rand(cin, seed=105) / 2).to(dev)      # (negative gammas too)
-    mean = y_prev.reshape(-1, cin).mean(0); invstd = 1.0 / torch.sqrt(y_prev.reshape(-1, cin).var(0, unbiased=False) + 1e-5)
-    tap = dict(y=y_prev, mean=mean, invstd=invstd, gamma=gamma, beta=beta, act=ops.ACT_LEAKY, slope=0.1)
-    for accumulate in (False, True):
-        base = _rand(n, h, w, cin, seed=106).to(dev)
-        plain = base.clone() if accumulate else None
-        plain = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), k, 1, out=plain, accumulate=accumulate)
-        tapped = base.clone() if accumulate else None
-        tapped, part = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), k, 1, out=tapped, accumulate=accumulate, tap=tap)
-        assert part is not None, "the launch did not tap"
-        assert torch.equal(plain, tapped)
-        ref, r_ = ops._bn_bwd_partials(y_prev, plain, mean, invstd, gamma, beta, ops.ACT_LEAKY, 0.1, None)
-        ref = ref[:r_ * 2 * cin].view(r_, 2, cin).clone()
-        _close(part.double().sum(0), ref.double().sum(0), 2e-5, f"tap partial sums (accumulate={accumulate})")
-        # the BatchNorm backward fed with the tapped partials equals the one that reduces by itself
-        d0 = ops.bn_act_bwd(y_prev, plain, mean, invstd, gamma, beta, ops.ACT_LEAKY, 0.1)
-        d1 = ops.bn_act_bwd(y_prev, plain, mean, invstd, gamma, beta, ops.ACT_LEAKY, 0.1, part=part)
-        for a_, b_ in zip(d0, d1):
-            _close(a_, b_, 2e-5, "bn_act_bwd with tapped partials")
-    lib().set_tuning(b"3m16", 1)
+    with tuning({"3m16": m16}):          # conv3.hip (0) / conv3x.hip wherever it fits (2)
+        wgt = (_rand(cout, cin, k, k, seed=101) / (3 * k)).to(dev)
+        w_ohwi = wgt.permute(0, 2, 3, 1).contiguous()
+        dy = _rand(n, h, w, cout, seed=102).to(dev)
+        y_prev = (_rand(n, h, w, cin, seed=103) * 2).to(dev)
+        gamma = (_rand(cin, seed=104)).to(dev); beta = (_rand(cin, seed=105) / 2).to(dev)      # (negative gammas too)
+        mean = y_prev.reshape(-1, cin).mean(0); invstd = 1.0 / torch.sqrt(y_prev.reshape(-1, cin).var(0, unbiased=False) + 1e-5)
+        tap = dict(y=y_prev, mean=mean, invstd=invstd, gamma=gamma, beta=beta, act=ops.ACT_LEAKY, slope=0.1)
+        for accumulate in (False, True):
+            base = _rand(n, h, w, cin, seed=106).to(dev)
+            plain = base.clone() if accumulate else None
+            plain = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), k, 1, out=plain, accumulate=accumulate)
+            tapped = base.clone() if accumulate else None
+            tapped, part = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), k, 1, out=tapped, accumulate=accumulate, tap=tap)
+            assert part is not None, "the launch did not tap"
+            assert torch.equal(plain, tapped)
+            ref, r_ = ops._bn_bwd_partials(y_prev, plain, mean, invstd, gamma, beta, ops.ACT_LEAKY, 0.1, None)
+            ref = ref[:r_ * 2 * cin].view(r_, 2, cin).clone()
+            _close(part.double().sum(0), ref.double().sum(0), 2e-5, f"tap partial sums (accumulate={accumulate})")
+            # the BatchNorm backward fed with the tapped partials equals the one that reduces by itself
+            d0 = ops.bn_act_bwd(y_prev, plain, mean, invstd, gamma, beta, ops.ACT_LEAKY, 0.1)
+            d1 = ops.bn_act_bwd(y_prev, plain, mean, invstd, gamma, beta, ops.ACT_LEAKY, 0.1, part=part)
+            for a_, b_ in zip(d0, d1):
+                _close(a_, b_, 2e-5, "bn_act_bwd with tapped partials")
 
 
 @pytest.mark.parametrize("case", PRE_CASES)
@@ -1257,16 +1244,17 @@ def test_nconv1_register_bank_kernels(dev, case):
 
         def run():
             return ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 1), None, ops.conv2d_bwd_data(dy.contiguous(), w_ohwi, (h, w), 3, 1)
-    try:
-        lib().set_tuning(b"Nconv", 0)
-        old = run()
-        lib().set_tuning(b"Nconv", 1)
-        lib().prof_enable(1)
-        new = run()
-        lib().prof_enable(0)
-        ran = _prof_launches(38)
-    finally:
-        lib().set_tuning(b"Nconv", 1); lib().prof_enable(0)
+    with tuning() as tune:
+        try:
+            tune({"Nconv": 0})
+            old = run()
+            tune({"Nconv": 1})
+            lib().prof_enable(1)
+            new = run()
+            lib().prof_enable(0)
+            ran = _prof_launches(38)
+        finally:
+            lib().prof_enable(0)
     assert ran == 2, "the register-bank kernel did not run"
     _close(new[0], ref, 2e-5, f"nconv1 {mode}")
     _close(old[0], ref, 2e-5, "implicit-GEMM tile")
@@ -1332,18 +1320,19 @@ def test_nconv_kernels_on_tensors_beyond_2_gib(dev):
     wgt = (torch.randn(64, 32, 3, 3, generator=g) / 6)
     w_ohwi = wgt.permute(0, 2, 3, 1).contiguous().to(dev)
     dy = torch.randn(n, h // 2, w // 2, 64, device=dev)
-    try:
-        lib().set_tuning(b"Nconv", 0)
-        y0, st0 = ops.conv2d_fwd(x, w_ohwi, 3, 2, want_stats=True)
-        dx0 = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
-        lib().set_tuning(b"Nconv", 1)
-        lib().prof_enable(1)
-        y1, st1 = ops.conv2d_fwd(x, w_ohwi, 3, 2, want_stats=True)
-        dx1 = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
-        lib().prof_enable(0)
-        ran = _prof_launches(37) + _prof_launches(38)
-    finally:
-        lib().set_tuning(b"Nconv", 1); lib().prof_enable(0)
+    with tuning() as tune:
+        try:
+            tune({"Nconv": 0})
+            y0, st0 = ops.conv2d_fwd(x, w_ohwi, 3, 2, want_stats=True)
+            dx0 = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
+            tune({"Nconv": 1})
+            lib().prof_enable(1)
+            y1, st1 = ops.conv2d_fwd(x, w_ohwi, 3, 2, want_stats=True)
+            dx1 = ops.conv2d_bwd_data(dy, w_ohwi, (h, w), 3, 2)
+            lib().prof_enable(0)
+            ran = _prof_launches(37) + _prof_launches(38)
+        finally:
+            lib().prof_enable(0)
     assert ran == 2, "the register-bank kernels declined the large tensors"
     assert float((y1 - y0).abs().max()) <= 2e-5 * float(y0.abs().max())
     assert float((dx1 - dx0).abs().max()) <= 2e-5 * float(dx0.abs().max())
@@ -1442,31 +1431,29 @@ def test_wgrad9_nine_tap_kernel(dev, case):
     wgt = torch.zeros(cout, cin, 3, 3, dtype=torch.float64, requires_grad=True)
     F.conv2d(xd, wgt, padding=1, stride=st).backward(dy.permute(0, 3, 1, 2).double().cpu())
     ref = wgt.grad.permute(0, 2, 3, 1)                             # OHWI
-    try:
-        lib().set_tuning(b"9tap", 0)
-        old = ops.conv2d_bwd_weight(x, dy, 3, st)
-        lib().set_tuning(b"9tap", 3)                               # (3: the 64 -> 128 form at both strides)
-        lib().prof_enable(1)
-        new = ops.conv2d_bwd_weight(x, dy, 3, st)
-        lib().prof_enable(0)
-        ran = _prof_launches(36)
-        new_c = ops.conv2d_bwd_weight(x, dy.contiguous(), 3, st)
-        for target in (1, 7, 4096):                                # one slab ... as many as the positions allow
-            lib().set_tuning(b"9target", target)
-            alt = ops.conv2d_bwd_weight(x, dy, 3, st)
-            _close(alt, ref, 3e-5, f"wgrad9 target {target}")
-        lib().set_tuning(b"9target", 512)
-        again = ops.conv2d_bwd_weight(x, dy, 3, st)
-    finally:
-        lib().set_tuning(b"9tap", W9_DEFAULT); lib().set_tuning(b"9target", 512); lib().prof_enable(0)
+    with tuning() as tune:
+        try:
+            tune({"9tap": 0})
+            old = ops.conv2d_bwd_weight(x, dy, 3, st)
+            tune({"9tap": 3})                               # (3: the 64 -> 128 form at both strides)
+            lib().prof_enable(1)
+            new = ops.conv2d_bwd_weight(x, dy, 3, st)
+            lib().prof_enable(0)
+            ran = _prof_launches(36)
+            new_c = ops.conv2d_bwd_weight(x, dy.contiguous(), 3, st)
+            for target in (1, 7, 4096):                                # one slab ... as many as the positions allow
+                tune({"9target": target})
+                alt = ops.conv2d_bwd_weight(x, dy, 3, st)
+                _close(alt, ref, 3e-5, f"wgrad9 target {target}")
+            tune({"9target": 512})
+            again = ops.conv2d_bwd_weight(x, dy, 3, st)
+        finally:
+            lib().prof_enable(0)
     assert ran == 1, "the nine-tap kernel did not run"
     _close(new, ref, 3e-5, "wgrad9")
     _close(old, ref, 3e-5, "the kernel it replaces")
     assert torch.equal(new, new_c)                                 # the pixel stride of dY changes nothing
     assert torch.equal(new, again)                                 # fixed summation order
-
-
-W9_DEFAULT = 2      # csrc/wgrad9.hip g_w9
 
 
 W1X_CASES = [
@@ -1491,18 +1478,16 @@ def test_wgrad1x_wide_tile_kernel(dev, case):
     wide = (_rand(n, h, w, cout + 32, seed=52) / 8).to(dev)
     dy = wide[..., 16:16 + cout]
     ref = torch.einsum("nhwo,nhwi->oi", dy.double().cpu(), x.double().cpu()).view(cout, 1, 1, cin)
-    try:
-        lib().set_tuning(b"Y1wide", 0)
+    with tuning() as tune:
+        tune({"Y1wide": 0})
         old = ops.conv2d_bwd_weight(x, dy, 1, 1)
-        lib().set_tuning(b"Y1wide", 1)
+        tune({"Y1wide": 1})
         new = ops.conv2d_bwd_weight(x, dy, 1, 1)
         again = ops.conv2d_bwd_weight(x, dy.contiguous(), 1, 1)
         for target in (64, 1024):
-            lib().set_tuning(b"Y1wide", target)
+            tune({"Y1wide": target})
             alt = ops.conv2d_bwd_weight(x, dy, 1, 1)
             _close(alt, ref, 3e-5, f"wgrad1x target {target}")
-    finally:
-        lib().set_tuning(b"Y1wide", 1)
     _close(new, ref, 3e-5, "wgrad1x")
     _close(old, ref, 3e-5, "128 x 128 tile")
     _close(new, old, 3e-6, "wgrad1x vs the 128 x 128 tile")
@@ -1540,39 +1525,37 @@ def test_wgrad3_filter_row_kernel(dev, case, m16):
     wgt = torch.zeros(cout, cin, 3, 3, dtype=torch.float64, requires_grad=True)
     F.conv2d(xd, wgt, padding=1).backward(dy.permute(0, 3, 1, 2).double().cpu())
     ref = wgt.grad.permute(0, 2, 3, 1)                             # OHWI
-    try:
-        lib().set_tuning(b"U3m16", m16)                            # 16x16x32 MFMAs, 32 positions per K-step (1) / 32x32x16, 16 positions (0, the default)
-        lib().set_tuning(b"u3row", 0)
+    with tuning() as tune:
+        tune({"U3m16": m16})                            # 16x16x32 MFMAs, 32 positions per K-step (1) / 32x32x16, 16 positions (0, the default)
+        tune({"u3row": 0})
         old = ops.conv2d_bwd_weight(x, dy, 3, 1)
-        lib().set_tuning(b"u3row", 1)
+        tune({"u3row": 1})
         new = ops.conv2d_bwd_weight(x, dy, 3, 1)
         new_c = ops.conv2d_bwd_weight(x, dy.contiguous(), 3, 1)
         if m16:
-            lib().set_tuning(b"U3m16", 0)
+            tune({"U3m16": 0})
             other = ops.conv2d_bwd_weight(x, dy, 3, 1)
-            lib().set_tuning(b"U3m16", 1)
+            tune({"U3m16": 1})
             assert not torch.equal(new, other), "the 16x16x32 build did not run"
             _close(new, other, 3e-6, "wgrad3: 16x16x32 vs 32x32x16")
         for target in (96, 2048):                                  # one split ... many splits
-            lib().set_tuning(b"v3target", target)
+            tune({"v3target": target})
             alt = ops.conv2d_bwd_weight(x, dy, 3, 1)
             _close(alt, ref, 3e-5, f"wgrad3 target {target}")
-    finally:
-        lib().set_tuning(b"u3row", 1); lib().set_tuning(b"v3target", 512); lib().set_tuning(b"U3m16", 0)
     # bf16-operand mode (configs[2]; also the weight gradient of the fp8 mode): the same kernel with one bf16 plane per operand,
     # against its exact model — the fp64 weight gradient of the bf16-rounded tensors
     rb = lambda t: t.to(torch.bfloat16).double()
     wgt16 = torch.zeros(cout, cin, 3, 3, dtype=torch.float64, requires_grad=True)
     F.conv2d(rb(x.cpu()).permute(0, 3, 1, 2), wgt16, padding=1).backward(rb(dy.cpu()).permute(0, 3, 1, 2))
     ref16 = wgt16.grad.permute(0, 2, 3, 1)
-    try:
-        ops.set_precision("bf16")
-        got16 = ops.conv2d_bwd_weight(x, dy, 3, 1)
-        lib().set_tuning(b"u3row", 0)
-        old16 = ops.conv2d_bwd_weight(x, dy, 3, 1)
-    finally:
-        lib().set_tuning(b"u3row", 1)
-        ops.set_precision("fp32")
+    with tuning() as tune:
+        try:
+            ops.set_precision("bf16")
+            got16 = ops.conv2d_bwd_weight(x, dy, 3, 1)
+            tune({"u3row": 0})
+            old16 = ops.conv2d_bwd_weight(x, dy, 3, 1)
+        finally:
+            ops.set_precision("fp32")
     _close(got16, ref16, 3e-5, "wgrad3 bf16 operands vs exact model")
     _close(old16, ref16, 3e-5, "per-tap bf16 operands vs exact model")     # (64-channel sides run on the 128x128 tile as well)
     assert float((got16.double().cpu() - ref).abs().max()) > 1e-5 * max(1.0, float(ref.abs().max()))      # it IS reduced precision
@@ -1587,7 +1570,7 @@ SLAB_FOLD_CASES = [
     # n, h, w, cin, cout, k, stride, knobs  — every kernel family that folds (csrc/slabsum.h), ragged tiles, many and few splits
     (8, 13, 13, 128, 256, 3, 1, {}),                      # wgrad3_kernel<2>
     (2, 33, 31, 136, 160, 3, 1, {}),                      # ... ragged channel tiles
-    (9, 11, 12, 192, 320, 3, 1, {b"U3m16": 1}),           # wgrad3x_kernel
+    (9, 11, 12, 192, 320, 3, 1, {"U3m16": 1}),            # wgrad3x_kernel
     (8, 26, 26, 256, 512, 1, 1, {}),                      # wgrad1x_kernel<4>
     (7, 25, 27, 384, 192, 1, 1, {}),                      # ... ragged
     (4, 26, 26, 256, 128, 1, 1, {}),                      # wgrad_kernel<128,128> f16 split
@@ -1608,23 +1591,17 @@ def test_slab_fold_is_bitwise_the_separate_pass(dev, case):
     ho, wo = (h + 2 * (k // 2) - k) // s + 1, (w + 2 * (k // 2) - k) // s + 1
     x = _rand(n, h, w, cin, seed=61).to(dev)
     dy = (_rand(n, ho, wo, cout, seed=62) / 8).to(dev)
-    try:
-        for kk, vv in knobs.items():
-            lib().set_tuning(kk, vv)
-        lib().set_tuning(b"Slabfold", 0)
+    with tuning(knobs) as tune:
+        tune({"Slabfold": 0})
         sep = ops.conv2d_bwd_weight(x, dy, k, s)
-        lib().set_tuning(b"Slabfold", 1 << 20)               # no size limit: every launch with more than one split folds
+        tune({"Slabfold": 1 << 20})               # no size limit: every launch with more than one split folds
         folds = [ops.conv2d_bwd_weight(x, dy, k, s) for _ in range(3)]
         if cin % 8 == 0 and cout % 8 == 0:
             xb, dyb = x.to(torch.bfloat16), dy.to(torch.bfloat16)
             fold16 = ops.conv2d_bwd_weight_b16(xb, dyb, k, s)
-            lib().set_tuning(b"Slabfold", 0)
+            tune({"Slabfold": 0})
             sep16 = ops.conv2d_bwd_weight_b16(xb, dyb, k, s)
             assert torch.equal(fold16, sep16)
-    finally:
-        lib().set_tuning(b"Slabfold", 0)                     # (the default: off — measured slower in the step, csrc/slabsum.h)
-        for kk in knobs:
-            lib().set_tuning(kk, 0)
     for f in folds:
         assert torch.equal(f, sep)
     assert int(ops.slab_counters(dev, 0).abs().sum()) == 0

@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (test infrastructure; may import oracle/)."""
+import contextlib
 import json
 import os
 import random
@@ -45,3 +46,22 @@ def build_product(size, sd, dev, test_model=False):
 
 def maxdiff(a, b):
     return float((a.detach().cpu().double() - b.detach().cpu().double()).abs().max())
+
+
+@contextlib.contextmanager
+def tuning(knobs=None):
+    """``with tuning({"Nconv": 0}) as tune:`` sets dcn_set_tuning knobs; ``tune({...})`` sets more inside the block.  On exit every knob
+    has the value it had on entry again, read through dcn_tuning_info: no test needs to know a default."""
+    from dcnet_amd.lib import lib, tuning as read
+
+    def tune(kv):
+        for k, v in kv.items():
+            lib().set_tuning(k.encode(), v)
+
+    before = {k: v["value"] for k, v in read().items()}
+    try:
+        tune(knobs or {})
+        yield tune
+    finally:
+        for _ in range(2):          # ("precision" drives "wsplit" as well: the second pass puts back what the first pass's setters moved)
+            tune({k: before[k] for k, v in read().items() if v["value"] != before[k]})

@@ -1,5 +1,8 @@
 """Timing ablations of one conv kernel on a few layer shapes (N = 64), in one process, interleaved rounds, minimum per arm.
-Needs a build with the ablation variants compiled in (e.g. DCN_EXTRA_FLAGS=-DC3_ABL=1 python -m dcnet_amd.build --force).
+The ablation values make results WRONG and exist only in builds that ask for them; a default build refuses them:
+    DCN_EXTRA_FLAGS="-DC3_ABL=1" python -m dcnet_amd.build     # "3abl" (conv3.hip)
+    DCN_EXTRA_FLAGS="-DDCN_ABL=1" python -m dcnet_amd.build    # "abl" (igemm.hip, wgrad.hip), "Slabfold" = -1
+    DCN_EXTRA_FLAGS="-DG3_ABL=1" python -m dcnet_amd.build     # bits 4-7 of "Gemm3" (tools/bench_gemm3.py --abl)
 
     python tools/bench_abl.py --knob 3abl --values 0,1,3,7,8,15,16 --shapes 128,256,3,1,52;256,512,3,1,26 [--pass fwd|dgrad|wgrad]
 """

@@ -1,5 +1,5 @@
 """Per-layer timing of the bf16-storage convolution kernels (csrc/conv1.hip conv1b, wgrad.hip IN16) on the benchmark's layer shapes.
-    python tools/bench_b16.py [--set key=value,...]   (dcn_set_tuning knobs, e.g. bwide=256, btall=512)"""
+    python tools/bench_b16.py [--set key=value,...]   (dcn_set_tuning knobs, e.g. bwide=256, 2btile=128)"""
 import argparse, os, sys, torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -25,7 +25,7 @@ def main():
     ap = argparse.ArgumentParser(); ap.add_argument("--g", type=int, default=52); ap.add_argument("--b", type=int, default=32)
     ap.add_argument("--c", type=int, default=512)
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--abl", type=str, default="0", help="timing-only ablations to run (bits: 1 no DMA, 2 no fragment reads, 4 no MFMAs; needs G3_ABL 1) + 16 * schedule variant")
+    ap.add_argument("--abl", type=str, default="0", help="timing-only ablations to run (bits: 1 no DMA, 2 no fragment reads, 4 no MFMAs; needs a -DG3_ABL=1 build) + 16 * schedule variant")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     hw, b, c = args.g * args.g, args.b, args.c
