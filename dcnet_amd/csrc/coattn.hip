@@ -14,6 +14,7 @@
 // All GEMMs run on the shared engines: NT and NN forms on igemm.hip, TN on wgrad.hip.
 #include "igemm.h"
 #include "prof.h"
+#include "coattn.h"
 
 int tn_gemm_batched(const float* A, int lda, long long a_bs, const float* B, int ldb, long long b_bs,
                     float* C, int ldc, long long c_bs, const float* row_scale,
@@ -214,6 +215,27 @@ void gemm_params(IgemmParams& p, const float* A, int lda, long long a_bs, const 
 // the products of a (b, hw, c) problem run on gemm3.hip (pre-split operands)?  A function of the shape, the precision mode and the
 // "Gemm3" knob only: dcn_coattn_bwd must see what dcn_coattn_fwd saw (E is saved in the form the forward wrote).
 static bool on_gemm3(int b, int hw, int c) { return c % 32 == 0 && gemm3_applicable(hw, c, hw, b) && gemm3_applicable(hw, hw, c, b); }
+
+// ---- shared with video.hip (coattn.h): the same kernels on operands that live in a feature bank ---------------------------------
+int coattn_ld_pad(int hw) { return ld_pad(hw); }
+bool coattn_on_gemm3(int b, int hw, int c) { return on_gemm3(b, hw, c); }
+unsigned* coattn_ws_amax(float* ws, int b, int hw) { return reinterpret_cast<unsigned*>(ws + (int64_t)cdiv(hw, EXP_ROWS) * b * ld_pad(hw)); }
+int coattn_amax_init(unsigned* am, hipStream_t stream) {
+  hipLaunchKernelGGL(amax_init_kernel, dim3(1), dim3(256), 0, stream, am);
+  DCN_CHECK_LAUNCH("coattn amax_init");
+  return DCN_OK;
+}
+int coattn_exp_sums(float* E, int b, int hw, float temperature, float* rinv, float* cinv, float* ws, bool split, hipStream_t stream) {
+  const int ldE = ld_pad(hw), nrb = cdiv(hw, EXP_ROWS);
+  const int pid = prof_begin(12, (double)b * hw * ldE * 8.0, stream);
+  if (split) hipLaunchKernelGGL(exp_sums_kernel<true>, dim3(nrb, b), dim3(256), 0, stream, E, hw, ldE, temperature, rinv, ws);
+  else hipLaunchKernelGGL(exp_sums_kernel<false>, dim3(nrb, b), dim3(256), 0, stream, E, hw, ldE, temperature, rinv, ws);
+  prof_end(pid, stream);
+  DCN_CHECK_LAUNCH("exp_sums");
+  hipLaunchKernelGGL(colsum_inv_kernel, dim3(cdiv(hw, 256), b), dim3(256), 0, stream, ws, nrb, b, hw, ldE, cinv);
+  DCN_CHECK_LAUNCH("colsum_inv");
+  return DCN_OK;
+}
 
 extern "C" int64_t dcn_coattn_fwd_ws(int b, int hw, int c) {
   (void)c;

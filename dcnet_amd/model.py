@@ -384,11 +384,24 @@ class grounding_model(nn.Module):
         corr, sim, neg_sim = NormScore.apply(corr_raw, flang_attn, self.training)
         return fv, corr, sim, neg_sim, self._fusion_head(s, corr, flang)
 
+    def _map_scale(self, s: int, raw_s):
+        """"Encode" half of a scale, up to the normalisation: mapping_visu on the backbone tap (model/test_DCNet_model.py:299-301)."""
+        return self.mapping_visu[s](raw_s, self.visumodel._tap_amax[s])
+
+    def _corr_accumulate(self, s: int, cat, acc, scale: float):
+        """corr_conv on a concat [f_centre | f_attn] (B,H,W,2E) and acc (+)= scale * normalize(.)  (:312-332, inference form)."""
+        one = ops.amax_const(cat.device, 1.0) if ops.use_amax() else None
+        return NormAccumulate.apply(self.corr_conv[s][0](cat, one), acc, scale)
+
+    def _score_scale(self, s: int, corr, flang, flang_attn):
+        """"Correspond" half behind the mean: sim_score (:386-391) and the fusion head.  Returns (sim, logits)."""
+        return RowDot.apply(corr, flang_attn, False), self._fusion_head(s, corr, flang)
+
     def _scale_nframe(self, s: int, raw_s, flang, flang_attn, B: int, n_frame: int):
         """Scale s of the inference model: centre frame vs every other frame, mean of the normalised
         correspondence features (model/test_DCNet_model.py:299-332), then the shared head."""
         one = ops.amax_const(raw_s.device, 1.0) if ops.use_amax() else None
-        fv = L2Norm.apply(self.mapping_visu[s](raw_s, self.visumodel._tap_amax[s]))
+        fv = L2Norm.apply(self._map_scale(s, raw_s))
         _, h, w, e = fv.shape
         clips = fv.view(B, n_frame, h * w, e)
         ctr, acc = n_frame // 2, None                                            # :303
@@ -405,8 +418,8 @@ class grounding_model(nn.Module):
             else:
                 acc = NormAccumulate.apply(z, acc, 1.0 / (n_frame - 1))          # :277-280, mean :324-332
         corr = acc
-        sim = RowDot.apply(corr, flang_attn, False)                              # :386-391
-        return fv, corr, sim, None, self._fusion_head(s, corr, flang)
+        sim, logits = self._score_scale(s, corr, flang, flang_attn)
+        return fv, corr, sim, None, logits
 
     def _coord_rows(self, grids, device):
         """(P,8) coordinate rows of the three scales, coarsest first (model/DCNet_model.py:565-567); identical for every image."""

@@ -1622,6 +1622,66 @@ def post_fusion(center, ref, ref_score, valid=None):
     return best, fused
 
 
+# ---- whole-video grounding (csrc/video.hip) --------------------------------------------------------------------------
+def bank_write(x, bank, split):
+    """x (..., c) fp32 rows (pixel stride x.stride(-2)) -> bank / split (same number of rows, dense [rows][c], contiguous): the
+    L2-normalised rows and their f16 two-piece split form (gemm3_presplit's layout, abs-max word 1.0), one pass."""
+    c = x.shape[-1]
+    rows = x.numel() // c
+    _rows(x, "bank_write x"); _chk(bank, "bank_write bank"); _chk(split, "bank_write split")
+    if bank.shape[-1] != c or split.shape[-1] != c or bank.numel() != rows * c or split.numel() != rows * c:
+        raise ValueError(f"bank_write: bank / split must hold the {rows} rows of x ({tuple(bank.shape)}, {tuple(split.shape)})")
+    lib().bank_write(x.data_ptr(), x.stride(-2), bank.data_ptr(), split.data_ptr(), rows, c, _s())
+    return bank, split
+
+
+COATTN_BANK_WS_BYTES = 2 << 30       # budget of the affinity workspace E of one coattn_bank_fwd launch sequence (it sub-batches)
+
+
+def coattn_bank_fwd(bank, split, a0, d, n, out1, out2, temperature):
+    """bank / split (F, hw, c) contiguous fp32 (bank_write).  The n pairs (a, a + d), a = a0 ... a0 + n - 1: out1[i] (n, hw, c view,
+    last dim contiguous) = what frame a takes from frame a + d, out2[i] = what frame a + d takes from frame a; either may be None.
+    One affinity per pair; sub-batched so that E stays within COATTN_BANK_WS_BYTES (at least one pair per launch)."""
+    _chk(bank, "coattn_bank bank"); _chk(split, "coattn_bank split")
+    F_, hw, c = bank.shape
+    if tuple(split.shape) != (F_, hw, c) or n <= 0 or a0 < 0 or d < 0 or a0 + d + n > F_:
+        raise ValueError(f"coattn_bank_fwd: pairs ({a0} .. {a0 + n - 1}) + {d} outside a bank of {F_} frames")
+    if out1 is None and out2 is None:
+        raise ValueError("coattn_bank_fwd: no output wanted")
+    for o in (out1, out2):
+        if o is not None and not (o.is_cuda and o.dtype == torch.float32 and tuple(o.shape) == (n, hw, c) and o.stride(2) == 1):
+            raise ValueError("coattn_bank_fwd: outputs must be fp32 CUDA (n, hw, c) views with a contiguous last dimension")
+    if out1 is not None and out2 is not None and out1.stride() != out2.stride():
+        raise ValueError("coattn_bank_fwd: out1 and out2 must share their strides")
+    ref = out1 if out1 is not None else out2
+    L = lib()
+    per = max(1, int(COATTN_BANK_WS_BYTES // (4 * max(1, L.coattn_e_size(1, hw)))))
+    bs = hw * c                                   # (Python integers: offsets into the banks and E are 64-bit)
+    for i0 in range(0, n, per):
+        m = min(per, n - i0)
+        E = scratch(L.coattn_e_size(m, hw) + 2 * m * hw, bank.device, slot=6)
+        rinv = E[L.coattn_e_size(m, hw):]
+        ws = scratch(L.coattn_fwd_ws(m, hw, c), bank.device, slot=0)
+        o1 = 0 if out1 is None else out1.data_ptr() + 4 * i0 * out1.stride(0)
+        o2 = 0 if out2 is None else out2.data_ptr() + 4 * i0 * out2.stride(0)
+        ia, ib = 4 * bs * (a0 + i0), 4 * bs * (a0 + d + i0)
+        L.coattn_bank_fwd(bank.data_ptr() + ia, bank.data_ptr() + ib, split.data_ptr() + ia, split.data_ptr() + ib, bs,
+                          o1, o2, ref.stride(1), ref.stride(0), E.data_ptr(), rinv.data_ptr(), rinv.data_ptr() + 4 * m * hw,
+                          ws.data_ptr(), m, hw, c, float(temperature), _s())
+
+
+def post_fusion_bank(feats, scores, n_frame):
+    """csrc/video.hip: feats (n,k,E), scores (n,k) fp32 contiguous — the candidates of n consecutive centres; window b = centres
+    b - n_frame//2 ... b - n_frame//2 + n_frame - 1, entries outside the run missing.  Returns (best (n,) int64, fused (n,k))."""
+    _chk(feats, "post_fusion_bank feats"); _chk(scores, "post_fusion_bank scores")
+    n, k, E = feats.shape
+    if tuple(scores.shape) != (n, k):
+        raise ValueError("post_fusion_bank: shapes must be feats (n,k,E), scores (n,k)")
+    fused = torch.empty((n, k), dtype=torch.float32, device=feats.device); best = torch.empty(n, dtype=torch.int64, device=feats.device)
+    lib().post_fusion_bank(feats.data_ptr(), scores.data_ptr(), n, k, int(n_frame), E, fused.data_ptr(), best.data_ptr(), _s())
+    return best, fused
+
+
 def box_iou(b1, b2):
     _chk(b1, "box_iou"); _chk(b2, "box_iou")
     iou = torch.empty(b1.shape[0], dtype=torch.float32, device=b1.device)

@@ -1,0 +1,544 @@
+"""Whole-video grounding: frames in, one box per frame out — every frame through the backbone ONCE.
+
+The reference grounds a video one window at a time (test_DCNet.py re-runs the n_frame model per window; ``getChunk``,
+dataset/vid_loader.py:143-180, builds the windows), so a frame is encoded once per window it appears in and the affinity of two
+frames is computed once in each of their windows.  Here:
+
+  * every frame goes through Darknet-53, ``mapping_visu`` and the normalisation once, into a per-scale FEATURE BANK (fp32 rows and
+    their f16 two-piece split form, ``dcn_bank_write``);
+  * the co-attention of two frames is computed once: one affinity yields what each of the two takes from the other
+    (``dcn_coattn_bank_fwd`` reads bank rows through strides: the pairs of distance d are bank[a0:a0+n] against bank[a0+d:a0+d+n]);
+  * the language branch runs once per query; nothing before ``sim_score`` and the fusion head depends on the sentence, so any
+    number of queries share the visual work;
+  * the temporal re-scoring reads the candidates of the centres in place (``dcn_post_fusion_bank``).
+
+The window rule is the reference's (``getChunk``):
+
+    window of centre i  =  frames i - K//2 ... i + ceil(K/2) - 1,   centre slot K//2
+
+    vg = VideoGrounder(model, n_frame=5, border="valid", chunk=32, topk=None)
+    res = vg.run(image, word_id, meta=None)            # image (F,3,S,S) CUDA, word_id (Q,L) or (L,)
+    # or incrementally, for streams and long videos:
+    vg.reset(word_id); out = vg.push(image_chunk); ...; out = vg.flush()
+
+``python -m dcnet_amd.video --synthetic --frames 64 --n-frame 5`` runs it on synthetic frames and prints frames/s.
+"""
+from __future__ import annotations
+
+import math
+import os
+from dataclasses import dataclass, field
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+BORDERS = ("valid", "replicate")
+
+
+# ---- host logic (pure Python) -------------------------------------------------------------------------------------------------
+def _check_window(n_frame) -> int:
+    if not isinstance(n_frame, int) or isinstance(n_frame, bool) or n_frame < 2:
+        raise ValueError(f"n_frame = {n_frame!r}: a window needs at least 2 frames (an int >= 2)")
+    return n_frame
+
+
+def _check_border(border) -> str:
+    if border not in BORDERS:
+        raise ValueError(f"border = {border!r}: expected one of {BORDERS}")
+    return border
+
+
+def window_offsets(n_frame: int) -> List[int]:
+    """Frame offsets of a window relative to its centre, in window order (the centre, offset 0, sits in slot n_frame // 2)."""
+    K = _check_window(n_frame)
+    return list(range(-(K // 2), (K + 1) // 2))
+
+
+def centres(frames: int, n_frame: int, border: str = "valid") -> List[int]:
+    """The frames that get an answer.  "valid": every centre whose window lies inside the video; "replicate": every frame, window
+    indices clamped to [0, frames - 1] (the ``numpy.clip`` that ``getChunk`` carries)."""
+    K = _check_window(n_frame)
+    if _check_border(border) == "replicate":
+        return list(range(frames))
+    return list(range(K // 2, frames - (K + 1) // 2 + 1))
+
+
+def reference_centres(frames: int, n_frame: int) -> List[int]:
+    """The centres ``getChunk`` produces: the "valid" ones without the last (it drops a centre i with i + ceil(K/2) > frames - 1,
+    although that window still fits) — for people who reproduce the reference's numbers."""
+    K = _check_window(n_frame)
+    return list(range(K // 2, frames - (K + 1) // 2))
+
+
+def window_frames(centre: int, frames: int, n_frame: int, border: str = "valid") -> List[int]:
+    """Frame indices of the window of ``centre``, in window order (clamped under "replicate")."""
+    w = [centre + o for o in window_offsets(n_frame)]
+    if _check_border(border) == "replicate":
+        return [min(max(j, 0), frames - 1) for j in w]
+    if w[0] < 0 or w[-1] > frames - 1:
+        raise ValueError(f"frame {centre} is no \"valid\" centre of a video of {frames} frames with n_frame = {n_frame}")
+    return w
+
+
+def _multiplicity(i: int, j: int, K: int, border: str, total: Optional[int]) -> int:
+    """How many slots of centre i's window (the centre slot excluded) hold frame j; 0 if i is no centre.  ``total`` None: the
+    length of the video is not known yet (nothing clamps from above, no centre is excluded from above)."""
+    lo, hi = -(K // 2), (K + 1) // 2 - 1
+    if border == "valid":
+        if i < K // 2 or (total is not None and i > total - (K + 1) // 2):
+            return 0
+        return int(j != i and lo <= j - i <= hi)
+    top = math.inf if total is None else total - 1
+    return sum(1 for o in range(lo, hi + 1) if o != 0 and min(max(i + o, 0), top) == j)
+
+
+@dataclass
+class PairPlan:
+    """Batched co-attention work.  ``runs``: (d, a0, n, fwd, bwd) — the n frame pairs (a, a + d), a = a0 ... a0 + n - 1, of
+    distance d > 0; fwd: centre a takes from frame a + d (+d is a window offset), bwd: centre a + d takes from frame a (-d is one).
+    ``border``: (a, b, w_ab, w_ba), a <= b — single pairs whose results count w_ab times for centre a and w_ba times for centre b
+    (clamped windows; a == b is a self pair, w_ba = 0).  Every attended feature enters its centre's mean with weight
+    multiplicity / (n_frame - 1)."""
+    runs: List[Tuple[int, int, int, bool, bool]] = field(default_factory=list)
+    border: List[Tuple[int, int, int, int]] = field(default_factory=list)
+
+    def contributions(self) -> List[Tuple[int, int, int]]:
+        """(centre, neighbour frame, multiplicity) of everything the plan computes."""
+        out = []
+        for d, a0, n, fwd, bwd in self.runs:
+            for a in range(a0, a0 + n):
+                if fwd:
+                    out.append((a, a + d, 1))
+                if bwd:
+                    out.append((a + d, a, 1))
+        for a, b, w_ab, w_ba in self.border:
+            if w_ab:
+                out.append((a, b, w_ab))
+            if w_ba:
+                out.append((b, a, w_ba))
+        return out
+
+    def affinities(self) -> List[Tuple[int, int]]:
+        """The frame pairs (a, b), a <= b, whose affinity matrix the plan computes (one entry per computation)."""
+        return [(a, a + d) for d, a0, n, _, _ in self.runs for a in range(a0, a0 + n)] + [(a, b) for a, b, _, _ in self.border]
+
+
+def pair_plan(first: int, last: int, n_frame: int, border: str = "valid", total: Optional[int] = None) -> PairPlan:
+    """The work that becomes possible when frames ``first`` ... ``last - 1`` have been encoded (all earlier frames are in the bank):
+    every pair whose LATER frame is one of them, so that no affinity is computed twice however the video is cut into chunks.
+    ``total``: frames of the whole video if known (``run``); None while streaming — then, under "valid", centres near the end get
+    contributions before it is known whether their window fits (dropped at ``flush`` if not), and under "replicate" the clamp at
+    the last frame is made up for by ``flush_plan``."""
+    K = _check_window(n_frame); _check_border(border)
+    plan = PairPlan()
+    for d in range(1, K // 2 + 1):
+        run = None                                     # [a0, n, fwd, bwd]
+        for b in range(max(first, d), last):
+            a = b - d
+            w_ab, w_ba = _multiplicity(a, b, K, border, total), _multiplicity(b, a, K, border, total)
+            if w_ab > 1 or w_ba > 1:
+                plan.border.append((a, b, w_ab, w_ba))
+                flags = None
+            else:
+                flags = (bool(w_ab), bool(w_ba)) if (w_ab or w_ba) else None
+            if run is not None and (flags is None or flags != (run[2], run[3])):
+                plan.runs.append((d, run[0], run[1], run[2], run[3])); run = None
+            if flags is not None:
+                if run is None:
+                    run = [a, 0, flags[0], flags[1]]
+                run[1] += 1
+        if run is not None:
+            plan.runs.append((d, run[0], run[1], run[2], run[3]))
+    for b in range(first, last):
+        w = _multiplicity(b, b, K, border, total)
+        if w:
+            plan.border.append((b, b, w, 0))
+    return plan
+
+
+def flush_plan(frames: int, n_frame: int, border: str = "valid") -> PairPlan:
+    """What a stream of unknown length still owes once it ends after ``frames`` frames: under "replicate", the window slots of the
+    last centres that clamp to the last frame (these few affinities are computed a second time: a stream does not know its last
+    frame when it sees it).  Empty under "valid"."""
+    K = _check_window(n_frame); _check_border(border)
+    plan = PairPlan()
+    if border == "replicate" and frames > 0:
+        j = frames - 1
+        for i in range(max(0, frames - (K + 1) // 2), frames):
+            extra = _multiplicity(i, j, K, border, frames) - _multiplicity(i, j, K, border, None)
+            if extra:
+                plan.border.append((i, j, extra, 0))
+    return plan
+
+
+# ---- results ------------------------------------------------------------------------------------------------------------------
+@dataclass
+class VideoResult:
+    """Device tensors; n = number of centres, Q = number of queries.  ``outbox[q][s]``, ``sim[q][s]``, ``loc[q][s]``,
+    ``only_obj[q][s]``: the n_frame model's outputs of query q on scale s with the centres as the batch dimension; ``corr_feat[s]``
+    (n,E,g,g) is shared by the queries.  ``boxes`` (Q,n,4): ``losses.decode_boxes`` (letterbox pixels), or source pixels when the
+    letterbox meta was given.  With ``topk``: ``cand_boxes`` (Q,n,k,4), ``cand_scores`` (Q,n,k), ``cand_feats`` (Q,n,k,E) and the
+    temporally fused choice ``best`` (Q,n), ``fused`` (Q,n,k), ``fused_boxes`` (Q,n,4)."""
+    centres: torch.Tensor
+    outbox: List[List[torch.Tensor]]
+    sim: List[List[torch.Tensor]]
+    loc: List[List[torch.Tensor]]
+    corr_feat: List[torch.Tensor]
+    only_obj: List[List[torch.Tensor]]
+    boxes: torch.Tensor
+    cand_boxes: Optional[torch.Tensor] = None
+    cand_scores: Optional[torch.Tensor] = None
+    cand_feats: Optional[torch.Tensor] = None
+    best: Optional[torch.Tensor] = None
+    fused: Optional[torch.Tensor] = None
+    fused_boxes: Optional[torch.Tensor] = None
+
+    def query(self, q: int = 0):
+        """The n_frame model's return tuple (outbox, sim, loc, corr_feat, only_obj) of query q."""
+        return self.outbox[q], self.sim[q], self.loc[q], self.corr_feat, self.only_obj[q]
+
+    @staticmethod
+    def cat(parts: Sequence["VideoResult"]) -> "VideoResult":
+        parts = [p for p in parts if p is not None]
+        if not parts:
+            raise ValueError("VideoResult.cat: no centres (the video is shorter than a window?)")
+        if len(parts) == 1:
+            return parts[0]
+        Q = len(parts[0].outbox)
+        per_q = lambda name: [[torch.cat([getattr(p, name)[q][s] for p in parts]) for s in range(3)] for q in range(Q)]
+        opt = lambda name: None if getattr(parts[0], name) is None else torch.cat([getattr(p, name) for p in parts], dim=1)
+        return VideoResult(centres=torch.cat([p.centres for p in parts]), outbox=per_q("outbox"), sim=per_q("sim"), loc=per_q("loc"),
+                           corr_feat=[torch.cat([p.corr_feat[s] for p in parts]) for s in range(3)], only_obj=per_q("only_obj"),
+                           boxes=torch.cat([p.boxes for p in parts], dim=1), cand_boxes=opt("cand_boxes"),
+                           cand_scores=opt("cand_scores"), cand_feats=opt("cand_feats"))
+
+
+class VideoGrounder:
+    """Grounds every frame of a video against one or more sentences (module docstring).
+
+    model    a ``dcnet_amd.model.grounding_model`` (``model.DCNet_model`` and ``model.test_DCNet_model`` hand out the same class)
+             in eval mode.  Precision: the default "fp32" mode only — the feature bank holds fp32 rows and their f16 two-piece
+             split; any other mode of ``ops.set_precision`` raises a RuntimeError that names it.
+    n_frame  K, frames per window (>= 2); border "valid" | "replicate" (``centres``)
+    chunk    frames encoded per step: bounds the memory of the bank rows, concat buffers and the affinity workspace (the
+             co-attention sub-batches by ``ops.COATTN_BANK_WS_BYTES`` on its own)
+    topk     k: also the k best candidates of every centre and their temporal fusion over windows of n_frame centres
+             (n_frame <= 32, k <= 64)
+
+    ``push`` keeps the bank rows of the last n_frame // 2 frames (no pair reaches further back; per scale, fp32 and split) and the
+    unfinished means of the last ceil(n_frame / 2) - 1 centres between calls, so chunked and streamed runs encode every frame once
+    too.  Nothing here synchronises the host with the device."""
+
+    def __init__(self, model, n_frame: int = 5, border: str = "valid", chunk: int = 32, topk: Optional[int] = None):
+        from .model import grounding_model
+        self.n_frame, self.border = _check_window(n_frame), _check_border(border)
+        if not isinstance(model, grounding_model):
+            raise TypeError(f"model: expected a dcnet_amd.model.grounding_model, got {type(model).__name__}")
+        if model.training:
+            raise ValueError("model is in train mode: VideoGrounder is the inference path, call model.eval() first")
+        if not isinstance(chunk, int) or chunk < 1:
+            raise ValueError(f"chunk = {chunk!r}: frames per step, an int >= 1")
+        if topk is not None and (not isinstance(topk, int) or not 1 <= topk <= 64 or n_frame > 32):
+            raise ValueError(f"topk = {topk!r} with n_frame = {n_frame}: the temporal fusion takes topk in 1 ... 64 and n_frame <= 32")
+        self.model, self.chunk, self.topk = model, chunk, topk
+        self._lang = None
+
+    # ---- state ----------------------------------------------------------------------------------------------------------------
+    def reset(self, word_id: torch.Tensor, total: Optional[int] = None) -> None:
+        """Start a video: run the language branch, once, for the (Q,L) or (L,) token ids.  ``total``: frames of the whole video if
+        known in advance."""
+        from . import ops
+        m = self.model
+        if m.training:
+            raise ValueError("model is in train mode: VideoGrounder is the inference path, call model.eval() first")
+        if not (isinstance(word_id, torch.Tensor) and word_id.is_cuda):
+            raise ValueError("word_id: expected a CUDA tensor of token ids (Q,L) or (L,) (HIP kernels only, no CPU path)")
+        if ops.get_precision() != "fp32":
+            raise RuntimeError(f"VideoGrounder runs in the \"fp32\" precision mode only (feature banks are fp32 + f16 split); the "
+                               f"current mode is {ops.get_precision()!r}")
+        if word_id.dim() == 1:
+            word_id = word_id.unsqueeze(0)
+        dev = word_id.device
+        main = torch.cuda.current_stream()
+        with torch.no_grad():
+            if ops.use_amax():
+                ops.amax_begin_step(dev)
+            side = m._side_stream(dev) if m.language_stream else main
+            side.wait_stream(main)
+            with torch.cuda.stream(side):
+                wid, flang, context, embedded = m._language(word_id)
+                flang_attn, flang_loc = m._phrases(context, embedded, wid)
+        self._lang = {"side": side, "joined": side is main, "flang": flang, "attn": flang_attn, "loc": flang_loc, "Q": word_id.shape[0]}
+        K = self.n_frame
+        self._total, self._seen = total, 0
+        self._bank = None                                         # per scale (bank, split) of frames [_seen - keep, _seen)
+        self._acc = None                                          # per scale: unfinished means of centres [_acc_lo, ...)
+        self._acc_lo = K // 2 if self.border == "valid" else 0    # first centre not handed out yet
+        self._meta = []                                           # device (ratio, dw, dh, frame_hw) of frames [_meta_lo, ...)
+        self._meta_lo, self._meta_all = 0, False                  # _meta_all: run() uploaded the whole video's meta up front
+
+    def _join_language(self):
+        st = self._lang
+        if not st["joined"]:
+            main = torch.cuda.current_stream()
+            main.wait_stream(st["side"])
+            for t_ in (st["flang"], st["attn"], st["loc"]):
+                t_.record_stream(main)
+            st["joined"] = True
+
+    # ---- one step -------------------------------------------------------------------------------------------------------------
+    def _contribute(self, s, bank, split, base, acc, h, w, plan: PairPlan):
+        from . import ops
+        m, K = self.model, self.n_frame
+        hw, e = bank.shape[1], bank.shape[2]
+        lo = self._acc_lo
+
+        def one(a, d, n, fwd, bwd, w_f, w_b):
+            cat = torch.empty(((int(fwd) + int(bwd)) * n, hw, 2 * e), dtype=torch.float32, device=bank.device)
+            cf = cat[:n] if fwd else None
+            cb = cat[n if fwd else 0:] if bwd else None
+            if fwd:
+                cf[..., :e].copy_(bank[a - base:a - base + n])
+            if bwd:
+                cb[..., :e].copy_(bank[a + d - base:a + d - base + n])
+            ops.coattn_bank_fwd(bank, split, a - base, d, n, None if cf is None else cf[..., e:], None if cb is None else cb[..., e:],
+                                m.temperature)
+            if fwd:
+                m._corr_accumulate(s, cf.view(n, h, w, 2 * e), acc[a - lo:a - lo + n].view(n, h, w, e), w_f / (K - 1))
+            if bwd:
+                m._corr_accumulate(s, cb.view(n, h, w, 2 * e), acc[a + d - lo:a + d - lo + n].view(n, h, w, e), w_b / (K - 1))
+
+        for d, a0, n, fwd, bwd in plan.runs:
+            one(a0, d, n, fwd, bwd, 1.0, 1.0)
+        for a, b, w_ab, w_ba in plan.border:
+            one(a, b - a, 1, bool(w_ab), bool(w_ba), float(w_ab), float(w_ba))
+
+    def _emit(self, hi: int, size: int) -> Optional[VideoResult]:
+        """Heads of the finished centres [_acc_lo, hi) for every query."""
+        from . import losses, postprocess
+        m, lo = self.model, self._acc_lo
+        nc = hi - lo
+        if nc <= 0:
+            return None
+        self._join_language()
+        st = self._lang
+        corr = []
+        for s in range(3):
+            gh, gw = self._grid_hw[s]
+            done = self._acc[s][:nc]
+            self._acc[s] = self._acc[s][nc:].clone()
+            corr.append(done.view(nc, gh, gw, done.shape[-1]))
+        corr_nchw = [c.permute(0, 3, 1, 2) for c in corr]
+        dev = corr[0].device
+        outs, sims, locs, onlys, boxes, cands = [], [], [], [], [], []
+        meta = None
+        if self._meta:
+            i0 = lo - self._meta_lo
+            meta = [torch.cat([mm[k] for mm in self._meta])[i0:i0 + nc] for k in range(4)]
+        elif self.topk is not None:
+            meta = [torch.ones(nc, device=dev), torch.zeros(nc, device=dev), torch.zeros(nc, device=dev),
+                    torch.full((nc, 2), size, dtype=torch.int64, device=dev)]
+        for q in range(st["Q"]):
+            ex = lambda t: t[q:q + 1].expand(nc, *t.shape[1:]).contiguous()
+            flang, fattn, floc = ex(st["flang"]), ex(st["attn"]), ex(st["loc"])
+            res = [m._score_scale(s, corr[s], flang, fattn) for s in range(3)]
+            sim = [r[0] for r in res]
+            outbox, loc, only_obj = m._head(sim, [r[1] for r in res], floc)
+            outs.append(list(outbox)); sims.append(sim); locs.append(list(loc)); onlys.append(list(only_obj))
+            if self._meta:
+                b1 = postprocess.topk_candidates(outbox, corr_nchw, size, 1, *meta)[0][:, 0]
+            else:
+                b1 = losses.decode_boxes(outbox, size)
+            boxes.append(b1)
+            if self.topk is not None:
+                cands.append(postprocess.topk_candidates(outbox, corr_nchw, size, self.topk, *meta)[:3])
+        res = VideoResult(centres=torch.arange(lo, hi, device=dev), outbox=outs, sim=sims, loc=locs, corr_feat=corr_nchw, only_obj=onlys,
+                          boxes=torch.stack(boxes))
+        if cands:
+            res.cand_boxes, res.cand_scores, res.cand_feats = (torch.stack([c[k] for c in cands]) for k in range(3))
+        self._acc_lo = hi
+        return res
+
+    def _upload_meta(self, meta, n: int, size: int, dev):
+        from .postprocess import letterbox_frame
+        ratio, dw, dh = ([float(v) for v in x] for x in meta)
+        if not (len(ratio) == len(dw) == len(dh) == n):
+            raise ValueError(f"meta: (ratio, dw, dh) must have one entry per frame ({n})")
+        hw = [letterbox_frame(size, r, a, b) for r, a, b in zip(ratio, dw, dh)]
+        up = lambda v, dt: torch.tensor(v, dtype=dt).pin_memory().to(dev, non_blocking=True)      # (page-locked: a true async copy)
+        self._meta.append((up(ratio, torch.float32), up(dw, torch.float32), up(dh, torch.float32), up(hw, torch.int64).reshape(n, 2)))
+
+    @torch.no_grad()
+    def push(self, image: torch.Tensor, meta=None) -> Optional[VideoResult]:
+        """The next frames of the video, (n,3,S,S) CUDA fp32 (any n >= 1; more than ``chunk`` frames are taken in steps).  ``meta``:
+        (ratio, dw, dh) per frame of this call (what ``prep.Prepared`` carries), for boxes in source pixels — for every call of a
+        video or for none.  Returns the results of the centres that were completed, or None."""
+        from . import ops
+        if self._lang is None:
+            raise RuntimeError("VideoGrounder.push: call reset(word_id) first")
+        if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dim() == 4 and image.shape[0] >= 1):
+            raise ValueError("image: expected a CUDA tensor (n,3,S,S) (HIP kernels only, no CPU path)")
+        if image.shape[0] > self.chunk:
+            parts = []
+            for i0 in range(0, image.shape[0], self.chunk):
+                mm = None if meta is None else tuple(x[i0:i0 + self.chunk] for x in meta)
+                parts.append(self.push(image[i0:i0 + self.chunk], mm))
+            return VideoResult.cat(parts) if any(p is not None for p in parts) else None
+        m, K, dev = self.model, self.n_frame, image.device
+        n_new, size = image.shape[0], image.shape[-1]
+        if meta is not None:
+            if self._seen and not self._meta:
+                raise ValueError("meta: given for this call but not for the earlier frames of the video")
+            self._upload_meta(meta, n_new, size, dev)            # (before the step's kernels are queued)
+        elif self._meta and not self._meta_all:
+            raise ValueError("meta: given for the earlier frames of the video but not for this call")
+        p0, p1 = self._seen, self._seen + n_new
+        keep = 0 if self._bank is None else self._bank[0][0].shape[0]
+        base = p0 - keep
+        if ops.use_amax():
+            ops.amax_begin_step(dev)
+        raw = m.visumodel.forward_nhwc(image.float(), taps_b16=True)
+        m._head_filter_banks()
+        plan = pair_plan(p0, p1, K, self.border, self._total)
+        n_acc = max(0, p1 - self._acc_lo)
+        banks, accs = [], []
+        for s in range(3):
+            x = m._map_scale(s, raw[s])
+            _, h, w, e = x.shape
+            bank = torch.empty((keep + n_new, h * w, e), dtype=torch.float32, device=dev)
+            split = torch.empty_like(bank)
+            if keep:
+                bank[:keep].copy_(self._bank[s][0]); split[:keep].copy_(self._bank[s][1])
+            ops.bank_write(x, bank[keep:], split[keep:])
+            acc = torch.zeros((n_acc, h * w, e), dtype=torch.float32, device=dev)
+            if self._acc is not None and self._acc[s].shape[0]:
+                acc[:self._acc[s].shape[0]].copy_(self._acc[s])
+            self._contribute(s, bank, split, base, acc, h, w, plan)
+            banks.append((bank, split)); accs.append(acc)
+        self._acc = accs
+        k2 = min(K // 2, keep + n_new)
+        self._bank = [(b[b.shape[0] - k2:].clone(), sp[sp.shape[0] - k2:].clone()) if k2 < b.shape[0] else (b, sp) for b, sp in banks]
+        self._seen, self._size = p1, size
+        self._grid_hw = [(int(round(math.sqrt(b.shape[1]))),) * 2 for b, _ in banks]
+        return self._emit(p1 - (K + 1) // 2 + 1, size)
+
+    @torch.no_grad()
+    def flush(self) -> Optional[VideoResult]:
+        """End of the video: the centres that were waiting for it (border "replicate"); under "valid" the unfinished ones are
+        dropped.  Returns their results, or None; the grounder needs a ``reset`` before the next video."""
+        if self._lang is None:
+            raise RuntimeError("VideoGrounder.flush: call reset(word_id) first")
+        out = None
+        if self.border == "replicate" and self._seen > self._acc_lo:
+            if self._total is None:
+                plan = flush_plan(self._seen, self.n_frame, self.border)
+                base = self._seen - self._bank[0][0].shape[0]
+                for s in range(3):
+                    h, w = self._grid_hw[s]
+                    self._contribute(s, self._bank[s][0], self._bank[s][1], base, self._acc[s], h, w, plan)
+            out = self._emit(self._seen, self._size)
+        self._lang = None
+        self._bank = self._acc = None
+        return out
+
+    def fuse(self, res: VideoResult) -> VideoResult:
+        """Temporal fusion over the candidates of ALL centres of a video (``topk`` set): window b = the candidates of centres
+        b - K//2 ... b - K//2 + K - 1, centres outside the run missing.  Fills best / fused / fused_boxes."""
+        from . import ops
+        if res.cand_feats is None:
+            raise ValueError("fuse: the grounder was built without topk")
+        best, fused = zip(*[ops.post_fusion_bank(res.cand_feats[q].contiguous(), res.cand_scores[q].contiguous(), self.n_frame)
+                            for q in range(res.cand_feats.shape[0])])
+        res.best, res.fused = torch.stack(best), torch.stack(fused)
+        res.fused_boxes = torch.gather(res.cand_boxes, 2, res.best[:, :, None, None].expand(-1, -1, 1, 4))[:, :, 0]
+        return res
+
+    @torch.no_grad()
+    def run(self, image: torch.Tensor, word_id: torch.Tensor, meta=None) -> VideoResult:
+        """A whole video at once: image (F,3,S,S) CUDA, word_id (Q,L) or (L,), meta = (ratio, dw, dh) per frame or None."""
+        if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dim() == 4):
+            raise ValueError("image: expected a CUDA tensor (F,3,S,S) (HIP kernels only, no CPU path)")
+        F_ = image.shape[0]
+        if not centres(F_, self.n_frame, self.border):
+            raise ValueError(f"image: {F_} frames hold no centre of a window of n_frame = {self.n_frame} (border {self.border!r})")
+        self.reset(word_id, total=F_)
+        if meta is not None:
+            self._upload_meta(meta, F_, image.shape[-1], image.device)      # (once, before any of the video's kernels is queued)
+            self._meta_all = True
+        parts = []
+        for i0 in range(0, F_, self.chunk):
+            parts.append(self.push(image[i0:i0 + self.chunk]))
+        parts.append(self.flush())
+        res = VideoResult.cat(parts)
+        return self.fuse(res) if self.topk is not None else res
+
+
+# ---- command line -------------------------------------------------------------------------------------------------------------
+def synthetic_model(size: int, device):
+    """The product model with the deterministic synthetic weights the tests and bench.py use (needs the repository's
+    tests/golden/state_dict_keys_256.json and bn_calib.npz)."""
+    import json
+    from .model import grounding_model
+    from .utils.synth import apply_bn_calibration, synth_state_dict
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    gold = os.path.join(root, "tests", "golden")
+    with open(os.path.join(gold, "state_dict_keys_256.json")) as f:
+        shapes = {k: tuple(v) for k, v in json.load(f).items()}
+    shapes["loc_text_embedding.0.weight"] = (512, sum((size // 32 * 2 ** i) ** 2 for i in range(3)))
+    sd = apply_bn_calibration(synth_state_dict(shapes, 0), os.path.join(gold, "bn_calib.npz"))
+    m = grounding_model(corpus=list(range(1000)), light=False, emb_size=512, coordmap=True, dataset="vid", img_size=size,
+                        config_path=os.path.join(root, "model", "yolov3.cfg"), weights_path=None)
+    m.load_state_dict(sd, strict=True)
+    return m.to(device).eval()
+
+
+def main(argv=None):
+    import argparse
+    import time
+    import numpy as np
+    ap = argparse.ArgumentParser(description="whole-video grounding on synthetic frames")
+    ap.add_argument("--synthetic", action="store_true", help="synthetic weights and frames (the only source this tool has)")
+    ap.add_argument("--frames", type=int, default=64)
+    ap.add_argument("--n-frame", type=int, default=5)
+    ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--border", default="valid", choices=BORDERS)
+    ap.add_argument("--chunk", type=int, default=32)
+    ap.add_argument("--queries", type=int, default=1)
+    ap.add_argument("--topk", type=int, default=None)
+    ap.add_argument("--raw-frames", action="store_true", help="375x500 uint8 frames through prep.prepare_clips(augment=False); prints source-pixel boxes")
+    ap.add_argument("--repeat", type=int, default=3)
+    a = ap.parse_args(argv)
+    if not a.synthetic:
+        ap.error("only --synthetic input is built in; use VideoGrounder from Python for real videos")
+    from .utils.synth import synth_inputs
+    dev = torch.device("cuda:0")
+    m = synthetic_model(a.size, dev)
+    image, word_id, _ = synth_inputs(a.frames, a.size, n_queries=a.queries, seed=1)
+    meta = None
+    if a.raw_frames:
+        from . import prep
+        rs = np.random.RandomState(7)
+        frames = [[rs.randint(0, 256, size=(375, 500, 3)).astype(np.uint8) for _ in range(a.frames)]]
+        p = prep.prepare_clips(frames, [np.tile(np.array([[10, 10, 100, 100]]), (a.frames, 1))], [["a phrase"] * a.frames], a.size, False)
+        image, meta = p.image, (p.ratio, p.dw, p.dh)
+    image, word_id = image.to(dev), word_id.to(dev)
+    vg = VideoGrounder(m, n_frame=a.n_frame, border=a.border, chunk=a.chunk, topk=a.topk)
+    times = []
+    for _ in range(a.repeat + 1):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = vg.run(image, word_id, meta)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    t = float(np.median(times[1:])) if len(times) > 1 else times[0]
+    print(f"{a.frames} frames {a.size}x{a.size}, n_frame {a.n_frame}, border {a.border}, {a.queries} quer{'y' if a.queries == 1 else 'ies'}: "
+          f"{res.centres.numel()} centres in {t * 1e3:.1f} ms = {a.frames / t:.1f} frames/s, peak memory "
+          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB")
+    if a.raw_frames:
+        b = (res.fused_boxes if a.topk is not None else res.boxes)[0].cpu()
+        for i, c in enumerate(res.centres.cpu().tolist()):
+            print(f"frame {c}: box (source pixels) " + " ".join(f"{v:.1f}" for v in b[i].tolist()))
+
+
+if __name__ == "__main__":
+    main()

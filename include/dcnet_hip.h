@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 310
+#define DCN_ABI_VERSION 311
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -552,6 +552,29 @@ int dcn_post_topk(const float* const* outbox, const float* const* feat, const in
  * :266-269).  fused [n][k] = sum_r softmax_r(max_i <c, ref_r,i>) * ref_score[r][argmax_i], best [n] = first arg-max of fused. */
 int dcn_post_fusion(const float* center, const float* ref, const float* ref_score, const unsigned char* valid, int n, int k, int r,
                     int e, float* fused, int64_t* best, void* stream);
+
+/* ---- whole-video grounding: feature banks, co-attention on bank rows, windowed temporal fusion (ABI 311) ------------- */
+/* F.normalize(x, dim=channel) of the mapped features of a run of frames (model/test_DCNet_model.py:299-301) into their rows of a
+ * frame-major feature bank, in both forms the co-attention reads: bank [rows][c] fp32 (bitwise dcn_l2norm_score_fwd's output) and
+ * split [rows][c] = dcn_gemm3_presplit's layout of the same values with the abs-max word of the constant 1.0 (unit-norm rows).
+ * x [rows][c], row stride ldx (<= 0: c); c a multiple of 8, <= 1024; one pass. */
+int dcn_bank_write(const float* x, int ldx, float* bank, float* split, int64_t rows, int c, void* stream);
+/* Co-attention (model/test_DCNet_model.py:259-274) of b pairs of bank rows: f1 / f2 [b][hw][c] fp32 (dense rows, batch stride bsf
+ * floats, <= 0: hw*c) and f1s / f2s the same rows of the split bank.  With frames laid out frame-major the pairs of distance d are
+ * f1 = bank + a0*bsf, f2 = bank + (a0 + d)*bsf.  One affinity E = exp(t <f1_i, f2_j> - t), then f1_attn (what a centre frame f1
+ * takes from f2) and / or f2_attn (what a centre frame f2 takes from f1) — either may be NULL — written with pixel stride ldo and
+ * batch stride bso.  E: dcn_coattn_e_size(b, hw) floats, rinv / cinv [b][hw], ws: dcn_coattn_fwd_ws(b, hw, c) floats; nothing is
+ * kept for a backward.  Shapes whose products do not run on gemm3.hip (dcn_coattn_fwd's rule) go through dcn_coattn_fwd on the fp32
+ * rows.  Replaces one dcn_coattn_fwd per window and neighbour (test_DCNet.py re-runs the model per window). */
+int dcn_coattn_bank_fwd(const float* f1, const float* f2, const float* f1s, const float* f2s, int64_t bsf, float* f1_attn,
+                        float* f2_attn, int ldo, int64_t bso, float* E, float* rinv, float* cinv, float* ws, int b, int hw, int c,
+                        float temperature, void* stream);
+/* post_processing.py:246-278 on the candidate bank of n consecutive centres: feats [n][k][e], scores [n][k].  Window b consists of
+ * the entries of centres b - r/2 ... b - r/2 + r - 1; an entry outside [0, n) is missing (post_processing.py:189-193: the centre's
+ * own entry stands in, its weight is zeroed after the softmax, :266-269).  fused [n][k], best [n]: bitwise dcn_post_fusion's on the
+ * gathered tensors.  k <= 64, r <= 32. */
+int dcn_post_fusion_bank(const float* feats, const float* scores, int n, int k, int r, int e, float* fused, int64_t* best,
+                         void* stream);
 
 /* ---- clip preprocessing: letterbox, flip, HSV and affine warp of decoded frames (ABI 309) ---------------------------- */
 /* One record per frame of the batch (host-built by dcnet_amd/prep.py; dataset/vid_loader.py:333-395 draws the parameters,
