@@ -24,7 +24,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import convblock, ops
 
 # ----------------------------------------------------------------------------------------------------
 # cfg handling
@@ -268,8 +268,42 @@ def build_plan(module_defs: List[dict], in_channels: int = 3):
 # execution
 # ----------------------------------------------------------------------------------------------------
 
+def _inputs(op):
+    return (op.src, op.res) if isinstance(op, _ConvOp) else (op.up_src, op.lat_src) if isinstance(op, _UpCatOp) else (op.src,)
+
+
 def _cpad(c: int) -> int:
     return 4 if c <= 4 else ops.pad32(c)
+
+
+def _b16_diag_layer(diag, op, p, x, res, w, bank, act, out, amx):
+    """Experiments (ops.B16_DIAG, tools/precision_criterion.py --backbone): which part of the bf16-storage backbone costs the box
+    criterion, in eval mode.  "layers": predicate on the conv slot — True = this layer on bf16 tensors, False = on fp32 tensors at fp32
+    accuracy; "res32": the shortcut sums are kept in fp32 (the convolutions read a bf16 copy).
+    Returns (x, res, done): done = the layer's output is in ``out``; else the bf16 operands the ordinary path goes on with."""
+    fold = (p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5)
+    if not diag.get("layers", lambda s_: True)(op.slot):
+        ops.set_precision(diag.get("arith", "fp32"))      # ("bf16": fp32 TENSORS, operands rounded to bf16 in the loaders)
+        try:
+            ss = ops.bn_fold(*fold) if op.bn else (None, p["b"])
+            # (no abs-max words: the launch takes the bf16 three-piece split — fp32 accuracy all the same)
+            o, _ = ops.conv2d_fwd(ops.to_f32(x), w, op.k, op.stride, ss[0], ss[1], act, 0.1,
+                                  residual=None if res is None else ops.to_f32(diag.get("_r32", {}).get(op.res, res)))
+        finally:
+            ops.set_precision("bf16s")
+        if res is not None and diag.get("res32"):
+            diag.setdefault("_r32", {})[op.dst] = o
+        out[op.dst] = o; amx[op.dst] = None
+        return x, res, True
+    x = ops.to_b16(x)
+    if res is not None and diag.get("res32"):
+        o32, _ = convblock.conv_forward(x, op.k, op.stride, op.cout, bank=bank, fold=fold, act=act, slope=0.1, out_f32=True)
+        r32 = diag.setdefault("_r32", {})
+        o32 = o32 + (r32[op.res] if op.res in r32 else ops.to_f32(res))
+        r32[op.dst] = o32
+        out[op.dst] = ops.to_b16(o32); amx[op.dst] = None
+        return x, res, True
+    return x, (None if res is None else ops.to_b16(res)), False
 
 
 def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], banks=None, taps_b16: bool = False):
@@ -288,8 +322,7 @@ def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], ba
     readers: Dict[int, list] = {}
     f8_left: Dict[int, int] = {}          # fp8 storage: e4m3 readers of a tensor still to come (its attached copy is dropped after the last)
     for op in plan:
-        ins = (op.src, op.res) if isinstance(op, _ConvOp) else (op.up_src, op.lat_src) if isinstance(op, _UpCatOp) else (op.src,)
-        for s_ in ins:
+        for s_ in _inputs(op):
             if s_ is not None:
                 readers.setdefault(s_, []).append(op)
 
@@ -320,7 +353,6 @@ def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], ba
                 banks.pending = None
             if bank is not None:       # prepared for the whole network in one go (no per-layer transpose / abs-max / pre-split)
                 w, aw, wsp, w16 = bank["ohwi"], (bank["amax"] if am else None), bank["split"], bank["b16"]
-                w._dcn_wt = (bank["t"], bank["tsplit"]); w._dcn_wt16 = bank["tb16"]; w._dcn_bank = bank
             else:
                 w = ops.weight_to_ohwi(p["w"]); wsp = w16 = None
                 aw = ops.absmax(p["w"]) if (am and op.cin > 4) else None
@@ -328,104 +360,37 @@ def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], ba
             res = out[op.res] if op.res is not None else None
             act = ops.ACT_LEAKY if op.leaky else ops.ACT_NONE
             if s16 and ops.B16_DIAG is not None and not training and op.cin > 4:
-                # experiments (tools/precision_criterion.py --backbone): which part of the bf16-storage backbone costs the box criterion.
-                # "layers": predicate on the conv slot — True = this layer on bf16 tensors, False = on fp32 tensors at fp32 accuracy;
-                # "res32": the shortcut sums are kept in fp32 (the convolutions read a bf16 copy)
-                diag = ops.B16_DIAG
-                on16 = diag.get("layers", lambda s_: True)(op.slot)
-                if not on16:
-                    ops.set_precision(diag.get("arith", "fp32"))      # ("bf16": fp32 TENSORS, operands rounded to bf16 in the loaders)
-                    try:
-                        ss = ops.bn_fold(p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5) if op.bn else (None, p["b"])
-                        # (no abs-max words: the launch takes the bf16 three-piece split — fp32 accuracy all the same)
-                        o, _ = ops.conv2d_fwd(ops.to_f32(x), w, op.k, op.stride, ss[0], ss[1], act, 0.1,
-                                              residual=None if res is None else ops.to_f32(diag.get("_r32", {}).get(op.res, res)))
-                    finally:
-                        ops.set_precision("bf16s")
-                    if res is not None and diag.get("res32"):
-                        diag.setdefault("_r32", {})[op.dst] = o
-                    out[op.dst] = o; amx[op.dst] = None
+                x, res, done = _b16_diag_layer(ops.B16_DIAG, op, p, x, res, w, bank, act, out, amx)
+                if done:
                     continue
-                x = ops.to_b16(x)
-                if res is not None and diag.get("res32"):
-                    ss = ops.bn_fold(p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5)
-                    o32, _ = ops.conv2d_fwd_b16(x, bank["b16"], op.cout, op.k, op.stride, ss[0], ss[1], act, 0.1, out_f32=True)
-                    r32 = diag.setdefault("_r32", {})
-                    o32 = o32 + (r32[op.res] if op.res in r32 else ops.to_f32(res))
-                    r32[op.dst] = o32
-                    out[op.dst] = ops.to_b16(o32); amx[op.dst] = None
-                    continue
-                res = None if res is None else ops.to_b16(res)
-            if s16 and x.dtype == torch.bfloat16:
-                if bank is None:
-                    raise RuntimeError("bf16 storage needs the prepared filter banks (ops.FILTER_BANKS) for every layer behind the stem")
-                use8 = ops.f8_takes(op.cin, op.cout, op.k)          # "fp8s": this layer's forward on e4m3 operands (quantised here, once)
-                if use8:
-                    x8, xs = ops.quant_of(x)                         # (the copy scale_act wrote beside x, else a pass now)
-                    # the copy rides on the tensor, which the backward keeps (its weight gradient reads the bf16 values): drop it once
-                    # the last e4m3 reader has it (round-5 advice: ~0.3 GB of dead bytes at 64 images otherwise)
-                    f8_left[op.src] = f8_left.get(op.src, sum(1 for r_ in readers.get(op.src, []) if isinstance(r_, _ConvOp)
-                                                              and ops.f8_takes(r_.cin, r_.cout, r_.k))) - 1
-                    if f8_left[op.src] <= 0 and hasattr(x, "_dcn_q8"):
-                        del x._dcn_q8
-                    w8, ws = ops.bank_q8(bank, "q8", bank["b16"], op.cout)       # (made once per step by FilterBanks.refresh)
-                if op.bn and training:
-                    if use8:
-                        y, stats = ops.conv2d_fwd_f8(x8, xs, w8.view(-1), ws, op.cout, op.k, op.stride, want_stats=True)
-                    else:
-                        y, stats = ops.conv2d_fwd_b16(x, bank["b16"], op.cout, op.k, op.stride, want_stats=True)
-                    mi = ops.bn_finalize(stats, y.numel() // op.cout, p["gamma"], p["beta"], 1e-5, p["momentum"], p["rm"], p["rv"])
-                    # "fp8s": a reader that takes e4m3 operands gets its copy from this pass (no quantisation pass of its own)
-                    q_ = ops.storage_f8() and any(isinstance(r_, _ConvOp) and r_.src == op.dst and ops.f8_takes(r_.cin, r_.cout, r_.k)
-                                                  for r_ in readers.get(op.dst, []))
-                    o = ops.scale_act(y, mi[2], mi[3], act, 0.1, residual=res, quant=q_)
-                    if save is not None:
-                        save[op.slot] = (x, y, mi, w, None, None)
-                else:
-                    if op.bn:
-                        ss = ops.bn_fold(p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5)
-                        scale, shift = ss[0], ss[1]
-                    else:
-                        scale, shift = None, p["b"]
-                    if use8:
-                        o, _ = ops.conv2d_fwd_f8(x8, xs, w8.view(-1), ws, op.cout, op.k, op.stride, scale, shift, act, 0.1, residual=res)
-                    else:
-                        o, _ = ops.conv2d_fwd_b16(x, bank["b16"], op.cout, op.k, op.stride, scale, shift, act, 0.1, residual=res)
-                out[op.dst] = o; amx[op.dst] = None
-                continue
+            # "fp8s": a layer that reads its input as e4m3 operands tells conv_forward when it is the last such reader of that tensor
+            last8 = (s16 and x.dtype == torch.bfloat16 and ops.f8_takes(op.cin, op.cout, op.k)
+                     and convblock.last_q8_reader(f8_left, op.src, sum(1 for r_ in readers.get(op.src, []) if isinstance(r_, _ConvOp)
+                                                                      and ops.f8_takes(r_.cin, r_.cout, r_.k))))
+
+            def conv(**kw):
+                return convblock.conv_forward(x, op.k, op.stride, op.cout, w=w, bank=bank, amax_x=ax, amax_w=aw, w_split=wsp, w_b16=w16,
+                                              drop_q8=last8, **kw)
+
             if op.bn and training:
-                # (the conv hands out the abs-max of its raw output with its store: the bound below starts from it)
+                # (the conv hands out the abs-max of its raw output with its store: the bound of an unwritten activation starts from it)
                 ay = ops.amax_slot(x.device) if (not isinstance(x, ops.PreAct) and sole_pre_reader(op, x)) else None
-                y, stats = ops.conv2d_fwd(x, w, op.k, op.stride, want_stats=True, amax_x=ax, amax_w=aw, amax_out=ay,
-                                          w_split_ready=wsp, w_b16=w16)
-                cnt = y.numel() // op.cout
-                mi = ops.bn_finalize(stats, cnt, p["gamma"], p["beta"], 1e-5, p["momentum"], p["rm"], p["rv"])
-                if ay is not None and y.is_contiguous():
-                    ao = ops.bn_act_amax_bound(ay, mi[2], mi[3], 0.1)
-                    o = ops.PreAct(y, mi[2], mi[3], act, 0.1)
-                    if ops.PRE_ACT == "check":        # (tests: the activation written out, read with the same abs-max word)
-                        o = o.materialise()
-                else:
-                    o = ops.scale_act(y, mi[2], mi[3], act, 0.1, residual=res, amax_out=ao, out_b16=s16)    # (s16: the stem's fp32 raw output -> bf16)
+                y, stats = conv(want_stats=True, amax_out=ay)
+                # "fp8s": a reader that takes e4m3 operands gets its copy from the BatchNorm pass (no quantisation pass of its own)
+                q_ = ops.storage_f8() and any(isinstance(r_, _ConvOp) and r_.src == op.dst and ops.f8_takes(r_.cin, r_.cout, r_.k)
+                                              for r_ in readers.get(op.dst, []))
+                mi, o, ao = convblock.train_bn_forward(y, stats, p["gamma"], p["beta"], 1e-5, p["momentum"], p["rm"], p["rv"], act, 0.1,
+                                                       residual=res, amax_out=ao, amax_y=ay, out_b16=s16, quant=q_)    # (s16: the stem's fp32 raw output -> bf16)
                 if save is not None:
-                    save[op.slot] = (x, y, mi, w, ax, aw)
+                    save[op.slot] = convblock.SavedLayer(x, y, w, bank, ax, aw, mi=mi)
             else:
-                if op.bn:
-                    ss = ops.bn_fold(p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5)
-                    scale, shift = ss[0], ss[1]
-                else:
-                    scale, shift = None, p["b"]
+                fold, shift = ((p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5), None) if op.bn else (None, p["b"])
                 if save is None:      # inference: one kernel per layer, shortcut fused in the epilogue
-                    o, _ = ops.conv2d_fwd(x, w, op.k, op.stride, scale, shift, act, 0.1, residual=res, amax_x=ax, amax_w=aw, amax_out=ao,
-                                          w_split_ready=wsp, w_b16=w16)
+                    o, _ = conv(fold=fold, shift=shift, act=act, slope=0.1, residual=res, amax_out=ao)
                 else:                 # frozen-BN fine-tuning: keep the pre-shortcut activation for act'
-                    if res is None:
-                        a, _ = ops.conv2d_fwd(x, w, op.k, op.stride, scale, shift, act, 0.1, amax_x=ax, amax_w=aw, amax_out=ao, w_split_ready=wsp, w_b16=w16)
-                        o = a
-                    else:
-                        a, _ = ops.conv2d_fwd(x, w, op.k, op.stride, scale, shift, act, 0.1, amax_x=ax, amax_w=aw, w_split_ready=wsp, w_b16=w16)
-                        o = ops.scale_act(a, None, None, ops.ACT_NONE, 0.0, residual=res, amax_out=ao)
-                    save[op.slot] = (x, a, scale, w, ax, aw)
+                    a, ss = conv(fold=fold, shift=shift, act=act, slope=0.1, amax_out=ao if res is None else None)
+                    o = a if res is None else ops.scale_act(a, None, None, ops.ACT_NONE, 0.0, residual=res, amax_out=ao)
+                    save[op.slot] = convblock.SavedLayer(x, a, w, bank, ax, aw, scale=None if ss is None else ss[0])
             if s16:
                 o = ops.to_b16(o)          # (the stem in inference: its fused epilogue wrote fp32)
             out[op.dst] = o; amx[op.dst] = ao
@@ -476,8 +441,7 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
     producer = {op.dst: op for op in plan if isinstance(op, _ConvOp)}
     first_use: Dict[int, int] = {}
     for i, op in enumerate(plan):
-        ins = (op.src, op.res) if isinstance(op, _ConvOp) else (op.up_src, op.lat_src) if isinstance(op, _UpCatOp) else (op.src,)
-        for s_ in ins:
+        for s_ in _inputs(op):
             if s_ is not None:
                 first_use.setdefault(s_, i)
     index_of = {id(op): i for i, op in enumerate(plan)}
@@ -493,6 +457,17 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
             d_["w"] = hw_.issue()
             if sink is not None:
                 pending.append((slot_, "w", d_["w"])); pending_bytes += d_["w"].numel() * 4
+
+    def finished(slot, d):
+        """the gradients of a layer are final (a held weight gradient follows through release): to the reducer's sink, bucket by bucket"""
+        nonlocal pending, pending_bytes
+        pg[slot] = d
+        if sink is not None:
+            for k_, t_ in d.items():
+                if t_ is not None:
+                    pending.append((slot, k_, t_)); pending_bytes += t_.numel() * 4
+            if pending_bytes >= bucket_bytes:
+                sink(pending); pending = []; pending_bytes = 0
 
     for op in reversed(plan):
         dout = g.pop(op.dst, None)
@@ -512,7 +487,10 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
             add(op.lat_src, dout[..., op.c_up:])
         else:
             p = P[op.slot]
-            x, y, aux, w, ax, aw = save.pop(op.slot)
+            rec = save.pop(op.slot)
+            x, y = rec.x, rec.y
+            act = ops.ACT_LEAKY if op.leaky else ops.ACT_NONE
+            # the stem: nothing but its weight gradient reads dy, so dy is formed inside that kernel and never written
             stem_fused = (op.bn and training and not op.need_dx and ops.STEM_FUSED_BWD and torch.is_tensor(x) and x.shape[3] == 4 and op.cout == 32
                           and op.k == 3 and op.stride == 1 and op.res is None and torch.is_tensor(y) and y.is_contiguous() and x.shape[2] >= 32)
             if s16 and torch.is_tensor(x) and x.dtype == torch.float32 and dout.dtype == torch.bfloat16 and not stem_fused:
@@ -520,111 +498,54 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
             shape = tuple(p["w"].shape)
             d = {}
             ady = ops.amax_slot(dout.device) if ops.use_amax() else None
-            if (op.bn and training and not op.need_dx and ops.STEM_FUSED_BWD and x.shape[3] == 4 and op.cout == 32 and op.k == 3
-                    and op.stride == 1 and op.res is None and y.is_contiguous() and x.shape[2] >= 32):
-                # the stem: nothing but its weight gradient reads dy, so dy is formed inside that kernel and never written
-                mi = aux
-                dw, d["gamma"], d["beta"] = ops.stem_bwd_weight_bn(x, y, dout, mi[0], mi[1], p["gamma"], p["beta"],
-                                                                   ops.ACT_LEAKY if op.leaky else ops.ACT_NONE, 0.1,
+            if stem_fused:
+                dw, d["gamma"], d["beta"] = ops.stem_bwd_weight_bn(x, y, dout, rec.mi[0], rec.mi[1], p["gamma"], p["beta"], act, 0.1,
                                                                    part=tapped.pop(op.slot, None))
                 d["w"] = ops.weight_grad_to_oihw(dw, shape)
-                pg[op.slot] = d
-                if sink is not None:
-                    for k_, t_ in d.items():
-                        if t_ is not None:
-                            pending.append((op.slot, k_, t_)); pending_bytes += t_.numel() * 4
-                    if pending_bytes >= bucket_bytes:
-                        sink(pending); pending = []; pending_bytes = 0
+                finished(op.slot, d)
                 continue
             if op.bn and training:
-                mi = aux
-                dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, mi[0], mi[1], p["gamma"], p["beta"],
-                                                   ops.ACT_LEAKY if op.leaky else ops.ACT_NONE, 0.1, amax_out=ady,
-                                                   part=tapped.pop(op.slot, None),
-                                                   quant=bool(op.need_dx) and ops.f8_takes(op.cout, op.cin, op.k))      # ("fp8s": dy's e4m3 copy for the data gradient)
-                d["gamma"], d["beta"] = dgamma, dbeta
+                dy, d["gamma"], d["beta"] = ops.bn_act_bwd(y, dout, rec.mi[0], rec.mi[1], p["gamma"], p["beta"], act, 0.1, amax_out=ady,
+                                                           part=tapped.pop(op.slot, None),
+                                                           quant=bool(op.need_dx) and ops.f8_takes(op.cout, op.cin, op.k))      # ("fp8s": dy's e4m3 copy for the data gradient)
             else:
                 # frozen statistics: y holds act(scale*conv+shift) before the shortcut add
-                dz = ops.act_bwd(y, dout, 0.1) if op.leaky else dout
-                if aux is not None:       # folded BN: z = scale*conv + shift
-                    xhat_like = None
-                    dy = dz * aux
-                    d["beta"] = dz.reshape(-1, op.cout).sum(0)
-                    # dgamma = sum(dz * (conv - rm) * rsqrt(rv+eps)); recover conv from y only where act is
-                    # invertible (leaky/none are), z = y>0 ? y : y/slope
-                    z = torch.where(y > 0, y, y / 0.1) if op.leaky else y
-                    gsafe = torch.where(p["gamma"] == 0, torch.ones_like(p["gamma"]), p["gamma"])
-                    d["gamma"] = (dz * (z - p["beta"]) / gsafe).reshape(-1, op.cout).sum(0)
+                if rec.scale is not None:       # folded BN: z = scale*conv + shift
+                    dy, dgamma, d["beta"] = convblock.frozen_bn_backward(y, dout, rec.scale, p["gamma"], p["beta"], act, 0.1)
+                    d["gamma"] = dgamma          # (behind beta: the order in which the reducer's sink sees them)
                 else:
-                    dy = dz
+                    dy = ops.act_bwd(y, dout, 0.1) if op.leaky else dout
                     if p["b"] is not None:
-                        d["b"] = dz.reshape(-1, op.cout).sum(0)
+                        d["b"] = dy.reshape(-1, op.cout).sum(0)
                 ady = None            # (frozen-BN path: the GEMMs below compute the abs-max of dy themselves)
             if op.res is not None:
                 add(op.res, dout)
             release()                  # (behind this layer's BatchNorm passes: the main chain stays the first dependent of the data gradient before)
-            if not ops.WGRAD_AFTER_DGRAD:
-                d["w"] = ops.wgrad_on_side(x, dy, op.k, op.stride, shape, amax_x=ax, amax_dy=ady)     # overlaps with the data gradient below
-            if op.need_dx and s16 and dy.dtype == torch.bfloat16:
+
+            def dgrad():
+                if not op.need_dx:
+                    return
                 cur = g.get(op.src)
-                tap = None
+                b16 = s16 and dy.dtype == torch.bfloat16
                 prev = producer.get(op.src)
-                if (ops.BN_TAP and ops.BN_TAP_TRUNK and training and op.stride == 1 and prev is not None and prev.bn
-                        and first_use.get(op.src) == index_of[id(op)] and prev.slot in save):
-                    _, y_prev, mi_prev = save[prev.slot][:3]
-                    if torch.is_tensor(y_prev) and y_prev.dtype == torch.bfloat16 and y_prev.is_contiguous():
-                        tap = dict(y=y_prev, mean=mi_prev[0], invstd=mi_prev[1], gamma=P[prev.slot]["gamma"], beta=P[prev.slot]["beta"],
-                                   act=ops.ACT_LEAKY if prev.leaky else ops.ACT_NONE, slope=0.1)
-                if ops.f8_takes(op.cout, op.cin, op.k) and dy.is_contiguous():      # "fp8s": the data gradient on e4m3 operands
-                    dy8, dys = ops.quant_of(dy)
-                    wt8, wts = ops.bank_q8(getattr(w, "_dcn_bank", None), "tq8", getattr(w, "_dcn_wt16"), op.cin)
-                    res_ = ops.conv2d_bwd_data_f8(dy8, dys, wt8.view(-1), wts, (x.shape[1], x.shape[2]), x.shape[3], op.k, op.stride,
-                                                  out=cur, accumulate=cur is not None, tap=tap)
-                else:
-                    res_ = ops.conv2d_bwd_data_b16(dy, getattr(w, "_dcn_wt16"), (x.shape[1], x.shape[2]), x.shape[3], op.k, op.stride,
-                                                   out=cur, accumulate=cur is not None, tap=tap)
-                if tap is not None:
-                    res_, part_ = res_
-                    if part_ is not None:
-                        tapped[prev.slot] = part_
-                if cur is None:
-                    g[op.src] = res_
-            elif op.need_dx:
-                cur = g.get(op.src)
-                hw = (x.shape[1], x.shape[2])
-                wtr = getattr(w, "_dcn_wt", None)      # the transposed banks of this step (ops.FilterBanks)
-                wt16 = getattr(w, "_dcn_wt16", None)
                 tap = None
-                prev = producer.get(op.src)
-                # (the register-bank kernel of the stride-2 layer behind the stem; every stride-1 layer on conv1.hip / conv3.hip)
-                if (ops.BN_TAP and training and prev is not None and prev.bn and first_use.get(op.src) == index_of[id(op)]
-                        and prev.slot in save
-                        and ((x.shape[3] == 32 and op.stride == 2 and op.k == 3) or (ops.BN_TAP_TRUNK and op.stride == 1 and x.shape[3] >= 64
-                                 and (ops.BN_TAP_TRUNK is True or ops.BN_TAP_TRUNK == 1 or (ops.BN_TAP_TRUNK == 2) == (op.k == 3))))):
-                    _, y_prev, mi_prev = save[prev.slot][:3]
-                    if torch.is_tensor(y_prev) and y_prev.is_contiguous():
-                        tap = dict(y=y_prev, mean=mi_prev[0], invstd=mi_prev[1], gamma=P[prev.slot]["gamma"], beta=P[prev.slot]["beta"],
-                                   act=ops.ACT_LEAKY if prev.leaky else ops.ACT_NONE, slope=0.1)
-                res_ = ops.conv2d_bwd_data(dy, w, hw, op.k, op.stride, out=cur, accumulate=cur is not None, amax_dy=ady, amax_w=aw,
-                                           wt_ready=wtr, wt_b16=wt16, tap=tap)
-                if tap is not None:
-                    res_, part_ = res_
-                    if part_ is not None:
-                        tapped[prev.slot] = part_
+                if prev is not None and prev.bn and first_use.get(op.src) == index_of[id(op)]:
+                    tap = convblock.bn_tap_for(b16, training, x.shape[3], op.k, op.stride, save.get(prev.slot), P[prev.slot]["gamma"],
+                                               P[prev.slot]["beta"], ops.ACT_LEAKY if prev.leaky else ops.ACT_NONE, 0.1)
+                fb = rec.bank              # the banks of this step (ops.FilterBanks; None: transposed per launch)
+                dx, part = convblock.conv_dgrad(dy, x.shape, op.k, op.stride, w=rec.w, bank=fb, out=cur, accumulate=cur is not None, tap=tap,
+                                                amax_dy=ady, amax_w=rec.aw, wt_ready=fb and (fb["t"], fb["tsplit"]), wt_b16=fb and fb["tb16"])
+                if part is not None:
+                    tapped[prev.slot] = part
                 if cur is None:
-                    g[op.src] = res_
-            if ops.WGRAD_AFTER_DGRAD:      # (schedule experiment: queued behind the data gradient, beside the next layer's BatchNorm passes)
-                if ops.WGRAD_SIDE and ops.WGRAD_HELD:
-                    held = (d, op.slot, ops.HeldWgrad(x, dy, op.k, op.stride, shape, amax_x=ax, amax_dy=ady))
-                else:
-                    d["w"] = ops.wgrad_on_side(x, dy, op.k, op.stride, shape, amax_x=ax, amax_dy=ady)
-            pg[op.slot] = d
-            if sink is not None:
-                for k_, t_ in d.items():
-                    if t_ is not None:
-                        pending.append((op.slot, k_, t_)); pending_bytes += t_.numel() * 4
-                if pending_bytes >= bucket_bytes:
-                    sink(pending); pending = []; pending_bytes = 0
+                    g[op.src] = dx
+
+            _, dw = convblock.schedule_wgrad(x, dy, op.k, op.stride, shape, dgrad, amax_x=rec.ax, amax_dy=ady, may_hold=True)
+            if isinstance(dw, ops.HeldWgrad):      # launched behind the next layer's BatchNorm passes (release)
+                held = (d, op.slot, dw)
+            else:
+                d["w"] = dw
+            finished(op.slot, d)
     release()
     if sink is not None and pending:
         sink(pending)
@@ -656,12 +577,8 @@ class _DarknetFn(torch.autograd.Function):
                                                         taps_b16=bool(net.__dict__.get("_taps_b16")))
         net._tap_amax = tap_amax              # abs-max words of the three taps (read by the head's first convolutions)
         if save is not None:
-            # outputs must go through save_for_backward (an attribute reference would make a
-            # ctx <-> output cycle and pin the whole activation set until the GC runs)
-            for slot, tup in list(save.items()):
-                for k, o in enumerate(outs):
-                    if tup[0] is o:
-                        save[slot] = (("tap", k),) + tup[1:]
+            for rec in save.values():
+                rec.unlink_outputs(outs)          # (outputs go through save_for_backward)
             ctx.save_for_backward(*outs)
         ctx.net, ctx.training, ctx.save, ctx.nflat = net, training, save, len(flat)
         ctx.P = P
@@ -675,8 +592,10 @@ class _DarknetFn(torch.autograd.Function):
                                                                "(one backward per forward; retain_graph is not supported)")
             raise (NotImplementedError if "bf16" in why else RuntimeError)("dcnet_amd.Darknet: " + why)
         outs = ctx.saved_tensors
-        save = {slot: ((outs[t[0][1]],) + t[1:] if isinstance(t[0], tuple) else t) for slot, t in ctx.save.items()}
+        save = ctx.save
         ctx.save = None
+        for rec in save.values():
+            rec.link_outputs(outs)
         red = net.__dict__.get("_grad_reducer")       # parallel.OverlappedGradReducer (data-parallel runs), else None
         sink = None
         if red is not None:
@@ -760,15 +679,10 @@ class Darknet(nn.Module):
 
     def _filter_banks(self, P):
         """All filter banks of the backbone in their GEMM forms, refreshed once per forward (ops.FilterBanks: three launches
-        instead of ~5 small kernels per layer; the banks of a step serve its backward too).  The job table holds raw parameter
-        addresses, so it is rebuilt when a parameter moved."""
+        instead of ~5 small kernels per layer; the banks of a step serve its backward too)."""
         if not ops.FILTER_BANKS:
             return None
-        ws = {slot: d["w"] for slot, d in P.items()}
-        fb = self.__dict__.get("_fbanks")
-        if fb is None or not fb.valid_for(ws):
-            fb = ops.FilterBanks(ws, next(iter(ws.values())).device)
-            self.__dict__["_fbanks"] = fb
+        fb = convblock.cached_filter_banks(self.__dict__, "_fbanks", {slot: d["w"] for slot, d in P.items()})
         # the refresh (0.6 ms of kernels) runs on a stream of its own, beside the image transpose and the stem, which do not read
         # the banks; _run_forward joins it in front of the first convolution that does
         main = torch.cuda.current_stream()

@@ -7,7 +7,7 @@ from typing import Optional
 
 import torch
 
-from . import ops
+from . import convblock, ops
 
 
 class ConvBNAct(torch.autograd.Function):
@@ -26,60 +26,33 @@ class ConvBNAct(torch.autograd.Function):
         am = ops.use_amax()
         if bank is not None and x.shape[3] != weight.shape[1]:
             bank = None                    # (K-padded input: the per-launch path pads the bank)
-        ctx.b16 = None
-        ctx.wparam = weight if (ops.WGRAD_DIRECT and ops.WGRAD_SIDE and training and isinstance(weight, torch.nn.Parameter)
-                                and weight.requires_grad) else None
-        if ops.storage_b16() and bank is not None:
-            x_f32 = x.dtype == torch.float32
-            x16 = ops.to_b16(x.contiguous())
-            use8 = ops.f8_takes(x16.shape[3], cout, ksize)          # "fp8s": the head's 3x3 block on e4m3 operands
-            if use8:
-                x8, xs = ops.quant_of(x16)
-                w8, ws = ops.bank_q8(bank, "q8", bank["b16"], cout)
-            if training and use8:
-                y, stats = ops.conv2d_fwd_f8(x8, xs, w8.view(-1), ws, cout, ksize, 1, want_stats=True)
-                mi = ops.bn_finalize(stats, y.numel() // cout, gamma.detach(), beta.detach(), bn.eps, bn.momentum,
-                                     bn.running_mean, bn.running_var)
-                ops.bump_batches(bn)
-                out = ops.scale_act(y, mi[2], mi[3], ops.ACT_LEAKY, slope, out_f32=not out_b16)
-                ctx.save_for_backward(x16, y, mi, gamma, beta)
-            elif training:
-                y, stats = ops.conv2d_fwd_b16(x16, bank["b16"], cout, ksize, 1, want_stats=True)
-                mi = ops.bn_finalize(stats, y.numel() // cout, gamma.detach(), beta.detach(), bn.eps, bn.momentum,
-                                     bn.running_mean, bn.running_var)
-                ops.bump_batches(bn)
-                out = ops.scale_act(y, mi[2], mi[3], ops.ACT_LEAKY, slope, out_f32=not out_b16)
-                ctx.save_for_backward(x16, y, mi, gamma, beta)
+        ctx.wparam = convblock.direct_wgrad_param(weight, training)
+        ctx.b16 = ops.storage_b16() and bank is not None
+        ctx.x_f32 = x.dtype == torch.float32
+        w = wsp = aw = ax = ao = None
+        if ctx.b16:
+            x = ops.to_b16(x.contiguous())
+        else:
+            if bank is not None:
+                w, wsp = bank["ohwi"], bank["split"]
+                aw = bank["amax"] if am else None
             else:
-                ss = ops.bn_fold(gamma.detach(), beta.detach(), bn.running_mean, bn.running_var, bn.eps)
-                if use8:
-                    out, _ = ops.conv2d_fwd_f8(x8, xs, w8.view(-1), ws, cout, ksize, 1, ss[0], ss[1], ops.ACT_LEAKY, slope, out_f32=not out_b16)
-                else:
-                    out, _ = ops.conv2d_fwd_b16(x16, bank["b16"], cout, ksize, 1, ss[0], ss[1], ops.ACT_LEAKY, slope, out_f32=not out_b16)
-            ctx.b16 = (bank["tb16"], x_f32); ctx.bank = bank
-            ctx.meta = (ksize, training, slope, tuple(weight.shape))
-            return out, None
-        wsp = wtr = None
-        if bank is not None:
-            w, wsp, wtr = bank["ohwi"], bank["split"], (bank["t"], bank["tsplit"])
-            aw = bank["amax"] if am else None
-        else:
-            w = ops.weight_to_ohwi(weight, ci_pad=x.shape[3])
-            aw = ops.absmax(weight.detach()) if am else None
-        ax = (amax_x if amax_x is not None else ops.absmax(x)) if am else None
-        ao = ops.amax_slot(x.device) if am else None
-        ctx.wtr = wtr
+                w = ops.weight_to_ohwi(weight, ci_pad=x.shape[3])
+                aw = ops.absmax(weight.detach()) if am else None
+            ax = (amax_x if amax_x is not None else ops.absmax(x)) if am else None
+            ao = ops.amax_slot(x.device) if am else None
         if training:
-            y, stats = ops.conv2d_fwd(x, w, ksize, 1, want_stats=True, amax_x=ax, amax_w=aw, w_split_ready=wsp)
-            mi = ops.bn_finalize(stats, y.numel() // cout, gamma.detach(), beta.detach(), bn.eps, bn.momentum,
-                                 bn.running_mean, bn.running_var)
-            ops.bump_batches(bn)
-            out = ops.scale_act(y, mi[2], mi[3], ops.ACT_LEAKY, slope, amax_out=ao)
-            ctx.save_for_backward(x, y, mi, w, gamma, beta)
+            y, stats = convblock.conv_forward(x, ksize, 1, cout, w=w, bank=bank, want_stats=True, amax_x=ax, amax_w=aw, w_split=wsp)
+            aux, out, _ = convblock.train_bn_forward(y, stats, gamma.detach(), beta.detach(), bn.eps, bn.momentum, bn.running_mean,
+                                                     bn.running_var, ops.ACT_LEAKY, slope, bn=bn, amax_out=ao, out_f32=not out_b16)
         else:
-            ss = ops.bn_fold(gamma.detach(), beta.detach(), bn.running_mean, bn.running_var, bn.eps)
-            out, _ = ops.conv2d_fwd(x, w, ksize, 1, ss[0], ss[1], ops.ACT_LEAKY, slope, amax_x=ax, amax_w=aw, amax_out=ao, w_split_ready=wsp)
-            ctx.save_for_backward(x, out, ss, w, gamma, beta)
+            out, aux = convblock.conv_forward(x, ksize, 1, cout, w=w, bank=bank, fold=(gamma.detach(), beta.detach(), bn.running_mean,
+                                                                                       bn.running_var, bn.eps),
+                                              act=ops.ACT_LEAKY, slope=slope, out_f32=not out_b16, amax_x=ax, amax_w=aw, amax_out=ao, w_split=wsp)
+            y = out
+        if training or not ctx.b16:        # (bf16 storage has no backward in eval mode: nothing is kept)
+            ctx.save_for_backward(x, y, aux, w, gamma, beta)
+        ctx.bank = bank
         ctx.meta = (ksize, training, slope, tuple(weight.shape))
         ctx.amax = (ax, aw)
         if ao is not None:
@@ -88,64 +61,34 @@ class ConvBNAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _ga=None):
-        if ctx.b16 is not None:            # bf16 storage: dout bf16 or fp32 (read as it is), dy / saved tensors bf16, dw fp32
-            if not ctx.meta[1]:
-                raise NotImplementedError("ConvBNAct, bf16 storage: no backward in eval mode (frozen-BatchNorm fine-tuning is not built)")
-            x16, y, mi, gamma, beta = ctx.saved_tensors
-            ksize, training, slope, wshape = ctx.meta
-            tb16, x_f32 = ctx.b16
-            dy, dgamma, dbeta = ops.bn_act_bwd(y, dout.contiguous(), mi[0], mi[1], gamma.detach(), beta.detach(), ops.ACT_LEAKY, slope,
-                                               quant=ctx.needs_input_grad[0] and ops.f8_takes(y.shape[3], x16.shape[3], ksize))
-            dx = None
-
-            def dgrad():
-                if ops.f8_takes(dy.shape[3], x16.shape[3], ksize) and dy.is_contiguous():      # "fp8s": the data gradient on e4m3 operands
-                    dy8, dys = ops.quant_of(dy)
-                    wt8, wts = ops.bank_q8(getattr(ctx, "bank", None), "tq8", tb16, x16.shape[3])
-                    return ops.conv2d_bwd_data_f8(dy8, dys, wt8.view(-1), wts, (x16.shape[1], x16.shape[2]), x16.shape[3], ksize, 1, out_f32=x_f32)
-                return ops.conv2d_bwd_data_b16(dy, tb16, (x16.shape[1], x16.shape[2]), x16.shape[3], ksize, 1, out_f32=x_f32)
-
-            if ctx.wparam is not None:     # (ops.WGRAD_DIRECT: the block before's weight gradient goes out behind this block's passes)
-                ops.release_held_wgrads()
-                if ctx.needs_input_grad[0]:
-                    dx = dgrad()
-                ops.hold_wgrad_into(ctx.wparam, x16, dy, ksize, 1, wshape)
-                return dx, None, dgamma, dbeta, None, None, None, None, None, None, None
-            if not ops.WGRAD_AFTER_DGRAD:
-                dwt = ops.wgrad_on_side(x16, dy, ksize, 1, wshape)
-            if ctx.needs_input_grad[0]:
-                dx = dgrad()
-            if ops.WGRAD_AFTER_DGRAD:
-                dwt = ops.wgrad_on_side(x16, dy, ksize, 1, wshape)
-            ops.join_side(x16.device)
-            return dx, dwt, dgamma, dbeta, None, None, None, None, None, None, None
+        """bf16 storage: dout bf16 or fp32 (read as it is), dy / saved tensors bf16, dw fp32."""
+        ksize, training, slope, wshape = ctx.meta
+        if ctx.b16 and not training:
+            raise NotImplementedError("ConvBNAct, bf16 storage: no backward in eval mode (frozen-BatchNorm fine-tuning is not built)")
         x, y, aux, w, gamma, beta = ctx.saved_tensors
         gamma, beta = gamma.detach(), beta.detach()
-        ksize, training, slope, wshape = ctx.meta
         ax, aw = ctx.amax
+        bank = ctx.bank
         dout = dout.contiguous()
         ady = None
         if training:
             ady = ops.amax_slot(dout.device) if ops.use_amax() else None
-            dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, aux[0], aux[1], gamma, beta, ops.ACT_LEAKY, slope, amax_out=ady)
+            dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, aux[0], aux[1], gamma, beta, ops.ACT_LEAKY, slope, amax_out=ady,
+                                               quant=ctx.needs_input_grad[0] and ops.f8_takes(y.shape[3], x.shape[3], ksize))
         else:
-            dz = ops.act_bwd(y, dout, slope)
-            dy = dz * aux[0]
-            dbeta = dz.reshape(-1, wshape[0]).sum(0)
-            z = y if slope == 0 else torch.where(y > 0, y, y / slope)
-            gs = torch.where(gamma == 0, torch.ones_like(gamma), gamma)
-            dgamma = (dz * (z - beta) / gs).reshape(-1, wshape[0]).sum(0)
-        if ctx.wparam is not None and training:
-            ops.release_held_wgrads()
-            dx = ops.conv2d_bwd_data(dy, w, (x.shape[1], x.shape[2]), ksize, 1, amax_dy=ady, amax_w=aw, wt_ready=ctx.wtr) if ctx.needs_input_grad[0] else None
-            ops.hold_wgrad_into(ctx.wparam, x, dy, ksize, 1, wshape, amax_x=ax, amax_dy=ady)
-            return dx, None, dgamma, dbeta, None, None, None, None, None, None, None
-        if not ops.WGRAD_AFTER_DGRAD:
-            dwt = ops.wgrad_on_side(x, dy, ksize, 1, wshape, amax_x=ax, amax_dy=ady)
-        dx = ops.conv2d_bwd_data(dy, w, (x.shape[1], x.shape[2]), ksize, 1, amax_dy=ady, amax_w=aw, wt_ready=ctx.wtr) if ctx.needs_input_grad[0] else None
-        if ops.WGRAD_AFTER_DGRAD:
-            dwt = ops.wgrad_on_side(x, dy, ksize, 1, wshape, amax_x=ax, amax_dy=ady)
-        ops.join_side(x.device)
+            dy, dgamma, dbeta = convblock.frozen_bn_backward(y, dout, aux[0], gamma, beta, ops.ACT_LEAKY, slope)
+
+        def dgrad():
+            if not ctx.needs_input_grad[0]:
+                return None
+            return convblock.conv_dgrad(dy, x.shape, ksize, 1, w=w, bank=bank, out_f32=ctx.x_f32, amax_dy=ady, amax_w=aw,
+                                        wt_ready=bank and (bank["t"], bank["tsplit"]))[0]
+
+        # (ops.WGRAD_DIRECT: the block before's weight gradient goes out behind this block's passes, this one's is added to .grad on the
+        #  side stream: no join here)
+        dx, dwt = convblock.schedule_wgrad(x, dy, ksize, 1, wshape, dgrad, amax_x=ax, amax_dy=ady, direct_into=ctx.wparam)
+        if ctx.wparam is None:
+            ops.join_side(x.device)
         return dx, dwt, dgamma, dbeta, None, None, None, None, None, None, None
 
 
@@ -158,64 +101,52 @@ class ConvBias(torch.autograd.Function):
     def forward(ctx, x, weight, bias, amax_x=None):
         cout = weight.shape[0]
         cop = ops.pad32(cout)
-        ctx.wparam = weight if (ops.WGRAD_DIRECT and ops.WGRAD_SIDE and isinstance(weight, torch.nn.Parameter) and weight.requires_grad) else None
+        ctx.wparam = convblock.direct_wgrad_param(weight)
         w = ops.weight_to_ohwi(weight, ci_pad=x.shape[3], co_pad=cop)
         b = torch.zeros(cop, dtype=torch.float32, device=x.device)
         b[:cout] = bias.detach()
-        ctx.b16 = None
-        if ops.storage_b16() and weight.shape[2] == 1 and x.shape[3] % 32 == 0:
-            # bf16 storage: x bf16 (an fp32 x is cast once), the 32 x Cin bank in bf16 (8 K elements: converted here), logits fp32
-            x_f32 = x.dtype == torch.float32
-            x16 = ops.to_b16(x.contiguous())
-            w16 = w.reshape(cop, -1).to(torch.bfloat16)
-            y, _ = ops.conv2d_fwd_b16(x16, w16.reshape(-1), cop, 1, 1, None, b, out_f32=True)
-            ctx.save_for_backward(x16, w16)
-            ctx.wshape = tuple(weight.shape)
-            ctx.b16 = x_f32
-            return y
-        y, _ = ops.conv2d_fwd(x, w, weight.shape[2], 1, None, b)          # (32 filters: the fp32-pipe tile, no scales)
-        ctx.save_for_backward(x, w)
         ctx.wshape = tuple(weight.shape)
-        ctx.amax = (amax_x, ops.absmax(weight.detach()) if ops.use_amax() else None)
+        ctx.b16 = ops.storage_b16() and weight.shape[2] == 1 and x.shape[3] % 32 == 0
+        ctx.x_f32 = x.dtype == torch.float32
+        ctx.amax, bank = (None, None), None
+        if ctx.b16:
+            # bf16 storage: x bf16 (an fp32 x is cast once), the 32 x Cin bank in bf16 (8 K elements: converted here), logits fp32
+            x = ops.to_b16(x.contiguous())
+            w = w.reshape(cop, -1).to(torch.bfloat16)
+            bank = {"b16": w.reshape(-1)}
+        y, _ = convblock.conv_forward(x, weight.shape[2], 1, cop, w=w, bank=bank, shift=b, out_f32=True)   # (32 filters: the fp32-pipe tile, no scales)
+        ctx.save_for_backward(x, w)
+        if not ctx.b16:
+            ctx.amax = (amax_x, ops.absmax(weight.detach()) if ops.use_amax() else None)
         return y
 
     @staticmethod
     def backward(ctx, dy):
-        if ctx.b16 is not None:
-            x16, w16 = ctx.saved_tensors
-            co, ci, k, _ = ctx.wshape
-            dy = dy.contiguous()
-            db = ops.colsum_rows(dy.view(-1, dy.shape[-1]))[:co]
-            dy16 = ops.to_b16(dy)
-            dx = None
-            if ctx.wparam is not None:      # (ops.WGRAD_DIRECT: added to .grad on the side stream, no join here)
-                ops.release_held_wgrads()
-                if ctx.needs_input_grad[0]:
-                    dx = ops.conv2d_bwd_data_b16(dy16, w16.t().contiguous().reshape(-1), (x16.shape[1], x16.shape[2]), x16.shape[3], 1, 1,
-                                                 out_f32=ctx.b16)
-                ops.hold_wgrad_into(ctx.wparam, x16, dy16, 1, 1, ctx.wshape)
-                return dx, None, db, None
-            dwt = ops.wgrad_on_side(x16, dy16, 1, 1, ctx.wshape)
-            if ctx.needs_input_grad[0]:
-                dx = ops.conv2d_bwd_data_b16(dy16, w16.t().contiguous().reshape(-1), (x16.shape[1], x16.shape[2]), x16.shape[3], 1, 1,
-                                             out_f32=ctx.b16)
-            ops.join_side(x16.device)
-            return dx, dwt, db, None
-        x, w = ctx.saved_tensors
+        x, w = ctx.saved_tensors           # (bf16 storage: both bf16, w the [32][Cin] bank)
         co, ci, k, _ = ctx.wshape
         ax, aw = ctx.amax
         dy = dy.contiguous()
-        ady = ops.absmax(dy) if ops.use_amax() else None
-        if ctx.wparam is not None:
-            ops.release_held_wgrads()
-            db = ops.colsum_rows(dy.view(-1, dy.shape[-1]))[:co]
-            dx = ops.conv2d_bwd_data(dy, w, (x.shape[1], x.shape[2]), k, 1, amax_dy=ady, amax_w=aw) if ctx.needs_input_grad[0] else None
-            ops.hold_wgrad_into(ctx.wparam, x, dy, k, 1, ctx.wshape, amax_x=ax, amax_dy=ady)
-            return dx, None, db, None
-        dwt = ops.wgrad_on_side(x, dy, k, 1, ctx.wshape, amax_x=ax, amax_dy=ady)
-        db = ops.colsum_rows(dy.view(-1, dy.shape[-1]))[:co]
-        dx = ops.conv2d_bwd_data(dy, w, (x.shape[1], x.shape[2]), k, 1, amax_dy=ady, amax_w=aw) if ctx.needs_input_grad[0] else None
-        ops.join_side(x.device)
+        rowsum = lambda: ops.colsum_rows(dy.view(-1, dy.shape[-1]))[:co]
+        if ctx.b16:
+            db = rowsum()                  # (of the fp32 gradient)
+            dy, ady = ops.to_b16(dy), None
+        else:
+            db = None                      # (fp32: the pass goes between the two gradients' launches)
+            ady = ops.absmax(dy) if ops.use_amax() else None
+
+        def dgrad():
+            nonlocal db
+            if db is None:
+                db = rowsum()
+            if not ctx.needs_input_grad[0]:
+                return None
+            bank = {"tb16": w.t().contiguous().reshape(-1)} if ctx.b16 else None
+            return convblock.conv_dgrad(dy, x.shape, k, 1, w=w, bank=bank, out_f32=ctx.x_f32, amax_dy=ady, amax_w=aw)[0]
+
+        # (ops.WGRAD_DIRECT: added to .grad on the side stream, no join here)
+        dx, dwt = convblock.schedule_wgrad(x, dy, k, 1, ctx.wshape, dgrad, amax_x=ax, amax_dy=ady, after=False, direct_into=ctx.wparam)
+        if ctx.wparam is None:
+            ops.join_side(x.device)
         return dx, dwt, db, None
 
 
@@ -515,31 +446,27 @@ class FusionConvBNAct(torch.autograd.Function):
         coord2d = coord.reshape(h * w, -1).contiguous()
         # the pre-filled term W2.flang[n] + W3.coord[p] (csrc/fusion.hip; W2, W3 are column slices of the parameter: no copies)
         y = ops.fusion_prefill(ops.gemm_nt(flang.detach().contiguous(), w2), coord2d, w3).view(n, h, w, co)
-        ctx.b16 = False
-        if ops.storage_b16() and training and e % 32 == 0 and co % 32 == 0:
-            # bf16 storage: the K = E convolution on bf16 operands (corr cast once, the 512 x 512 bank converted here), accumulated onto the
-            # fp32 pre-fill in the kernel's epilogue — raw result and statistics fp32 —, the activation written as bf16 for the next block
-            corr16 = ops.to_b16(corr)
-            w16 = w1.view(co, e).to(torch.bfloat16)
-            y, stats = ops.conv2d_fwd_b16(corr16, w16.reshape(-1), co, 1, 1, out=y, want_stats=True, accumulate=True, out_f32=True)
-            mi = ops.bn_finalize(stats, n * h * w, gamma.detach(), beta.detach(), bn.eps, bn.momentum, bn.running_mean, bn.running_var)
-            ops.bump_batches(bn)
-            out = ops.scale_act(y, mi[2], mi[3], ops.ACT_LEAKY, 0.0, out_b16=True)
-            ctx.save_for_backward(corr16, y, mi, w16, gamma, beta, flang, weight)
-            ctx.training, ctx.coord2d, ctx.b16, ctx.amax = True, coord2d, True, (None, None)
-            return out, None
-        wk = ops.weight_to_ohwi(w1)
-        aw = ops.absmax(wk) if am else None
-        if training:
-            y, stats = ops.conv2d_fwd(corr, wk, 1, 1, out=y, want_stats=True, accumulate=True, amax_x=ax, amax_w=aw)
-            mi = ops.bn_finalize(stats, n * h * w, gamma.detach(), beta.detach(), bn.eps, bn.momentum, bn.running_mean, bn.running_var)
-            ops.bump_batches(bn)
-            out = ops.scale_act(y, mi[2], mi[3], ops.ACT_LEAKY, 0.0, amax_out=ao)
-            ctx.save_for_backward(corr, y, mi, wk, gamma, beta, flang, weight)
+        # bf16 storage: the K = E convolution on bf16 operands (corr cast once, the 512 x 512 bank converted here), accumulated onto the
+        # fp32 pre-fill in the kernel's epilogue — raw result and statistics fp32 —, the activation written as bf16 for the next block
+        ctx.b16 = ops.storage_b16() and training and e % 32 == 0 and co % 32 == 0
+        aw = bank = None
+        if ctx.b16:
+            corr = ops.to_b16(corr)
+            wk = w1.view(co, e).to(torch.bfloat16)
+            bank = {"b16": wk.reshape(-1)}
         else:
-            ss = ops.bn_fold(gamma.detach(), beta.detach(), bn.running_mean, bn.running_var, bn.eps)
-            out, _ = ops.conv2d_fwd(corr, wk, 1, 1, ss[0], ss[1], ops.ACT_LEAKY, 0.0, out=y, accumulate=True, amax_x=ax, amax_w=aw, amax_out=ao)
-            ctx.save_for_backward(corr, out, ss, wk, gamma, beta, flang, weight)
+            wk = ops.weight_to_ohwi(w1)
+            aw = ops.absmax(wk) if am else None
+        if training:
+            y, stats = convblock.conv_forward(corr, 1, 1, co, w=wk, bank=bank, out=y, want_stats=True, accumulate=True, out_f32=True,
+                                              amax_x=ax, amax_w=aw)
+            aux, out, _ = convblock.train_bn_forward(y, stats, gamma.detach(), beta.detach(), bn.eps, bn.momentum, bn.running_mean,
+                                                     bn.running_var, ops.ACT_LEAKY, 0.0, bn=bn, amax_out=ao, out_b16=ctx.b16)
+        else:
+            out, aux = convblock.conv_forward(corr, 1, 1, co, w=wk, fold=(gamma.detach(), beta.detach(), bn.running_mean, bn.running_var, bn.eps),
+                                              act=ops.ACT_LEAKY, slope=0.0, out=y, accumulate=True, amax_x=ax, amax_w=aw, amax_out=ao)
+            y = out
+        ctx.save_for_backward(corr, y, aux, wk, gamma, beta, flang, weight)
         ctx.training = training
         ctx.coord2d = coord2d
         ctx.amax = (ax, aw)
@@ -549,41 +476,32 @@ class FusionConvBNAct(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dout, _ga=None):
-        corr, y, aux, wk, gamma, beta, flang, weight = ctx.saved_tensors
+        corr, y, aux, wk, gamma, beta, flang, weight = ctx.saved_tensors      # (bf16 storage: corr and the bank wk bf16, y fp32)
         gamma, beta = gamma.detach(), beta.detach()
         n, h, w, e = corr.shape
         co = weight.shape[0]
         ax, aw = ctx.amax
         dout = dout.contiguous()
-        if ctx.b16:
-            dy16, dgamma, dbeta = ops.bn_act_bwd(y, dout, aux[0], aux[1], gamma, beta, ops.ACT_LEAKY, 0.0)      # y fp32, dout bf16 | fp32 -> dy bf16
-            dw1 = ops.wgrad_on_side(corr, dy16, 1, 1, (co, e, 1, 1)).view(co, e)
-            dcorr = ops.conv2d_bwd_data_b16(dy16, wk.t().contiguous().reshape(-1), (h, w), e, 1, 1, out_f32=True) if ctx.needs_input_grad[0] else None
-            ops.join_side(corr.device)
-            wd = weight.detach().view(co, -1)
-            dweight = torch.empty((co, wd.shape[1]), dtype=torch.float32, device=dy16.device)
-            d_img = ops.fusion_bwd(ops.to_f32(dy16), ctx.coord2d, flang.detach().contiguous(), dweight, e)     # (the per-image / per-position terms read fp32)
-            ops.copy_slice(dw1, dweight[:, :e])
-            dflang = ops.gemm_nn(d_img, wd[:, e:2 * e]) if ctx.needs_input_grad[1] else None
-            return dcorr, dflang, None, dweight.view_as(weight), dgamma, dbeta, None, None, None
         ady = None
         if ctx.training:
             ady = ops.amax_slot(dout.device) if ops.use_amax() else None
-            dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, aux[0], aux[1], gamma, beta, ops.ACT_LEAKY, 0.0, amax_out=ady)
+            dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, aux[0], aux[1], gamma, beta, ops.ACT_LEAKY, 0.0, amax_out=ady)      # (bf16 storage: dy bf16)
         else:
-            dz = ops.act_bwd(y, dout, 0.0)
-            dy = dz * aux[0]
-            dbeta = dz.reshape(-1, co).sum(0)
-            gs = torch.where(gamma == 0, torch.ones_like(gamma), gamma)
-            dgamma = (dz * (y - beta) / gs).reshape(-1, co).sum(0)
+            dy, dgamma, dbeta = convblock.frozen_bn_backward(y, dout, aux[0], gamma, beta, ops.ACT_LEAKY, 0.0)
         wd = weight.detach().view(co, -1)
-        dw1 = ops.wgrad_on_side(corr, dy, 1, 1, (co, e, 1, 1), amax_x=ax, amax_dy=ady).view(co, e)      # overlaps with the data gradient
-        dcorr = ops.conv2d_bwd_data(dy, wk, (h, w), 1, 1, amax_dy=ady, amax_w=aw) if ctx.needs_input_grad[0] else None
+
+        def dgrad():
+            if not ctx.needs_input_grad[0]:
+                return None
+            bank = {"tb16": wk.t().contiguous().reshape(-1)} if ctx.b16 else None
+            return convblock.conv_dgrad(dy, corr.shape, 1, 1, w=wk, bank=bank, out_f32=True, amax_dy=ady, amax_w=aw)[0]
+
+        dcorr, dw1 = convblock.schedule_wgrad(corr, dy, 1, 1, (co, e, 1, 1), dgrad, amax_x=ax, amax_dy=ady, after=False)
         ops.join_side(corr.device)
         # gradients of the per-image / per-position terms: one pass over dy (d_img, dW3), dW2 = d_img^T.flang, dflang = d_img.W2
         dweight = torch.empty((co, wd.shape[1]), dtype=torch.float32, device=dy.device)
-        d_img = ops.fusion_bwd(dy, ctx.coord2d, flang.detach().contiguous(), dweight, e)
-        ops.copy_slice(dw1, dweight[:, :e])
+        d_img = ops.fusion_bwd(ops.to_f32(dy), ctx.coord2d, flang.detach().contiguous(), dweight, e)      # (the terms read fp32)
+        ops.copy_slice(dw1.view(co, e), dweight[:, :e])
         dflang = ops.gemm_nn(d_img, wd[:, e:2 * e]) if ctx.needs_input_grad[1] else None
         return dcorr, dflang, None, dweight.view_as(weight), dgamma, dbeta, None, None, None
 
@@ -723,11 +641,7 @@ class BatchNormRowsAct(torch.autograd.Function):
         if ctx.training:
             dx, dgamma, dbeta = ops.bn_act_bwd(a, dout, aux[0], aux[1], gamma, beta, act, 0.0)
         else:
-            dz = ops.act_bwd(a, dout, 0.0) if ctx.relu else dout
-            dx = dz * aux[0]
-            dbeta = dz.sum(0)
-            gs = torch.where(gamma == 0, torch.ones_like(gamma), gamma)
-            dgamma = (dz * (a - beta) / gs).sum(0)
+            dx, dgamma, dbeta = convblock.frozen_bn_backward(a, dout, aux[0], gamma, beta, act, 0.0)
         return dx, dgamma, dbeta, None, None, None
 
 

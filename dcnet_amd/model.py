@@ -30,7 +30,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from . import ops
+from . import convblock, ops
 from .darknet import Darknet
 from .functions import (BatchNormRowsAct, BiLSTM, CoAttentionCenter, CoAttentionPairs, ConvBias, ConvBNAct, CrossModalSample,
                         Embedding, FusionConvBNAct, HeadTail, InterframeSample, L2Norm, LinearAct, NormAccumulate, NormScore, PhraseAttn, RowDot)
@@ -314,11 +314,7 @@ class grounding_model(nn.Module):
                 blk.__dict__["_dcn_bank"] = None
             return
         blocks = self._head_blocks()
-        ws = {i: b.conv.weight for i, b in enumerate(blocks)}
-        fb = self.__dict__.get("_hbanks")
-        if fb is None or not fb.valid_for(ws):
-            fb = ops.FilterBanks({i: w.detach() for i, w in ws.items()}, next(iter(ws.values())).device)
-            self.__dict__["_hbanks"] = fb
+        fb = convblock.cached_filter_banks(self.__dict__, "_hbanks", {i: b.conv.weight.detach() for i, b in enumerate(blocks)})
         fb.refresh()
         for i, b in enumerate(blocks):
             b.__dict__["_dcn_bank"] = fb.get(i, b.conv.weight)

@@ -114,7 +114,7 @@ def get_precision() -> str:
 REGION_PRECISION = None
 
 
-B16_DIAG = None      # experiments: {"layers": slot -> bool, "res32": bool} for the bf16-storage backbone in eval mode (darknet._run_forward)
+B16_DIAG = None      # experiments: {"layers": slot -> bool, "res32": bool} for the bf16-storage backbone in eval mode (darknet._b16_diag_layer)
 
 
 def region(name: str) -> None:
@@ -344,16 +344,6 @@ def conv_out_hw(h: int, w: int, k: int, stride: int) -> Tuple[int, int]:
     return (h + 2 * pad - k) // stride + 1, (w + 2 * pad - k) // stride + 1
 
 
-def f8_scales(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
-    """Device tensor {s_a, s_w}: power-of-two scales that map max|a| and max|w| into the fp8 e4m3 range (dcn_f8_scale)."""
-    out = torch.empty(4, dtype=torch.float32, device=a.device)          # [s_a, s_w, scratch, scratch]
-    for i, t in enumerate((a, w)):
-        c = t.shape[-1]
-        lib().f8_scale(t.data_ptr(), t.numel() // c if t.is_contiguous() else t.numel() // c, c,
-                       c if t.is_contiguous() else t.stride(-2), out[i:].data_ptr(), out[2 + i:].data_ptr(), _s())
-    return out
-
-
 class PreAct:
     """The output of a conv + train-mode BatchNorm + activation layer that was never materialised: ``y`` is the raw convolution
     output, the consumer forms act(scale*y + shift) where it loads its input (dcn_conv2d_fwd_pre / dcn_conv2d_bwd_weight_pre)."""
@@ -394,24 +384,11 @@ def conv2d_fwd(x, w_ohwi, ksize, stride, scale=None, shift=None, act=ACT_NONE, s
     amax_x / amax_w: abs-max words of the operands (computed here by a pass over the data when missing and the
     precision mode needs them); amax_out: word that receives the abs-max of what is stored.
     x may be a PreAct (pre_supported shapes, raw output only: no epilogue arguments); amax_x is then the word of the activation."""
-    if isinstance(x, PreAct):
-        if not (scale is None and shift is None and residual is None and act == ACT_NONE and not accumulate and amax_out is None
-                and amax_x is not None and amax_w is not None):
-            raise DcnError("conv2d_fwd: a PreAct input takes no epilogue and needs both abs-max words")
-        _chk(x.y, "conv2d_fwd x")
-        n, h, wd, cin = x.shape
-        cout = w_ohwi.shape[0]
-        ho, wo = conv_out_hw(h, wd, ksize, stride)
-        if out is None:
-            out = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
-        stats = None
-        if want_stats:
-            stats = torch.empty((lib().conv2d_stats_rows(n, h, wd, cout, ksize, stride), 2, cout), dtype=torch.float32, device=x.device)
-        lib().conv2d_fwd_pre(x.y.data_ptr(), w_ohwi.data_ptr(), out.data_ptr(), n, h, wd, cin, cout, ksize, stride,
-                             x.scale.data_ptr(), x.shift.data_ptr(), x.act, float(x.slope), out.stride(2), _p(stats),
-                             amax_x.data_ptr(), amax_w.data_ptr(), _s())
-        return out, stats
-    _chk(x, "conv2d_fwd x")
+    pre = isinstance(x, PreAct)
+    if pre and not (scale is None and shift is None and residual is None and act == ACT_NONE and not accumulate and amax_out is None
+                    and amax_x is not None and amax_w is not None):
+        raise DcnError("conv2d_fwd: a PreAct input takes no epilogue and needs both abs-max words")
+    _chk(x.y if pre else x, "conv2d_fwd x")
     n, h, wd, cin = x.shape
     cout = w_ohwi.shape[0]
     ho, wo = conv_out_hw(h, wd, ksize, stride)
@@ -422,7 +399,11 @@ def conv2d_fwd(x, w_ohwi, ksize, stride, scale=None, shift=None, act=ACT_NONE, s
     if want_stats:
         rows = lib().conv2d_stats_rows(n, h, wd, cout, ksize, stride)
         stats = torch.empty((rows, 2, cout), dtype=torch.float32, device=x.device)
-    f8 = None                        # (fp8 mode: the tiles derive their scales from the abs-max words below)
+    if pre:
+        lib().conv2d_fwd_pre(x.y.data_ptr(), w_ohwi.data_ptr(), out.data_ptr(), n, h, wd, cin, cout, ksize, stride,
+                             x.scale.data_ptr(), x.shift.data_ptr(), x.act, float(x.slope), ldy, _p(stats),
+                             amax_x.data_ptr(), amax_w.data_ptr(), _s())
+        return out, stats
     wsplit = None
     if cin != 4:
         amax_x = _amax_or_pass(x, amax_x); amax_w = _amax_or_pass(w_ohwi, amax_w)
@@ -437,7 +418,7 @@ def conv2d_fwd(x, w_ohwi, ksize, stride, scale=None, shift=None, act=ACT_NONE, s
         wsplit, ready = w_b16, 2                                          # the bank in bf16 (FilterBanks): the strip kernel's operand
     lib().conv2d_fwd(x.data_ptr(), w_ohwi.data_ptr(), out.data_ptr(), n, h, wd, cin, cout, ksize, stride,
                      _p(scale), _p(shift), act, float(slope), _p(residual),
-                     0 if residual is None else residual.stride(2), ldy, _p(stats), int(accumulate), _p(f8),
+                     0 if residual is None else residual.stride(2), ldy, _p(stats), int(accumulate), 0,            # (0: the ABI's unused fp8 scale pointer)
                      _p(amax_x), _p(amax_w), _p(amax_out), _p(wsplit), ready, _s())
     return out, stats
 
@@ -454,7 +435,6 @@ def conv2d_bwd_data(dy, w_ohwi, in_hw, ksize, stride, out=None, accumulate=False
     h, wd = in_hw
     if out is None:
         out = torch.empty((n, h, wd, cin), dtype=torch.float32, device=dy.device)
-    f8 = None
     amax_dy = _amax_or_pass(dy, amax_dy); amax_w = _amax_or_pass(w_ohwi, amax_w)
     if wt_ready is not None:
         wt, wts = wt_ready
@@ -472,13 +452,13 @@ def conv2d_bwd_data(dy, w_ohwi, in_hw, ksize, stride, out=None, accumulate=False
         part = torch.empty((max(cap, 1), 2, cin), dtype=torch.float32, device=dy.device)
         rows = ctypes.c_int(0)
         lib().conv2d_bwd_data_tap(dy.data_ptr(), dy.stride(2), w_ohwi.data_ptr(), wt.data_ptr(), out.data_ptr(),
-                                  n, h, wd, cin, cout, ksize, stride, int(accumulate), _p(f8), _p(amax_dy), _p(amax_w),
+                                  n, h, wd, cin, cout, ksize, stride, int(accumulate), 0, _p(amax_dy), _p(amax_w),
                                   ready, _p(wts), tap["y"].data_ptr() if cap else 0, tap["mean"].data_ptr(), tap["invstd"].data_ptr(),
                                   _p(tap.get("gamma")), _p(tap.get("beta")), int(tap["act"]), float(tap["slope"]),
                                   part.data_ptr() if cap else 0, cap, ctypes.addressof(rows), _s())
         return out, (part[:rows.value] if rows.value > 0 else None)
     lib().conv2d_bwd_data(dy.data_ptr(), dy.stride(2), w_ohwi.data_ptr(), wt.data_ptr(), out.data_ptr(),
-                          n, h, wd, cin, cout, ksize, stride, int(accumulate), _p(f8), _p(amax_dy), _p(amax_w),
+                          n, h, wd, cin, cout, ksize, stride, int(accumulate), 0, _p(amax_dy), _p(amax_w),
                           ready, _p(wts), _s())
     return out
 
@@ -810,7 +790,7 @@ WGRAD_AFTER_DGRAD = True    # the side stream also waits for the layer's DATA gr
                             # False = round 2's order; a lowest-priority side stream: +-0)
 
 
-WGRAD_HELD = True      # A/B switch (darknet._run_backward): a layer's weight gradient is LAUNCHED behind the next layer's BatchNorm passes (its
+WGRAD_HELD = True      # A/B switch (convblock.schedule_wgrad, the backbone): a layer's weight gradient is LAUNCHED behind the next layer's BatchNorm passes (its
                        # dependency stays the event recorded behind its own data gradient).  Same DAG; in a captured step the main chain
                        # then is the first dependent of every data gradient and the graph executor keeps it on ONE queue, the weight
                        # gradients on another (without it the main chain hops queues layer by layer and meets the weight-gradient queue —
@@ -835,12 +815,16 @@ class HeldWgrad:
         return _wgrad_side_launch(self.main, self.side, x, dy, ksize, stride, wshape, amax_x, amax_dy)
 
 
+def _wgrad_oihw(x, dy, ksize, stride, wshape, slot, amax_x, amax_dy):
+    dw = conv2d_bwd_weight(x, dy, ksize, stride, slot=slot, amax_x=amax_x, amax_dy=amax_dy)
+    if wshape[0] != dw.shape[0]:
+        dw = dw[:wshape[0]].contiguous()
+    return weight_grad_to_oihw(dw, wshape)
+
+
 def _wgrad_side_launch(main, side, x, dy, ksize, stride, wshape, amax_x, amax_dy):
     with torch.cuda.stream(side):
-        dw = conv2d_bwd_weight(x, dy, ksize, stride, slot=3, amax_x=amax_x, amax_dy=amax_dy)
-        if wshape[0] != dw.shape[0]:
-            dw = dw[:wshape[0]].contiguous()
-        out = weight_grad_to_oihw(dw, wshape)
+        out = _wgrad_oihw(x, dy, ksize, stride, wshape, 3, amax_x, amax_dy)
     for t in ((x.y, x.scale, x.shift) if isinstance(x, PreAct) else (x,)) + (dy,):
         t.record_stream(side)                    # keep the allocator from recycling them under the side kernels
     out.record_stream(main)
@@ -851,10 +835,7 @@ def wgrad_on_side(x, dy, ksize, stride, wshape, amax_x=None, amax_dy=None):
     """Launch the weight gradient (+ its OHWI->OIHW conversion) on the side stream.  Returns the OIHW
     gradient; the caller must make the main stream wait for side_stream() before the result is consumed."""
     if not WGRAD_SIDE:
-        dw = conv2d_bwd_weight(x, dy, ksize, stride, amax_x=amax_x, amax_dy=amax_dy)
-        if wshape[0] != dw.shape[0]:
-            dw = dw[:wshape[0]].contiguous()
-        return weight_grad_to_oihw(dw, wshape)
+        return _wgrad_oihw(x, dy, ksize, stride, wshape, 0, amax_x, amax_dy)
     main = torch.cuda.current_stream()
     side = side_stream(x.device)
     side.wait_stream(main)                       # dy (and x) are produced on the main stream

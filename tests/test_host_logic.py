@@ -375,6 +375,94 @@ def test_graph_queue_model_on_a_small_dag(tmp_path):
     assert sim2[3] == 0 and sim2[4] == 0 and sim2[5] == 0 and sim2[2] == 1
 
 
+def test_convblock_weight_gradient_schedules_and_tap_predicate(monkeypatch):
+    """dcnet_amd.convblock's host decisions, with the launches replaced by a log: the order of schedule_wgrad's policies (read from the
+    ops switches at call time), the two BatchNorm-tap conditions, the saved record's output links, the e4m3 reader count."""
+    from dcnet_amd import convblock, ops
+    log = []
+    monkeypatch.setattr(ops, "wgrad_on_side", lambda *a, **k: log.append("wgrad") or "dw")
+    monkeypatch.setattr(ops, "HeldWgrad", lambda *a, **k: log.append("held") or "held")
+    monkeypatch.setattr(ops, "hold_wgrad_into", lambda p, *a, **k: log.append("hold:" + p))
+    monkeypatch.setattr(ops, "release_held_wgrads", lambda: log.append("release"))
+
+    def order(**kw):
+        del log[:]
+        got = convblock.schedule_wgrad(None, None, 3, 1, (64, 32, 3, 3), lambda: log.append("dgrad") or "dx", **kw)
+        return got, list(log)
+
+    for name in ("WGRAD_SIDE", "WGRAD_AFTER_DGRAD", "WGRAD_HELD"):
+        monkeypatch.setattr(ops, name, True)
+    assert order() == (("dx", "dw"), ["dgrad", "wgrad"])
+    assert order(may_hold=True) == (("dx", "held"), ["dgrad", "held"])
+    assert order(after=False, may_hold=True) == (("dx", "dw"), ["wgrad", "dgrad"])
+    assert order(direct_into="p") == (("dx", None), ["release", "dgrad", "hold:p"])
+    monkeypatch.setattr(ops, "WGRAD_HELD", False)
+    assert order(may_hold=True) == (("dx", "dw"), ["dgrad", "wgrad"])
+    monkeypatch.setattr(ops, "WGRAD_HELD", True); monkeypatch.setattr(ops, "WGRAD_SIDE", False)
+    assert order(may_hold=True) == (("dx", "dw"), ["dgrad", "wgrad"])
+    monkeypatch.setattr(ops, "WGRAD_AFTER_DGRAD", False)
+    assert order(may_hold=True) == (("dx", "dw"), ["wgrad", "dgrad"])
+
+    y32, y16 = torch.zeros(1, 4, 4, 64), torch.zeros(1, 4, 4, 64, dtype=torch.bfloat16)
+    rec = lambda y: convblock.SavedLayer(None, y, None, None, None, None, mi=torch.zeros(4, 64))
+    tap = lambda b16, y, cin, k, s, training=True: convblock.bn_tap_for(b16, training, cin, k, s, rec(y), "g", "b", ops.ACT_LEAKY, 0.1) is not None
+    monkeypatch.setattr(ops, "BN_TAP", True)
+    for trunk, k1, k3 in ((True, True, True), (1, True, True), (2, False, True), (3, True, False), (False, False, False), (0, False, False)):
+        monkeypatch.setattr(ops, "BN_TAP_TRUNK", trunk)
+        assert (tap(False, y32, 64, 1, 1), tap(False, y32, 128, 3, 1)) == (k1, k3), trunk
+        assert tap(False, y32, 32, 3, 2) and not tap(False, y32, 32, 3, 1) and not tap(False, y32, 64, 3, 2)      # the layer behind the stem, whatever TRUNK says
+        assert tap(True, y16, 32, 3, 1) == tap(True, y16, 256, 1, 1) == bool(trunk) and not tap(True, y16, 32, 3, 2) and not tap(True, y32, 64, 1, 1)
+    monkeypatch.setattr(ops, "BN_TAP_TRUNK", True)
+    assert not tap(False, y32, 64, 1, 1, training=False) and not tap(False, y32[..., ::2], 64, 1, 1)
+    assert convblock.bn_tap_for(False, True, 64, 1, 1, None, "g", "b", ops.ACT_LEAKY, 0.1) is None
+    t = convblock.bn_tap_for(False, True, 64, 1, 1, rec(y32), "g", "b", ops.ACT_NONE, 0.1)
+    assert t["y"] is y32 and t["gamma"] == "g" and t["act"] == ops.ACT_NONE and t["mean"].shape == (64,)
+    monkeypatch.setattr(ops, "BN_TAP", False)
+    assert not tap(False, y32, 32, 3, 2) and not tap(True, y16, 64, 1, 1)
+
+    outs = [torch.zeros(1), torch.zeros(1)]
+    r = rec(y32); r.x = outs[1]
+    r.unlink_outputs(outs)
+    assert r.x == ("tap", 1)
+    r.link_outputs(outs)
+    assert r.x is outs[1]
+    left = {}
+    assert [convblock.last_q8_reader(left, 7, 3) for _ in range(3)] == [False, False, True] and convblock.last_q8_reader(left, 8, 1)
+
+
+def test_abi_trace_reduces_a_call_to_its_line():
+    """tools/abi_trace.py call_line: pointers become null / ptr whatever their address, the trailing stream handle its order of first
+    appearance, integers and floats are printed exactly (floats with repr) — so two processes that make the same calls write the same text."""
+    import ctypes
+    import importlib.util
+    import os
+    from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("abi_trace", os.path.join(root, "tools", "abi_trace.py"))
+    at = importlib.util.module_from_spec(spec); spec.loader.exec_module(at)
+    P, I, L, F = c_void_p, c_int, c_int64, c_float
+    streams = {}
+    sig = [P, P, I, L, F, P]
+    assert at.call_line("dcn_x", sig, (0x7f001000, 0, 3, 1 << 40, 0.1, 0xabc0), streams) == "dcn_x(ptr, null, 3, 1099511627776, 0.1, s0)"
+    assert at.call_line("dcn_x", sig, (0x7f002000, None, True, 7, 1e-5, 0xdef0), streams) == "dcn_x(ptr, null, 1, 7, 1e-05, s1)"
+    assert at.call_line("dcn_x", sig, (0x10, 0x20, -1, 0, 0.30000000000000004, 0xabc0), streams) == "dcn_x(ptr, ptr, -1, 0, 0.30000000000000004, s0)"
+    assert at.call_line("dcn_x", sig, (1, 1, 0, 0, 2.0, 0), streams) == "dcn_x(ptr, ptr, 0, 0, 2.0, s2)"          # the null stream is a stream
+    assert streams == {0xabc0: 0, 0xdef0: 1, 0: 2}
+    # the same calls with other addresses and other handles, in the same order: the same text
+    other = {}
+    assert at.call_line("dcn_x", sig, (0x5000, 0, 3, 1 << 40, 0.1, 0x111), other) == "dcn_x(ptr, null, 3, 1099511627776, 0.1, s0)"
+    # ctypes objects as they are passed by the wrappers: byref / addressof results, c_void_p, bytes
+    rows = ctypes.c_int(0)
+    assert at.call_line("dcn_y", [c_char_p, I, P, P, P], (b"precision", 4, ctypes.addressof(rows), ctypes.byref(rows), c_void_p(None)), {}) \
+        == "dcn_y(b'precision', 4, ptr, ptr, s0)"
+    # entry points without a stream (host-side samplers, profiler read-out) and value functions: the last pointer is a pointer
+    assert at.call_line("dcn_mt_sample_crossmodal", [P, I, I, I, P], (0x100, 2, 64, 5, 0x200), streams) == "dcn_mt_sample_crossmodal(ptr, 2, 64, 5, ptr)"
+    assert at.call_line("dcn_bn_ws", [I], (512,), streams) == "dcn_bn_ws(512)" and at.call_line("dcn_version", [], (), streams) == "dcn_version()"
+    assert len(streams) == 3
+    from dcnet_amd.lib import SIGNATURES
+    assert at.NO_STREAM <= set(SIGNATURES)
+
+
 def test_profiling_tags_are_named_and_not_shared_between_kernel_files():
     """Every literal tag a csrc file hands to prof_begin() has a name in bench.py, fits DCN_PROF_TAGS, and belongs to ONE file — two kernels
     of different files on one tag add their times and work up under the first one's name (round 5: conv2b and the bf16 strip kernel both
