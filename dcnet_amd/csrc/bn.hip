@@ -374,6 +374,12 @@ inline int pc_lg(int c) {
   while ((1 << lg) < c4) ++lg;
   return lg;
 }
+// the apply passes' form for c channels: log2(c / 4) = channel-per-thread kernel, -1 = grid-stride form (knob off, width, or a
+// per-channel vector that is not 16-byte aligned)
+inline int apply_form(int c, bool params_aligned) { return (g_bn_pc && params_aligned) ? pc_lg(c) : -1; }
+inline bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr, const void* e = nullptr) {
+  return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d | (uintptr_t)e) & 15) == 0;
+}
 inline int stream_grid(int64_t work_items) {
   int64_t b = (work_items + 255) / 256;
   return (int)(b < 1 ? 1 : (b > 4096 ? 4096 : b));
@@ -452,6 +458,12 @@ extern "C" int dcn_bn_act_amax_bound(const uint32_t* amax_y, const float* scale,
   return DCN_OK;
 }
 
+// Read-only: log2(c / 4) if dcn_scale_act / dcn_bn_act_bwd_apply run their channel-per-thread kernels for c channels under the current
+// knobs (params_aligned: the per-channel vectors are 16-byte aligned, which dcn_bn_act_bwd_apply asks for), -1 = the grid-stride forms
+extern "C" int dcn_bn_apply_form(int c, int params_aligned) {
+  return apply_form(c, params_aligned != 0);
+}
+
 extern "C" int dcn_scale_act(const float* y, const float* scale, const float* shift, int act, float slope,
                              const float* residual, float* out, int64_t rows, int c, int ldo, uint32_t* amax, void* stream) {
   DCN_CHECK_ARG(y && out && rows > 0 && c > 0 && c % 4 == 0, "scale_act: bad argument (c=%d must be a multiple of 4)", c);
@@ -460,7 +472,7 @@ extern "C" int dcn_scale_act(const float* y, const float* scale, const float* sh
   const int pid = prof_begin(10, (double)rows * c * 4.0 * (residual ? 3 : 2), (hipStream_t)stream);
   // (with an abs-max word: at most 1024 workgroups, i.e. 1024 atomics over 64 words; they all finish together)
   const int want = amax ? min(stream_grid(rows * (c / 4)), 1024) : stream_grid(rows * (c / 4));
-  const int lg = g_bn_pc ? pc_lg(c) : -1;
+  const int lg = apply_form(c, aligned16(scale, shift));
   if (lg >= 0) {
     const int64_t total = rows * (c / 4), nchunk = (total + 256 * PC_UNR - 1) / (256 * PC_UNR);
     hipLaunchKernelGGL(scale_act_pc_kernel, dim3((int)(nchunk < want ? nchunk : want)), dim3(256), 0, (hipStream_t)stream,
@@ -512,8 +524,7 @@ extern "C" int dcn_bn_act_bwd_apply(const float* y, const float* dout, int lddo,
   if (lddo <= 0) lddo = c;
   const int pid = prof_begin(11, (double)rows * c * 4.0 * 3, (hipStream_t)stream);
   const int want = amax ? min(stream_grid(rows * (c / 4)), 1024) : stream_grid(rows * (c / 4));
-  const int lg = (g_bn_pc && (((uintptr_t)mean | (uintptr_t)invstd | (uintptr_t)sums | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0)
-                     ? pc_lg(c) : -1;
+  const int lg = apply_form(c, aligned16(mean, invstd, sums, gamma, beta));
   if (lg >= 0) {
     const int64_t total = rows * (c / 4), nchunk = (total + 256 * PC_UNR - 1) / (256 * PC_UNR);
     hipLaunchKernelGGL(bn_act_bwd_apply_pc_kernel, dim3((int)(nchunk < want ? nchunk : want)), dim3(256), 0, (hipStream_t)stream,

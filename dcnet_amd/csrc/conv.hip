@@ -233,10 +233,13 @@ int bwd_data_impl(const float* dy, int lddy, const float* w, float* wt, float* d
   // the kernels there are issue-bound, not waiting for dY): only where a class has at most 64 K rows (g_merge_classes = 2: always)
   const bool merged = stride == 2 && ksize == 3 && h >= 2 && wd >= 2 &&
                       (g_merge_classes == 2 || (g_merge_classes == 1 && (long long)n * ((h + 1) / 2) * ((wd + 1) / 2) <= 65536));
-  if (amax_dy && amax_w && igemm_will_presplit((long long)n * (stride == 1 ? h * wd : ((h + 1) / 2) * ((wd + 1) / 2)), cin,
+  if (amax_dy && amax_w && igemm_will_presplit((long long)n * (stride == 1 ? h * wd : (merged ? ((h + 1) / 2) * ((wd + 1) / 2) : (h / 2) * (wd / 2))), cin,
                                                stride == 1 ? T : (merged ? 4 : 1), cout)) {
-    // (stride 2: the four parity classes share one bank; as separate launches the smallest class, with 1 tap, decides for all
-    //  of them; merged, the launch is sized by its largest class: 4 taps)
+    // (stride 2: the four parity classes share one bank, so as separate launches the decision is the conservative combination of
+    //  them all: the FEWEST rows — the odd-odd class, (h/2) x (wd/2) pixels — with the FEWEST taps — 1, the even-even class.  On odd
+    //  maps the smallest class can fall below the 1024 rows a pre-split tile wants while the largest stays above, and igemm_launch
+    //  refuses a pre-split bank on such a launch.  With 1 tap a launch of <= 64 filters is never pre-split; above 64 only the rows
+    //  count.  Merged, the launch is sized by its largest class: 4 taps)
     const int64_t numel = (int64_t)cin * T * cout;
     if (wt_ready) {
       if (wt_split) { p.wt = wt_split; p.b_scale = wt_split + numel; }       // else: the tiles split the fp32 bank themselves

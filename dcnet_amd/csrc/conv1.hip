@@ -759,6 +759,16 @@ bool conv1_will_take(long long rows, int Co, int ntaps, int Ci) {
   return true;
 }
 
+// the tile conv1_launch / conv1b_launch would pick for a launch of these dimensions (dcn_conv1_tile): 10 * MI + NI, 0 = not on this kernel
+int conv1_tile_of(long long rows, int Co, int ntaps, int Ci, int stats, int gran, int storage16) {
+  if (storage16) return conv1b_shape((int)rows, Co);
+  if (!conv1_will_take(rows, Co, ntaps, Ci)) return 0;
+  static float one_word;                      // (conv1_shape only asks whether the launch writes BatchNorm partials)
+  IgemmParams p{};
+  p.M = (int)rows; p.Co = Co; p.ntaps = ntaps; p.Ci = Ci; p.stats = stats ? &one_word : nullptr;
+  return conv1_shape(p, gran);
+}
+
 // NT launches with a pre-split B bank and an abs-max word for A: 1x1 convolutions and their data gradients (plain GEMM rows), and
 // gathered multi-tap launches (stride-2 layers, parity classes of their data gradients, narrow 3x3 layers)
 bool conv1_applicable(const IgemmParams& p, int precision, int gran) {

@@ -343,6 +343,11 @@ int launch3g(const G3Params& p, int grid, hipStream_t stream) {
 
 }  // namespace
 
+// the schedule variant a launch runs: 0, 1 or 2.  The kernel's K loop only knows these three — with any other number it would never
+// issue the B pieces again and multiply stale LDS — so whatever else the knob's upper bits hold runs as variant 0.
+int gemm3_variant() { const int v = g_gemm3 >> 8; return (v == 1 || v == 2) ? v : 0; }
+extern "C" int dcn_gemm3_variant() { return gemm3_variant(); }
+
 // shapes the kernel takes: rows of 16-byte granularity everywhere, the T operands' tile columns inside their rows
 bool gemm3_applicable(int M, int N, int K, int batch) {
   // (precision 2, the bf16 modes: the co-attention keeps its fp32-accurate f16 split — its operands are fp32 tensors either way, and
@@ -376,7 +381,7 @@ int gemm3_launch(const float* A, int lda, long long a_bs, int at, const float* B
   p.a_cols = at ? (M + 7) / 8 * 8 : k16; p.b_cols = bt ? (N + 7) / 8 * 8 : k16;
   DCN_CHECK_ARG(p.a_cols <= lda && p.b_cols <= ldb, "gemm3: rows shorter than the tile reads (lda=%d ldb=%d)", lda, ldb);
   p.tiles_m = cdiv(M, G3_BM); p.tiles_n = cdiv(N, G3_BN);
-  p.row_scale = row_scale; p.rs_bs = rs_bs; p.accumulate = accumulate; p.amax_a = amax_a; p.amax_b = amax_b; p.amax_out = amax_out; p.abl = (g_gemm3 >> 4) & 15; p.var = g_gemm3 >> 8;
+  p.row_scale = row_scale; p.rs_bs = rs_bs; p.accumulate = accumulate; p.amax_a = amax_a; p.amax_b = amax_b; p.amax_out = amax_out; p.abl = (g_gemm3 >> 4) & 15; p.var = gemm3_variant();
   const int grid = p.tiles_m * p.tiles_n * batch;
   const int pid = prof_begin(40, 2.0 * batch * (double)M * N * K, stream);
   int rc;

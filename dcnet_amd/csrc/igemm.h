@@ -84,6 +84,7 @@ int conv3b_launch(const IgemmParams& p, int out_f32, hipStream_t stream);
 // classes of their data gradients, narrow 3x3 layers.  gran = output rows per BatchNorm partial row (128 | 256).
 bool conv1_applicable(const IgemmParams& p, int precision, int gran);
 int conv1_launch(const IgemmParams& p, int gran, hipStream_t stream);
+int conv1_tile_of(long long rows, int Co, int ntaps, int Ci, int stats, int gran, int storage16);
 // ... and its bf16-storage form (activations, gradients and filter banks bf16 in HBM): every forward / data-gradient launch with
 // Ci % 32 == 0.  conv1b_grid_m = BatchNorm partial rows (M-tiles) of a launch.
 int conv1b_grid_m(int M, int Co, int ntaps, int s1_w = 0);      // s1_w: map width when the launch is a 3x3 stride-1 convolution, else 0

@@ -661,6 +661,11 @@ DCN_KNOB(g_h2_narrow, "rnarrow", 0, "igemm.hip: 1 = the narrow NT tiles (128x64,
 DCN_KNOB(g_h2_bk, "qbk", 16, "igemm.hip: K-step of the f16-split tiles without a pre-split bank (16 | 32)");
 DCN_KNOB(g_h2_presplit, "ypresplit", 1, "igemm.hip: filter banks pre-split once per step (0 = inside every workgroup)");
 
+// which build of a split tile a launch takes, 10 * K-step + waves per SIMD: the f16 split WITHOUT a pre-split bank ("qbk", "h2occ") and the
+// three-piece bf16 split ("occ3": the 3-wave build for launches of <= n K-steps), on the 128 x 128 tile or another one
+inline int h2_free_build(bool t128) { return g_h2_bk == 32 ? 322 : ((t128 && g_h2_occ3) ? 163 : 162); }
+inline int split3_build(bool t128, int ksteps) { return (t128 && ksteps <= g_occ3) ? 163 : 161; }
+
 template <int BM, int BN, int WM, int WN, int BMODE, bool C4 = false>
 int launch_variant(const IgemmParams& p, hipStream_t stream) {
   const long long rows = (long long)p.M * (p.batch > 0 ? p.batch : 1);       // batched GEMMs fill the chip like one long M
@@ -684,9 +689,11 @@ int launch_variant(const IgemmParams& p, hipStream_t stream) {
       }
 #endif
       if (p.b_scale) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 2, 1, false, true>(p, stream);    // pre-split filter bank
-      if (g_h2_bk == 32) return launch_bk<BM, BN, WM, WN, BMODE, C4, 32, true, 0, 2>(p, stream);
-      if (BM == 128 && BN == 128 && g_h2_occ3) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 2, 3>(p, stream);
-      return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 2>(p, stream);
+      switch (h2_free_build(BM == 128 && BN == 128)) {
+        case 322: return launch_bk<BM, BN, WM, WN, BMODE, C4, 32, true, 0, 2>(p, stream);
+        case 163: if constexpr (BM == 128 && BN == 128) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 2, 3>(p, stream);
+        default: return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 2>(p, stream);
+      }
     }
     if (g_precision >= 2 && g_precision <= 3 && ((BM == 128 && BN == 128) || (BM == 256 && BN == 64)) && rows >= 1024)
       return launch_bk<BM, BN, WM, WN, BMODE, C4, 32, true, 0, 1>(p, stream);     // bf16 operands: 8 MFMAs per 32-wide K-step
@@ -696,8 +703,9 @@ int launch_variant(const IgemmParams& p, hipStream_t stream) {
       if (g_abl == 1) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 1>(p, stream);   // ablation: no split arithmetic (wrong results)
       if (g_abl == 2) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 2>(p, stream);   // ablation: 1 of 6 MFMA groups (wrong results)
 #endif
-      if (BM == 128 && BN == 128 && (p.c4 ? 4 : p.ntaps * (p.Ci / 16)) <= g_occ3)     // (256x64 tile: 10-25 % slower at 3)
-        return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 3, 3>(p, stream);
+      if constexpr (BM == 128 && BN == 128) {                                         // (256x64 tile: 10-25 % slower at 3)
+        if (split3_build(true, p.c4 ? 4 : p.ntaps * (p.Ci / 16)) == 163) return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true, 0, 3, 3>(p, stream);
+      }
       return launch_bk<BM, BN, WM, WN, BMODE, C4, 16, true>(p, stream);
     }
   }
@@ -741,6 +749,23 @@ bool igemm_will_presplit(long long rows, int Co, int ntaps, int Ci) {
   if (g_precision != 4 || !g_h2_presplit || g_split || rows < 1024 || Co <= 32) return false;
   if (Co <= 64) return tile_bm((int)rows, Co, ntaps, Ci) == 256;       // the 256x64 split tile
   return tile_bm((int)rows, Co, ntaps, Ci) == 128;                     // the 128x128 tile
+}
+
+// Read-only: which conv1.hip tile (10 * MI + NI: 14 = 128 x 128, 18 = 128 x 256, 12 / 22 / 21 the narrow ones) a gathered NT launch of
+// `rows` output rows, `cout` filters, `ntaps` taps of `cin` channels takes under the current knobs; 0 = another kernel runs it.
+// storage = 0: fp32 tensors (the launch must be one that carries a pre-split bank: 1x1 layers, stride-2 layers, parity classes of their
+// data gradients); 1: the bf16- / fp8-storage tiles (launches that conv2b.hip / the strip kernel do not take first).
+extern "C" int dcn_conv1_tile(int64_t rows, int cout, int ntaps, int cin, int stats, int storage) {
+  if (rows <= 0 || rows > 0x7FFFFFFF || cout <= 0 || cin <= 0 || ntaps < 1) return 0;
+  if (storage) return conv1_tile_of(rows, cout, ntaps, cin, stats, 0, 1);
+  if (g_precision != 4 || !igemm_will_presplit(rows, cout, ntaps, cin)) return 0;
+  return conv1_tile_of(rows, cout, ntaps, cin, stats, tile_bm((int)rows, cout, ntaps, 32), 0);
+}
+
+// Read-only: the build of a 128 x 128 split tile under the current knobs, 10 * K-step + waves per SIMD.  kind 0: the f16 split of a launch
+// without a pre-split bank; kind 1: the three-piece bf16 split of a launch of `ksteps` 16-deep K-steps (taps x channels / 16).
+extern "C" int dcn_igemm_split_build(int kind, int ksteps) {
+  return kind == 0 ? h2_free_build(true) : split3_build(true, ksteps);
 }
 
 bool igemm_tap_capable(const IgemmParams& p) {

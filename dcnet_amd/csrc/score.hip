@@ -94,12 +94,16 @@ __global__ __launch_bounds__(256) void l2norm_score_fwd_kernel(const float* __re
 DCN_KNOB(g_l2_rpw, "e2rpw", 2, "score.hip: rows per wave of l2norm_score_fwd (1 | 2 | 4 | 8; tools/bench_score.py)");
 DCN_KNOB(g_l2_nt, "f2nt", 1, "score.hip: non-temporal loads of x in l2norm_score_fwd (0 | 1)");
 
+// rows per wave of a launch with V4 16-byte loads per lane and row (8 rows x 1024 channels: 128 data registers -> 4)
+inline int l2_rows_per_wave(int v4) { const int r = (g_l2_rpw == 8 && v4 > 2) ? 4 : g_l2_rpw; return (r == 1 || r == 2 || r == 8) ? r : 4; }
+inline int l2_v4(int c) { return c <= 256 ? 1 : (c <= 512 ? 2 : 4); }
+
 template <int V4>
 void launch_l2fwd(const float* x, int ldx, float* out, int ldo, float* norm, const float* q, float* score, float* score_flip,
                   int64_t rows, int rpi, int c, float out_scale, int accumulate, hipStream_t stream) {
 #define L2F(R, N) hipLaunchKernelGGL((l2norm_score_fwd_kernel<V4, R, N>), dim3(cdiv(rows, 4 * R)), dim3(256), 0, stream, \
                                      x, ldx, out, ldo, norm, q, score, score_flip, rows, rpi, c, out_scale, accumulate)
-  const int r = (g_l2_rpw == 8 && V4 > 2) ? 4 : g_l2_rpw;          // (8 rows x 1024 channels: 128 data registers)
+  const int r = l2_rows_per_wave(V4);
   if (g_l2_nt) { if (r == 1) L2F(1, true); else if (r == 2) L2F(2, true); else if (r == 8) L2F(8, true); else L2F(4, true); }
   else { if (r == 1) L2F(1, false); else if (r == 2) L2F(2, false); else if (r == 8) L2F(8, false); else L2F(4, false); }
 #undef L2F
@@ -200,6 +204,12 @@ __global__ __launch_bounds__(256) void rowdot_bwd_kernel(const float* __restrict
 
 }  // namespace
 
+// Read-only: the instantiation dcn_l2norm_score_fwd launches for c channels under the current knobs: 10 * rows per wave + non-temporal
+extern "C" int dcn_l2norm_score_fwd_form(int c) {
+  if (c <= 0 || c % 4 != 0 || c > 256 * MAX_V4) return 0;
+  return 10 * l2_rows_per_wave(l2_v4(c)) + (g_l2_nt ? 1 : 0);
+}
+
 extern "C" int dcn_l2norm_score_fwd(const float* x, int ldx, float* out, int ldo, float* norm,
                                     const float* q, float* score, float* score_flip, int64_t rows, int rows_per_image, int c,
                                     float out_scale, int accumulate, void* stream) {
@@ -211,8 +221,9 @@ extern "C" int dcn_l2norm_score_fwd(const float* x, int ldx, float* out, int ldo
   // algorithmic bytes: read x, write out (+ norm, score)
   const int pid = prof_begin(8, (double)rows * (2.0 * c * 4 + 8), (hipStream_t)stream);
   const int rpi_ = rows_per_image > 0 ? rows_per_image : 1;
-  if (c <= 256) launch_l2fwd<1>(x, ldx, out, ldo, norm, q, score, score_flip, rows, rpi_, c, out_scale, accumulate, (hipStream_t)stream);
-  else if (c <= 512) launch_l2fwd<2>(x, ldx, out, ldo, norm, q, score, score_flip, rows, rpi_, c, out_scale, accumulate, (hipStream_t)stream);
+  const int v4 = l2_v4(c);
+  if (v4 == 1) launch_l2fwd<1>(x, ldx, out, ldo, norm, q, score, score_flip, rows, rpi_, c, out_scale, accumulate, (hipStream_t)stream);
+  else if (v4 == 2) launch_l2fwd<2>(x, ldx, out, ldo, norm, q, score, score_flip, rows, rpi_, c, out_scale, accumulate, (hipStream_t)stream);
   else launch_l2fwd<4>(x, ldx, out, ldo, norm, q, score, score_flip, rows, rpi_, c, out_scale, accumulate, (hipStream_t)stream);
   prof_end(pid, (hipStream_t)stream);
   DCN_CHECK_LAUNCH("l2norm_score_fwd");

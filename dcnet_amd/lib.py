@@ -26,6 +26,11 @@ SIGNATURES = {
     "dcn_absmax": (I, [P, L, I, I, P, P]),
     "dcn_f8_scale": (I, [P, L, I, I, P, P, P]),
     "dcn_conv2d_stats_rows": (I, [I, I, I, I, I, I]),
+    "dcn_conv1_tile": (I, [L, I, I, I, I, I]),
+    "dcn_l2norm_score_fwd_form": (I, [I]),
+    "dcn_bn_apply_form": (I, [I, I]),
+    "dcn_igemm_split_build": (I, [I, I]),
+    "dcn_gemm3_variant": (I, []),
     "dcn_conv2d_bwd_data": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, P, P, P, I, P, P]),
     "dcn_conv2d_bwd_data_tap": (I, [P, I, P, P, P, I, I, I, I, I, I, I, I, P, P, P, I, P, P, P, P, P, P, I, F, P, I, P, P]),
     "dcn_conv2d_bwd_data_tap_rows": (I, [I, I, I, I, I, I, I]),
@@ -164,8 +169,9 @@ SIGNATURES = {
 }
 _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap_rows", "dcn_conv2d_pre_supported",
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",
-                "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes"}
-ABI_VERSION = 311        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
+                "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes",
+                "dcn_conv1_tile", "dcn_l2norm_score_fwd_form", "dcn_bn_apply_form", "dcn_igemm_split_build", "dcn_gemm3_variant"}
+ABI_VERSION = 312        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
 
 
 class DcnError(RuntimeError):

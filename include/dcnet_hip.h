@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 311
+#define DCN_ABI_VERSION 312
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -92,6 +92,19 @@ int dcn_conv2d_fwd(const float* x, const float* w, float* y,
  * a word the caller zeroed once. */
 int dcn_absmax(const float* x, int64_t rows, int c, int ld, uint32_t* amax, void* stream);
 int dcn_conv2d_stats_rows(int n, int h, int wd, int cout, int ksize, int stride);
+/* Read-only dispatch queries (ABI 312): what the library would launch under the current dcn_set_tuning knobs, for tests and A/B tools
+ * that must know which arm a timing or a result belongs to.  dcn_conv1_tile: the LDS-DMA tile of a gathered launch (rows output rows,
+ * cout filters, ntaps taps of cin channels; stats != 0: with BatchNorm partials; storage 0 fp32 | 1 bf16 / fp8) as 10 * MI + NI
+ * (14 = 128 x 128, 18 = 128 x 256), 0 = another kernel.  dcn_l2norm_score_fwd_form: 10 * rows per wave + non-temporal loads.
+ * dcn_bn_apply_form: log2(c / 4) of the channel-per-thread apply kernels, -1 = grid-stride forms. */
+int dcn_conv1_tile(int64_t rows, int cout, int ntaps, int cin, int stats, int storage);
+int dcn_l2norm_score_fwd_form(int c);
+int dcn_bn_apply_form(int c, int params_aligned);
+/* dcn_igemm_split_build: the build of a 128 x 128 split tile as 10 * K-step + waves per SIMD; kind 0 the f16 split without a pre-split
+ * bank, kind 1 the three-piece bf16 split of a launch of ksteps 16-deep K-steps.  dcn_gemm3_variant: the schedule variant (0 | 1 | 2)
+ * dcn_gemm3 launches run; any other number in the knob's upper bits runs as 0. */
+int dcn_igemm_split_build(int kind, int ksteps);
+int dcn_gemm3_variant(void);
 /* f8_scales (dcn_conv2d_fwd / dcn_conv2d_bwd_data; NULL = off): device pointer to {s_activation, s_weight}, the
  * power-of-two operand scales of the builder-defined fp8 e4m3 conv path (BASELINE.json configs[4]): the wide tiles
  * round s*x to fp8, multiply with v_mfma_f32_32x32x16_fp8_fp8, accumulate in fp32 and rescale.  dcn_f8_scale writes

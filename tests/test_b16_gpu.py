@@ -6,14 +6,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from util import tuning
+from util import rand as _rand, tuning
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
 
 
 def _bf(t):

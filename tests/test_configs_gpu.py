@@ -5,8 +5,9 @@ and the reference has no reduced-precision semantics, so the te
   * every output and gradient is finite and a whole step (forward, five losses, backward) is bitwise repeatable;
   * at this very batch size the kernels agree with the mode's EXACT MODEL — the same convolution on operands that were
     rounded beforehand (bf16 nearest-even / scaled e4m3), evaluated by the fp32-exact split pipe, which
-    tests/test_ops_gpu.py pins against fp64 — forward, data gradient and weight gradient, on the layer shapes that carry
-    most of the step;
+    tests/test_fullsize_layers_gpu.py pins against fp64 at these very shapes and batches (tests/test_ops_gpu.py does so at
+    small launches only, which take other tiles) — forward, data gradient and weight gradient, on the layer shapes that
+    carry most of the step;
   * bf16, eval mode: a clip taken out of the batch and run alone sees the same per-element operand rounding, so it must
     agree with its slice of the full batch far better than the mode differs from fp32.
 """
@@ -106,7 +107,7 @@ def test_reduced_precision_config_at_full_workload(dev, mode, n_img):
 def test_bf16_storage_config_at_full_workload(dev):
     """configs[2] proper — bf16 STORAGE (``ops.set_precision("bf16s")``) — at its workload: 64 images of 416x416 through a full training step.
     Layer level at this batch size: the bf16-tensor kernels (conv1b / conv2b tiles, bf16 weight gradient) against their exact model — the same
-    convolution in the fp32-exact split pipe on the bf16 values, which tests/test_ops_gpu.py pins against fp64 — on the layer shapes that
+    convolution in the fp32-exact split pipe on the bf16 values, which tests/test_fullsize_layers_gpu.py pins against fp64 at this batch — on the layer shapes that
     carry most of the step; then the whole step: finite, bitwise repeatable, and in
     eval mode a clip run alone agrees with its slice of the full batch far better than the mode differs from fp32."""
     from dcnet_amd import ops

@@ -5,22 +5,9 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from util import tuning
+from util import close as _close, prof_launches as _prof_launches, rand as _rand, tuning
 
 pytestmark = pytest.mark.gpu
-
-
-def _rand(*shape, seed=0, scale=1.0):
-    g = torch.Generator().manual_seed(seed)
-    return torch.randn(*shape, generator=g) * scale
-
-
-def _close(a, b, tol, name=""):
-    a = a.detach().cpu().double(); b = b.detach().cpu().double()
-    assert a.shape == b.shape, (name, a.shape, b.shape)
-    ref = max(1.0, float(b.abs().max()))
-    err = float((a - b).abs().max())
-    assert err <= tol * ref, f"{name}: max err {err:.3e} vs tol {tol * ref:.3e}"
 
 
 def _nhwc(x):
@@ -1387,15 +1374,6 @@ def test_k9_bwd_match_lists(dev, case):
         want[2 * p + 1].index_add_(0, neg_idx[p].reshape(-1), d_neg[p].reshape(-1, e).double())
     _close(got, want, 1e-5, "k9_bwd")
     assert torch.equal(got, ops.k9_bwd(index.to(dev), neg_idx.to(dev), d_frame.to(dev), d_corr.to(dev), d_neg.to(dev), hw))
-
-
-def _prof_launches(tag):
-    """launches booked under a profiling tag since dcn_prof_enable(1) (csrc/prof.h)"""
-    import ctypes
-    from dcnet_amd.lib import lib
-    c = (ctypes.c_int64 * 64)(); m = (ctypes.c_double * 64)(); wk = (ctypes.c_double * 64)()
-    lib().prof_collect(ctypes.addressof(c), ctypes.addressof(m), ctypes.addressof(wk), 0)
-    return c[tag]
 
 
 W9_CASES = [

@@ -32,6 +32,62 @@ def test_every_knob_round_trips_and_the_readme_table_lists_them_all():
     assert {n: int(d) for n, d in rows} == {k: v["default"] for k, v in knobs.items()}
 
 
+def _listed_values(desc):
+    """the values a knob's description names: "N = meaning", "a | b | c" lists and "(0 fp32 MFMA, 1 bf16 split, ...)" enumerations;
+    "<= 0 = default" is a setter normalisation, not an arm"""
+    desc = re.sub(r"[<>]=?\s*-?\d+\s*=", "", desc)
+    vals = {int(v) for v in re.findall(r"(?<![\w.*])(-?\d+) =", desc)}
+    for lst in re.findall(r"-?\d+(?: \| -?\d+)+", desc):
+        vals |= {int(v) for v in lst.split(" | ")}
+    for lst in re.findall(r"\((\d+ [a-z][^()]*)\)", desc):
+        items = [re.match(r"(\d+) [a-zA-Z]", it.strip()) for it in lst.split(",")]
+        if len(items) > 1 and all(items):
+            vals |= {int(m.group(1)) for m in items}
+    return vals
+
+
+def test_every_knob_arm_has_a_test():
+    """Every ordinary knob of the registry is in tests/test_arms_gpu.py ARMS — with an entry for each non-default value its description
+    names — or in COVERED_BY, pointing at an existing test function whose source sets it; only the wrong-result switches of the ablation
+    builds are exempt.  A knob added without a test fails here, by name."""
+    import inspect
+    import importlib
+    from dcnet_amd.lib import tuning as read
+    import test_arms_gpu as A
+    knobs = read()
+    assert set(A.ARMS) | set(A.COVERED_BY) | set(A.EXEMPT) <= set(knobs), "the tables name knobs the registry does not have"
+    for knob, (which, flag) in A.EXEMPT.items():
+        assert flag.startswith("-D") and which, knob
+        assert knobs[knob]["ablation"] == 1 or knob in A.ARMS or knob in A.COVERED_BY, f"{knob}: only its wrong-result values are exempt"
+    missing = [k for k, v in knobs.items() if v["ablation"] == 0 and k not in A.ARMS and k not in A.COVERED_BY]
+    assert not missing, f"knobs without a test of their arms: {missing} (tests/test_arms_gpu.py ARMS / COVERED_BY)"
+    for knob, v in knobs.items():
+        if v["ablation"] != 0 and knob not in A.ARMS and knob not in A.COVERED_BY:
+            assert knob in A.EXEMPT, f"{knob}: an ablation-only switch must be listed in EXEMPT with its compile flag"
+    for knob, arms in A.ARMS.items():
+        assert arms, knob
+        set_to = set()
+        for values, workload, evidence in arms:
+            assert knob in values and workload[0] in A.WORKLOADS and evidence[0], (knob, values)
+            set_to.add(values[knob])
+        want = _listed_values(knobs[knob]["desc"]) - {knobs[knob]["default"]}
+        assert want <= set_to, f"{knob}: no ARMS entry for the value(s) {sorted(want - set_to)} its description lists"
+        assert set_to - {knobs[knob]["default"]}, f"{knob}: no entry sets it to anything but its default"
+    for knob, where in A.COVERED_BY.items():
+        mod = importlib.import_module(where[0])
+        fn = getattr(mod, where[1], None)
+        assert callable(fn) and where[1].startswith("test_"), f"{knob}: {where[0]}.{where[1]} is not a test function"
+        src = inspect.getsource(fn)
+        if len(where) > 2:
+            assert where[2] + "(" in src, f"{knob}: {where[1]} does not call {where[2]}"
+            src = inspect.getsource(getattr(mod, where[2]))
+        assert f'"{knob}"' in src, f"{knob}: the source of {'.'.join(where)} does not mention it"
+    # no case of the arm tests may be skipped or expected to fail
+    src = inspect.getsource(A)
+    for banned in ("pytest.skip", "mark.skip", "skipif", "xfail", "importorskip"):
+        assert banned not in src, f"tests/test_arms_gpu.py uses {banned}"
+
+
 @pytest.mark.parametrize("key", ["wide", "bpc", "precison", "1", "3x3", "9targ", "quiet", "", "Precision", "precision "])
 def test_keys_are_matched_whole(key):
     from dcnet_amd.lib import DcnError, lib, tuning as read

@@ -29,14 +29,19 @@ def synth_sd(size=256, seed=0):
     return apply_bn_calibration(synth_state_dict(ref_shapes(size), seed), os.path.join(GOLD, "bn_calib.npz"))
 
 
-def build_product(size, sd, dev, test_model=False):
+def new_product(size, test_model=False):
+    """The drop-in grounding model as the reference's scripts construct it, parameters as initialised (no state dict)."""
     if test_model:
         from model.test_DCNet_model import grounding_model
     else:
         from model.DCNet_model import grounding_model
-    m = grounding_model(corpus=list(range(1000)), light=False, emb_size=512, coordmap=True,
-                        bert_model="bert-base-uncased", dataset="vid", img_size=size,
-                        config_path=os.path.join(ROOT, "model", "yolov3.cfg"), weights_path=None)
+    return grounding_model(corpus=list(range(1000)), light=False, emb_size=512, coordmap=True,
+                           bert_model="bert-base-uncased", dataset="vid", img_size=size,
+                           config_path=os.path.join(ROOT, "model", "yolov3.cfg"), weights_path=None)
+
+
+def build_product(size, sd, dev, test_model=False):
+    m = new_product(size, test_model)
     m.load_state_dict(sd, strict=True)
     for mod in m.modules():
         if isinstance(mod, torch.nn.Dropout):
@@ -65,3 +70,71 @@ def tuning(knobs=None):
     finally:
         for _ in range(2):          # ("precision" drives "wsplit" as well: the second pass puts back what the first pass's setters moved)
             tune({k: before[k] for k, v in read().items() if v["value"] != before[k]})
+
+
+def rand(*shape, seed=0, scale=1.0):
+    g = torch.Generator().manual_seed(seed)
+    return torch.randn(*shape, generator=g) * scale
+
+
+def close(a, b, tol, name=""):
+    """max |a - b| <= tol * max(1, |b|max) in fp64; the operands may live on different devices"""
+    a = a.detach().double(); b = b.detach().double().to(a.device)
+    assert a.shape == b.shape, (name, a.shape, b.shape)
+    ref = max(1.0, float(b.abs().max()))
+    err = float((a - b).abs().max())
+    assert err <= tol * ref, f"{name}: max err {err:.3e} vs tol {tol * ref:.3e}"
+
+
+def prof_launches(tag=None):
+    """launches booked under a profiling tag (all 64 tags as a list without one) since dcn_prof_enable(1) (csrc/prof.h)"""
+    import ctypes
+    from dcnet_amd.lib import lib
+    c = (ctypes.c_int64 * 64)(); m = (ctypes.c_double * 64)(); wk = (ctypes.c_double * 64)()
+    lib().prof_collect(ctypes.addressof(c), ctypes.addressof(m), ctypes.addressof(wk), 0)
+    return list(c) if tag is None else c[tag]
+
+
+def prof_counts(fn):
+    """(fn(), launches per profiling tag while it ran)"""
+    from dcnet_amd.lib import lib
+    lib().prof_enable(1)
+    try:
+        out = fn()
+    finally:
+        lib().prof_enable(0)
+    return out, prof_launches()
+
+
+def conv_by_taps(x, w, k, stride, dy=None, dtype=torch.float64, chunk=None):
+    """Reference convolution that shares nothing with the library: x (N,H,W,Ci) and w (Co,k,k,Ci) NHWC / OHWI on any device,
+    'same' padding (k - 1) // 2, evaluated in ``dtype`` by torch.matmul one tap at a time on shifted slices of the padded input.
+    Returns y (N,Ho,Wo,Co) and, with dy (N,Ho,Wo,Co), dx (N,H,W,Ci) and dw (Co,k,k,Ci); with ``chunk`` (a slice of output-pixel
+    rows) also the part of dw those rows contribute (what zeroing them in the input would remove)."""
+    n, h, wd, ci = x.shape
+    co = w.shape[0]
+    pad = (k - 1) // 2
+    ho, wo = (h + 2 * pad - k) // stride + 1, (wd + 2 * pad - k) // stride + 1
+    xp = torch.nn.functional.pad(x.to(dtype), (0, 0, pad, pad, pad, pad))
+    wt = w.to(dtype)
+    y = torch.zeros(n * ho * wo, co, dtype=dtype, device=x.device)
+    dyf = None if dy is None else dy.to(dtype).reshape(-1, co)
+    dxp = None if dy is None else torch.zeros_like(xp)
+    dw = None if dy is None else torch.zeros(co, k, k, ci, dtype=dtype, device=x.device)
+    dwc = None if (dy is None or chunk is None) else torch.zeros_like(dw)
+    for r in range(k):
+        for s in range(k):
+            sl = (slice(None), slice(r, r + stride * (ho - 1) + 1, stride), slice(s, s + stride * (wo - 1) + 1, stride))
+            xs = xp[sl].reshape(-1, ci)
+            y += xs @ wt[:, r, s, :].t()
+            if dy is not None:
+                dxp[sl] += (dyf @ wt[:, r, s, :]).view(n, ho, wo, ci)
+                dw[:, r, s, :] = dyf.t() @ xs
+                if dwc is not None:
+                    dwc[:, r, s, :] = dyf[chunk].t() @ xs[chunk]
+            del xs
+    y = y.view(n, ho, wo, co)
+    if dy is None:
+        return y
+    dx = dxp[:, pad:pad + h, pad:pad + wd, :]
+    return (y, dx, dw) if dwc is None else (y, dx, dw, dwc)
