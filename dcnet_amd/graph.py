@@ -1,17 +1,17 @@
 """A training step of the hot path as ONE replayed hipGraph.
 
-The reference's step is a Python loop body (train_DCNet.py:580-646: forward, five losses, ``backward()``, RMSprop).  Eagerly
+The reference's step is a Python loop body (train_DCNet.py:580-646: forward, five losses, ``backward()``, the optimiser).  Eagerly
 that is ~1 300 kernel launches per step from one Python thread, which keeps that thread busy for most of the step's GPU time.
 ``GraphedTrainStep`` captures the same launches once — forward of ``grounding_model``, ``losses.total_loss``, autograd's
-backward (with the weight-gradient / language / sampling side streams as forked branches of the graph) and the fused RMSprop
-update — and replays them with one ``hipGraphLaunch`` per step.  What stays on the host per step:
+backward (with the weight-gradient / language / sampling side streams as forked branches of the graph) and the fused optimiser
+update (``dcnet_amd.optim``: RMSprop, Adam or SGD) — and replays them with one ``hipGraphLaunch`` per step.  What stays on the host per step:
 
   * the draws of the two sampling heads (Python's MT19937 stream must advance exactly as the reference's forward advances
     it): made natively on a worker thread, uploaded into static device buffers the captured kernels read
     (``grounding_model.draw_samples`` / ``static_samples``) — or, with ``grounding_model.sampler = "device"``, nothing: the draws
     are three captured kernels of a counter-based generator whose step counter lives on the device;
   * the learning rate of the schedule (train_DCNet.py:244-253): one device scalar per parameter group that the captured
-    RMSprop kernel reads (``optim.RMSprop.device_lr``);
+    optimiser kernel reads (``device_lr`` of the classes in ``dcnet_amd.optim``; Adam's step count lives on the device as well);
   * new input data: ``copy_`` into the static ``image`` / ``word_id`` / ``bbox`` tensors.
 
 Data-parallel runs capture forward + backward only; the gradient all-reduce (one flat RCCL all-reduce,

@@ -7,12 +7,12 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdcnet_hip.so")
 
-P, I, L, F = c_void_p, c_int, c_int64, c_float
+P, I, L, F, D = c_void_p, c_int, c_int64, c_float, c_double
 
 # name -> (restype, argtypes).  int-returning entries are status codes unless listed in _VALUE_FUNCS.
 SIGNATURES = {
@@ -119,6 +119,9 @@ SIGNATURES = {
     "dcn_bilstm_fwd": (I, [P, P, P, P, P, P, P, P, P, P, P, I, I, I, P]),
     "dcn_bilstm_bwd": (I, [P, P, P, P, P, P, P, P, I, I, I, P]),
     "dcn_rmsprop_step": (I, [P, P, P, P, I, F, P, F, F, F, P]),
+    "dcn_adam_prepare": (I, [P, P, I, F, P, D, D, P]),
+    "dcn_adam_step": (I, [P, P, P, P, P, P, I, D, D, F, F, P]),
+    "dcn_sgd_step": (I, [P, P, P, P, I, F, P, F, F, P]),
     "dcn_fusion_prefill": (I, [P, P, P, I, P, I, I, I, P]),
     "dcn_fusion_bwd_ws": (L, [I, I]),
     "dcn_fusion_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
@@ -171,7 +174,7 @@ _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",
                 "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes",
                 "dcn_conv1_tile", "dcn_l2norm_score_fwd_form", "dcn_bn_apply_form", "dcn_igemm_split_build", "dcn_gemm3_variant"}
-ABI_VERSION = 312        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
+ABI_VERSION = 313        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
 
 
 class DcnError(RuntimeError):

@@ -1,7 +1,7 @@
 """Training / evaluation harness around the hot path — the pieces of train_DCNet.py that a caller needs
 to drive ``grounding_model`` without the reference's data pipeline:
 
-  * ``make_optimizer``      RMSprop with the reference's two parameter groups (train_DCNet.py:519-534)
+  * ``make_optimizer``      RMSprop with the reference's two parameter groups, or its Adam / SGD (train_DCNet.py:519-534)
   * ``adjust_learning_rate`` polynomial decay (train_DCNet.py:241-253)
   * ``train_step``          forward + five losses + backward + step, no host sync inside
   * ``evaluate``            eval forward + box decode + Acc@0.5 / mean IoU (train_DCNet.py:764-816)
@@ -25,24 +25,29 @@ import torch
 from . import losses, ops
 
 
-def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop"):
-    """Two groups like the reference: everything except the backbone at ``lr``, the Darknet backbone at
-    ``lr / 10``; weight decay 5e-4 (train_DCNet.py:519-534).  ``model`` may be DDP-wrapped.
+def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: bool = True):
+    """The optimiser the reference builds for ``--optimizer`` (train_DCNet.py:519-534).  ``model`` may be DDP-wrapped.
 
-    Every parameter is listed, in ``model.parameters()`` order, whether or not it is trainable — the reference's
+    ``"RMSprop"`` (the default): two groups, everything except the backbone at ``lr``, the Darknet backbone at ``lr / 10``; weight
+    decay 5e-4.  ``"adam"``: one group over all parameters, weight decay 5e-4.  ``"sgd"``: one group, momentum 0.99.  All three are
+    the fused classes of ``dcnet_amd.optim`` (torch's update as one HIP pass, torch's ``state_dict`` layout, and the protocol
+    ``graph.GraphedTrainStep`` captures); ``fused=False`` returns the ``torch.optim`` classes for Adam and SGD instead.
+
+    Every parameter is listed, in ``model.parameters()`` order, whether or not it is trainable — the reference's RMSprop
     groups hold [93, 222] tensors including the dead YOLO heads and ``feature_map`` — so that the ``optimizer`` entry
     of a ``.pth.tar`` checkpoint moves between the reference and this harness in both directions even after
     ``parallel.freeze_gradless`` has run.  Parameters without a gradient are skipped by the step, as in torch."""
+    from . import optim
     core = model.module if hasattr(model, "module") else model
+    name = optimizer.lower()
+    if name == "adam":
+        return (optim.Adam if fused else torch.optim.Adam)(list(core.parameters()), lr=lr, weight_decay=0.0005)
+    if name == "sgd":
+        return (optim.SGD if fused else torch.optim.SGD)(list(core.parameters()), lr=lr, momentum=0.99)
     visu = list(core.visumodel.parameters())
     ids = {id(p) for p in visu}
     rest = [p for p in core.parameters() if id(p) not in ids]
-    if optimizer.lower() == "adam":
-        return torch.optim.Adam(list(core.parameters()), lr=lr, weight_decay=0.0005)
-    if optimizer.lower() == "sgd":
-        return torch.optim.SGD(list(core.parameters()), lr=lr, momentum=0.99)
-    from .optim import RMSprop          # torch.optim.RMSprop's update as one fused HIP pass (same state_dict layout)
-    return RMSprop([{"params": rest}, {"params": visu, "lr": lr / 10.}], lr=lr, weight_decay=0.0005)
+    return optim.RMSprop([{"params": rest}, {"params": visu, "lr": lr / 10.}], lr=lr, weight_decay=0.0005)
 
 
 def lr_poly(base_lr: float, it: int, max_iter: int, power: float) -> float:
@@ -136,6 +141,7 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     ap.add_argument("--frames", type=int, default=2)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--optimizer", choices=["rmsprop", "adam", "sgd"], default="rmsprop", help="train_DCNet.py's --optimizer")
     ap.add_argument("--raw-frames", action="store_true", help="feed uint8 frames through dcnet_amd.prep every step")
     args = ap.parse_args(argv)
     from .model import grounding_model
@@ -145,7 +151,7 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     torch.manual_seed(0); random.seed(0)
     model = grounding_model(corpus=list(range(1000)), emb_size=512, img_size=args.size, config_path="", weights_path=None).to(dev)
     freeze_gradless(model)
-    opt = make_optimizer(model, args.lr)
+    opt = make_optimizer(model, args.lr, args.optimizer)
     n = args.clips * args.frames
     image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, args.size, seed=1))
     bbox = synth_boxes(n, args.size, seed=1).to(dev)

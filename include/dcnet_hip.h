@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 312
+#define DCN_ABI_VERSION 313
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -693,6 +693,23 @@ int dcn_rmsprop_step(float* const* params, const float* const* grads, float* con
                      int count, float lr, const float* lr_dev /* device scalar that overrides lr when non-NULL: a step captured into a
                      hipGraph then follows the caller's learning-rate schedule (train_DCNet.py:244-253) without re-capture */,
                      float alpha, float eps, float weight_decay, void* stream);
+/* The driver's other two optimisers (train_DCNet.py:528-531), which it steps at train_DCNet.py:646 (ABI 313).
+ * dcn_adam_step replaces torch.optim.Adam(weight_decay=5e-4).step (amsgrad = False, maximize = False), in torch's order:
+ * g += weight_decay*p;  m += (g-m)*(1-beta1);  v = beta2*v + (1-beta2)*g*g;  p -= scal[0] * m/(sqrt(v)*scal[1] + eps)  with
+ * scal[0] = lr/(1-beta1^t), scal[1] = 1/sqrt(1-beta2^t).  The step count t lives on the device so that a step captured into a
+ * hipGraph advances it by itself: dcn_adam_prepare, called once in front of dcn_adam_step with one int32 step word and one
+ * two-float scalar slot per tensor (host arrays of device pointers), adds 1 to every step word and writes the tensor's two scalars
+ * from it, in double, with lr read from lr_dev when that is non-NULL (as dcn_rmsprop_step).  A tensor that sits a step out is left
+ * out of both calls and keeps its count (torch's rule for a parameter without a gradient). */
+int dcn_adam_prepare(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2, void* stream);
+int dcn_adam_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                  const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, float weight_decay,
+                  void* stream);
+/* dcn_sgd_step replaces torch.optim.SGD(momentum=0.99).step (train_DCNet.py:530-531; dampening = 0, nesterov = False):
+ * g += weight_decay*p;  buf = momentum*buf + g;  p -= lr*buf.  A zero-filled buffer makes the first step torch's buf = g.
+ * lr_dev as in dcn_rmsprop_step. */
+int dcn_sgd_step(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
+                 float lr, const float* lr_dev, float momentum, float weight_decay, void* stream);
 /* Keys: "precision" 4 (default): the wide tiles of the conv engine and of the weight-gradient GEMM run the f16 two-piece
  *         split (see dcn_absmax) wherever both operands carry their abs-max word, and as 1 otherwise;
  *         1: the bf16 matrix pipe with every fp32 operand cut into three bf16 pieces (exact) and the six cross terms

@@ -1,0 +1,147 @@
+"""The fused Adam / SGD steps (csrc/optim.hip) against torch's foreach steps, on the trained parameter shapes of the real model
+(synthetic weights, random gradients), alternating in one process:
+
+    python tools/bench_optim.py [--iters 20] [--warmup 3] [--step] [--json out.json]
+
+Per optimiser one JSON line: ms per step of ``torch.optim.{Adam,SGD}(foreach=True)`` and of ``dcnet_amd.optim.{Adam,SGD}`` (HIP events
+around ``step()`` on a warm, otherwise idle GPU; medians over --iters, the two sides measured in turns), the bytes a step has to move
+(Adam 16 B read + 12 B written per value, SGD 12 B + 8 B) and the fraction of the HBM peak the fused step reaches on them.
+
+``--step`` adds the whole training step at configs[1]'s geometry (8 clips x T 8 at 416x416): the eager ``train_step`` with
+``torch.optim.Adam`` — what Adam training had to run before the fused class could be captured — against the replayed hipGraph with
+the fused Adam (wall clock per step over --step-iters steps, host-synchronised at both ends).
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import random
+import statistics
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from dcnet_amd import optim            # noqa: E402
+
+HBM_PEAK = 8.0e12                      # MI355X HBM3E peak (MI355X_MICROARCH.md); ~6.3e12 achievable by a streaming copy
+BYTES_PER_VALUE = {"adam": 28, "sgd": 20}
+
+
+def build_model(size, dev):
+    from dcnet_amd.model import grounding_model
+    from dcnet_amd.parallel import freeze_gradless
+    torch.manual_seed(1234)
+    model = grounding_model(corpus=list(range(1000)), light=False, emb_size=512, coordmap=True, bert_model="bert-base-uncased",
+                            dataset="vid", img_size=size, config_path=os.path.join(ROOT, "model", "yolov3.cfg"), weights_path=None).to(dev)
+    model.train(); freeze_gradless(model)
+    return model
+
+
+def _make(name, params, fused):
+    if name == "adam":
+        return optim.Adam(params, lr=1e-4, weight_decay=5e-4) if fused else torch.optim.Adam(params, lr=1e-4, weight_decay=5e-4, foreach=True)
+    return optim.SGD(params, lr=1e-4, momentum=0.99) if fused else torch.optim.SGD(params, lr=1e-4, momentum=0.99, foreach=True)
+
+
+def _timed(fn):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record(); fn(); b.record()
+    b.synchronize()
+    return a.elapsed_time(b)
+
+
+def bench_steps(name, shapes, dev, iters, warmup):
+    g = torch.Generator(device=dev).manual_seed(0)
+    sides = {}
+    for fused in (False, True):
+        ps = [torch.nn.Parameter(torch.randn(s, device=dev, generator=g) * 0.05) for s in shapes]
+        for p in ps:
+            p.grad = torch.randn(p.shape, device=dev, generator=g) * 1e-3
+        sides[fused] = _make(name, ps, fused)
+    for _ in range(warmup):
+        for o in sides.values():
+            o.step()
+    torch.cuda.synchronize()
+    ts = {False: [], True: []}
+    for _ in range(iters):
+        for fused, o in sides.items():
+            ts[fused].append(_timed(o.step))
+    n = sum(int(torch.Size(s).numel()) for s in shapes)
+    t_ms, f_ms = statistics.median(ts[False]), statistics.median(ts[True])
+    alg = n * BYTES_PER_VALUE[name]
+    return {"optimizer": name, "tensors": len(shapes), "values_M": round(n / 1e6, 2), "alg_GB": round(alg / 1e9, 3),
+            "torch_foreach_ms": round(t_ms, 4), "fused_ms": round(f_ms, 4), "speedup": round(t_ms / f_ms, 2),
+            "fused_TBps": round(alg / f_ms / 1e9, 3), "frac_hbm_peak": round(alg / f_ms / 1e9 / (HBM_PEAK / 1e12), 3)}
+
+
+def bench_train_step(dev, size, clips, iters, warmup):
+    from dcnet_amd.graph import GraphedTrainStep
+    from dcnet_amd.train import make_optimizer, train_step
+    from dcnet_amd.utils.synth import synth_boxes, synth_inputs
+    n = clips * 8
+    image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, size, seed=100))
+    bbox = synth_boxes(n, size, seed=100).to(dev)
+    out = {"geometry": f"{clips} clips x T 8 at {size}x{size}", "steps": iters}
+    random.seed(13)
+    model = build_model(size, dev)
+    opt = make_optimizer(model, 1e-4, "adam", fused=False)
+    for _ in range(warmup):
+        train_step(model, opt, image, word_id, word_mask, bbox, size)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        train_step(model, opt, image, word_id, word_mask, bbox, size)
+    torch.cuda.synchronize()
+    out["eager_torch_adam_ms"] = round((time.perf_counter() - t0) / iters * 1e3, 2)
+    del model, opt
+    torch.cuda.empty_cache()
+    random.seed(13)
+    model = build_model(size, dev)
+    step = GraphedTrainStep(model, make_optimizer(model, 1e-4, "adam"), image, word_id, word_mask, bbox, size, warmup=max(1, warmup))
+    for _ in range(warmup):
+        step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(iters):
+        step()
+    torch.cuda.synchronize()
+    out["replayed_fused_adam_ms"] = round((time.perf_counter() - t0) / iters * 1e3, 2)
+    out["loss"] = float(step.loss)
+    return out
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--size", type=int, default=416)
+    ap.add_argument("--step", action="store_true", help="also time the whole step: eager torch Adam against the replayed fused Adam")
+    ap.add_argument("--clips", type=int, default=8)
+    ap.add_argument("--step-iters", type=int, default=10)
+    ap.add_argument("--json", default="")
+    a = ap.parse_args(argv)
+    dev = torch.device("cuda:0")
+    model = build_model(a.size, dev)
+    shapes = [tuple(p.shape) for p in model.parameters() if p.requires_grad]
+    del model
+    torch.cuda.empty_cache()
+    rows = []
+    for name in ("adam", "sgd"):
+        rows.append(bench_steps(name, shapes, dev, a.iters, a.warmup))
+        print(json.dumps(rows[-1]), flush=True)
+        torch.cuda.empty_cache()
+    if a.step:
+        rows.append(bench_train_step(dev, a.size, a.clips, a.step_iters, a.warmup))
+        print(json.dumps(rows[-1]), flush=True)
+    if a.json:
+        with open(a.json, "w") as fh:
+            json.dump(rows, fh, indent=1)
+
+
+if __name__ == "__main__":
+    main()
