@@ -21,7 +21,25 @@ __device__ __forceinline__ void rms_update(float& p, const float g0, float& v, f
   p = p - lr * (g / (sqrtf(v) + eps));                   // param.addcdiv_(grad, square_avg.sqrt().add_(eps), value=-lr)
 }
 
-__global__ __launch_bounds__(256) void rmsprop_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd) {
+// ---- gradient clipping: the control block ---------------------------------------------------------------------------------------
+// Four 32-bit words on the device (include/dcnet_hip.h, dcn_grad_clip_coef): [0] float norm, [1] float coef, [2] int32 apply,
+// [3] int32 skips.  The clipped form of an update kernel (CLIP) returns at once when apply is 0 and otherwise takes g0 * coef for
+// the gradient — one rounding, contraction off, in front of the weight-decay term: torch's in-place grad.mul_(coef) followed by
+// the optimiser.  The plain form (CLIP = false) is the kernel as it was: it never looks at `ctl`.
+constexpr int CTL_NORM = 0, CTL_COEF = 1, CTL_APPLY = 2, CTL_SKIPS = 3;
+__device__ __forceinline__ float clip_mul(const float g0, const float coef) {
+#pragma clang fp contract(off)
+  return g0 * coef;
+}
+
+template <bool CLIP>
+__device__ __forceinline__ void rmsprop_body(const RmsChunk& c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd,
+                                             const float* __restrict__ ctl) {
+  float coef = 1.f;
+  if (CLIP) {
+    if (reinterpret_cast<const int*>(ctl)[CTL_APPLY] == 0) return;
+    coef = ctl[CTL_COEF];
+  }
   if (lr_dev) lr = lr_dev[0];                 // a captured step (hipGraph) reads its learning rate from device memory
   const int t = blockIdx.y;
   float* __restrict__ p = c.p[t]; const float* __restrict__ g = c.g[t]; float* __restrict__ v = c.v[t];
@@ -32,11 +50,23 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(const RmsChunk c, float lr
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i], vv = reinterpret_cast<f32x4*>(v)[i];
     const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { float a = pp[e], b = vv[e]; rms_update(a, gg[e], b, lr, alpha, eps, wd); pp[e] = a; vv[e] = b; }
+    for (int e = 0; e < 4; ++e) {
+      float a = pp[e], b = vv[e];
+      rms_update(a, CLIP ? clip_mul(gg[e], coef) : gg[e], b, lr, alpha, eps, wd);
+      pp[e] = a; vv[e] = b;
+    }
     reinterpret_cast<f32x4*>(p)[i] = pp; reinterpret_cast<f32x4*>(v)[i] = vv;
   }
   for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    rms_update(p[i], g[i], v[i], lr, alpha, eps, wd);
+    rms_update(p[i], CLIP ? clip_mul(g[i], coef) : g[i], v[i], lr, alpha, eps, wd);
+}
+
+__global__ __launch_bounds__(256) void rmsprop_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd) {
+  rmsprop_body<false>(c, lr, lr_dev, alpha, eps, wd, nullptr);
+}
+__global__ __launch_bounds__(256) void rmsprop_clip_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd,
+                                                           const float* __restrict__ ctl) {
+  rmsprop_body<true>(c, lr, lr_dev, alpha, eps, wd, ctl);
 }
 
 // ---- Adam ---------------------------------------------------------------------------------------------------------------------
@@ -46,7 +76,7 @@ __global__ __launch_bounds__(256) void rmsprop_kernel(const RmsChunk c, float lr
 constexpr int STEP_CHUNK = 128;
 struct StepChunk { int* step[STEP_CHUNK]; float* scal[STEP_CHUNK]; };
 
-__global__ __launch_bounds__(64) void adam_prepare_kernel(const StepChunk c, float lr, const float* __restrict__ lr_dev, double beta1, double beta2) {
+__device__ __forceinline__ void adam_prepare_body(const StepChunk& c, float lr, const float* __restrict__ lr_dev, double beta1, double beta2) {
   if (threadIdx.x != 0) return;
   if (lr_dev) lr = lr_dev[0];
   const int t = c.step[blockIdx.x][0] + 1;
@@ -54,6 +84,16 @@ __global__ __launch_bounds__(64) void adam_prepare_kernel(const StepChunk c, flo
   const double bc1 = 1.0 - pow(beta1, (double)t), bc2 = 1.0 - pow(beta2, (double)t);
   c.scal[blockIdx.x][0] = (float)((double)lr / bc1);          // step_size = lr / bias_correction1
   c.scal[blockIdx.x][1] = (float)(1.0 / sqrt(bc2));           // torch divides sqrt(v) by the scalar sqrt(bc2): a multiplication by its inverse
+}
+
+__global__ __launch_bounds__(64) void adam_prepare_kernel(const StepChunk c, float lr, const float* __restrict__ lr_dev, double beta1, double beta2) {
+  adam_prepare_body(c, lr, lr_dev, beta1, beta2);
+}
+// (a skipped step — apply = 0 — leaves the step words and the scalars alone: the next applied step is step t + 1, not t + 2)
+__global__ __launch_bounds__(64) void adam_prepare_clip_kernel(const StepChunk c, float lr, const float* __restrict__ lr_dev, double beta1, double beta2,
+                                                               const int* __restrict__ ctl) {
+  if (ctl[CTL_APPLY] == 0) return;
+  adam_prepare_body(c, lr, lr_dev, beta1, beta2);
 }
 
 struct AdamChunk {
@@ -72,7 +112,13 @@ __device__ __forceinline__ void adam_update(float& p, const float g0, float& m, 
   p = p - step_size * (m / denom);                       // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, float wd) {
+template <bool CLIP>
+__device__ __forceinline__ void adam_body(const AdamChunk& c, float w1, float beta2, float w2, float eps, float wd, const float* __restrict__ ctl) {
+  float coef = 1.f;
+  if (CLIP) {
+    if (reinterpret_cast<const int*>(ctl)[CTL_APPLY] == 0) return;
+    coef = ctl[CTL_COEF];
+  }
   const int t = blockIdx.y;
   float* __restrict__ p = c.p[t]; const float* __restrict__ g = c.g[t]; float* __restrict__ m = c.m[t]; float* __restrict__ v = c.v[t];
   const float step_size = c.s[t][0], inv_bc2_sqrt = c.s[t][1];          // (adam_prepare_kernel wrote them in the launch before this one)
@@ -85,13 +131,21 @@ __global__ __launch_bounds__(256) void adam_kernel(const AdamChunk c, float w1, 
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float a = pp[e], b = mm[e], d = vv[e];
-      adam_update(a, gg[e], b, d, step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
+      adam_update(a, CLIP ? clip_mul(gg[e], coef) : gg[e], b, d, step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
       pp[e] = a; mm[e] = b; vv[e] = d;
     }
     reinterpret_cast<f32x4*>(p)[i] = pp; reinterpret_cast<f32x4*>(m)[i] = mm; reinterpret_cast<f32x4*>(v)[i] = vv;
   }
   for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    adam_update(p[i], g[i], m[i], v[i], step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
+    adam_update(p[i], CLIP ? clip_mul(g[i], coef) : g[i], m[i], v[i], step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
+}
+
+__global__ __launch_bounds__(256) void adam_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, float wd) {
+  adam_body<false>(c, w1, beta2, w2, eps, wd, nullptr);
+}
+__global__ __launch_bounds__(256) void adam_clip_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, float wd,
+                                                        const float* __restrict__ ctl) {
+  adam_body<true>(c, w1, beta2, w2, eps, wd, ctl);
 }
 
 // ---- SGD with momentum --------------------------------------------------------------------------------------------------------
@@ -103,7 +157,13 @@ __device__ __forceinline__ void sgd_update(float& p, const float g0, float& buf,
   p = p - lr * buf;                                      // param.add_(buf, alpha=-lr)
 }
 
-__global__ __launch_bounds__(256) void sgd_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float mu, float wd) {
+template <bool CLIP>
+__device__ __forceinline__ void sgd_body(const RmsChunk& c, float lr, const float* __restrict__ lr_dev, float mu, float wd, const float* __restrict__ ctl) {
+  float coef = 1.f;
+  if (CLIP) {
+    if (reinterpret_cast<const int*>(ctl)[CTL_APPLY] == 0) return;
+    coef = ctl[CTL_COEF];
+  }
   if (lr_dev) lr = lr_dev[0];
   const int t = blockIdx.y;
   float* __restrict__ p = c.p[t]; const float* __restrict__ g = c.g[t]; float* __restrict__ b = c.v[t];
@@ -114,11 +174,23 @@ __global__ __launch_bounds__(256) void sgd_kernel(const RmsChunk c, float lr, co
     f32x4 pp = reinterpret_cast<f32x4*>(p)[i], bb = reinterpret_cast<f32x4*>(b)[i];
     const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) { float a = pp[e], d = bb[e]; sgd_update(a, gg[e], d, lr, mu, wd); pp[e] = a; bb[e] = d; }
+    for (int e = 0; e < 4; ++e) {
+      float a = pp[e], d = bb[e];
+      sgd_update(a, CLIP ? clip_mul(gg[e], coef) : gg[e], d, lr, mu, wd);
+      pp[e] = a; bb[e] = d;
+    }
     reinterpret_cast<f32x4*>(p)[i] = pp; reinterpret_cast<f32x4*>(b)[i] = bb;
   }
   for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    sgd_update(p[i], g[i], b[i], lr, mu, wd);
+    sgd_update(p[i], CLIP ? clip_mul(g[i], coef) : g[i], b[i], lr, mu, wd);
+}
+
+__global__ __launch_bounds__(256) void sgd_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float mu, float wd) {
+  sgd_body<false>(c, lr, lr_dev, mu, wd, nullptr);
+}
+__global__ __launch_bounds__(256) void sgd_clip_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float mu, float wd,
+                                                       const float* __restrict__ ctl) {
+  sgd_body<true>(c, lr, lr_dev, mu, wd, ctl);
 }
 
 // blocks along x for a chunk whose longest tensor has `biggest` values (grid-stride beyond 128)
@@ -127,39 +199,273 @@ inline unsigned blocks_for(long long biggest) {
   return (unsigned)(bx < 1 ? 1 : (bx > 128 ? 128 : bx));
 }
 
+// ---- global gradient norm ---------------------------------------------------------------------------------------------------------
+// One more read of the gradients: every block sums the squares of its share of one tensor in double (the product of two floats is
+// exact in double, so contraction cannot change a bit) and writes ONE double into its own slot — slot (chunk, tensor in chunk,
+// blockIdx.x), every launched block writes, 0.0 when it had no work.  grad_clip_coef_kernel adds the slots in a fixed order.  No
+// atomics, no arrival counters: the norm is the same bits in every run, eager or replayed.  A thread takes the same four
+// consecutive values per trip whether the pointer is 16-byte aligned (one 16-byte load) or not (four 4-byte loads), so a view
+// into a flat gradient buffer gives the same bits as an aligned tensor.
+struct NormChunk { const float* g[RMS_CHUNK]; long long n[RMS_CHUNK]; };
+struct ScaleChunk { float* g[RMS_CHUNK]; long long n[RMS_CHUNK]; };
+
+// sum over the WAVES x 64 threads of a block, in a fixed order; `red` = WAVES doubles of shared memory.  Every thread must call.
+template <int WAVES>
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double s = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) s += red[w];
+  return s;
+}
+
+// four consecutive gradient values: one 16-byte load where the tensor is 16-byte aligned, four 4-byte loads otherwise
+__device__ __forceinline__ f32x4 load4(const float* __restrict__ g, long long i, bool vec) {
+  if (vec) return reinterpret_cast<const f32x4*>(g)[i];
+  f32x4 r;
+  r[0] = g[4 * i]; r[1] = g[4 * i + 1]; r[2] = g[4 * i + 2]; r[3] = g[4 * i + 3];
+  return r;
+}
+__device__ __forceinline__ double add_squares(double acc, const f32x4 gg) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { const double x = (double)gg[e]; acc += x * x; }
+  return acc;
+}
+
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const NormChunk c, double* __restrict__ partials) {
+  __shared__ double red[4];
+  const int t = blockIdx.y;
+  const float* __restrict__ g = c.g[t];
+  const long long n = c.n[t], n4 = n / 4;
+  const bool vec = (((uintptr_t)g) & 15) == 0;
+  const long long stride = (long long)gridDim.x * 256;
+  double acc = 0.0;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  // four loads in flight per thread (one load per trip leaves HBM half idle); the squares are added in the order of the plain loop
+  for (; i + 3 * stride < n4; i += 4 * stride) {
+    const f32x4 a = load4(g, i, vec), b = load4(g, i + stride, vec), d = load4(g, i + 2 * stride, vec), e = load4(g, i + 3 * stride, vec);
+    acc = add_squares(add_squares(add_squares(add_squares(acc, a), b), d), e);
+  }
+  for (; i < n4; i += stride) acc = add_squares(acc, load4(g, i, vec));
+  for (i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const double x = (double)g[i]; acc += x * x;
+  }
+  const double s = block_sum_f64<4>(acc, red);
+  if (threadIdx.x == 0) partials[(long long)t * gridDim.x + blockIdx.x] = s;
+}
+
+// clip_coef = max_norm / (total_norm + 1e-6), clamped to at most 1 — in fp32, each operation rounded once
+__device__ __forceinline__ float clip_coef(const float norm, const float max_norm) {
+#pragma clang fp contract(off)
+  const float coef = max_norm / (norm + 1e-6f);
+  return coef > 1.f ? 1.f : coef;                        // torch.clamp(clip_coef, max=1.0): a NaN stays a NaN
+}
+
+// one workgroup of 1024: thread i adds slots i, i + 1024, ... — four running sums (trip k into sum k mod 4: four loads in flight, the
+// sum is latency-bound), folded in a fixed order — then the block sum; thread 0 writes the control block
+__global__ __launch_bounds__(1024) void grad_clip_coef_kernel(const double* __restrict__ partials, long long slots, float max_norm, int skip_nonfinite,
+                                                              float* __restrict__ ctl) {
+  __shared__ double red[16];
+  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
+  long long i = threadIdx.x;
+  for (; i + 3 * 1024 < slots; i += 4 * 1024) {
+    const double p0 = partials[i], p1 = partials[i + 1024], p2 = partials[i + 2 * 1024], p3 = partials[i + 3 * 1024];
+    a0 += p0; a1 += p1; a2 += p2; a3 += p3;
+  }
+  if (i < slots) a0 += partials[i];
+  if (i + 1024 < slots) a1 += partials[i + 1024];
+  if (i + 2 * 1024 < slots) a2 += partials[i + 2 * 1024];
+  const double s = block_sum_f64<16>((a0 + a1) + (a2 + a3), red);
+  if (threadIdx.x != 0) return;
+  const float norm = (float)sqrt(s);
+  const int apply = (skip_nonfinite && !__builtin_isfinite(s)) ? 0 : 1;
+  ctl[CTL_NORM] = norm;
+  ctl[CTL_COEF] = clip_coef(norm, max_norm);
+  int* w = reinterpret_cast<int*>(ctl);
+  w[CTL_APPLY] = apply;
+  if (!apply) w[CTL_SKIPS] = w[CTL_SKIPS] + 1;
+}
+
+__global__ __launch_bounds__(256) void grad_scale_kernel(const ScaleChunk c, const float* __restrict__ ctl) {
+  const float coef = ctl[CTL_COEF];
+  const int t = blockIdx.y;
+  float* __restrict__ g = c.g[t];
+  const long long n = c.n[t];
+  const long long n4 = ((((uintptr_t)g) & 15) == 0) ? n / 4 : 0;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+    f32x4 gg = reinterpret_cast<f32x4*>(g)[i];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gg[e] = clip_mul(gg[e], coef);
+    reinterpret_cast<f32x4*>(g)[i] = gg;
+  }
+  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
+    g[i] = clip_mul(g[i], coef);
+}
+
+// slots of the partials buffer for `count` tensors: per chunk of 32, blocks_for(its longest tensor) x tensors in the chunk
+inline long long sumsq_slots(const int64_t* numel, int count) {
+  long long total = 0;
+  for (int base = 0; base < count; base += RMS_CHUNK) {
+    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
+    long long biggest = 0;
+    for (int i = 0; i < m; ++i)
+      if (numel[base + i] > biggest) biggest = numel[base + i];
+    total += (long long)blocks_for(biggest) * m;
+  }
+  return total;
+}
+
 }  // namespace
 
-extern "C" int dcn_rmsprop_step(float* const* params, const float* const* grads, float* const* square_avgs, const int64_t* numel,
-                                int count, float lr, const float* lr_dev, float alpha, float eps, float weight_decay, void* stream) {
-  DCN_CHECK_ARG(params && grads && square_avgs && numel && count > 0, "rmsprop_step: bad argument");
+extern "C" int64_t dcn_grad_sumsq_slots(const int64_t* numel, int count) {
+  if (!numel || count <= 0) { dcn_set_error("grad_sumsq_slots: bad argument"); return -1; }
+  for (int i = 0; i < count; ++i)
+    if (numel[i] < 0) { dcn_set_error("grad_sumsq_slots: negative element count of tensor %d", i); return -1; }
+  return sumsq_slots(numel, count);
+}
+
+extern "C" int dcn_grad_sumsq(const float* const* grads, const int64_t* numel, int count, double* partials, int64_t slots, void* stream) {
+  DCN_CHECK_ARG(grads && numel && partials && count > 0, "grad_sumsq: bad argument");
+  for (int i = 0; i < count; ++i)
+    DCN_CHECK_ARG(grads[i] && numel[i] >= 0, "grad_sumsq: null tensor %d", i);
+  DCN_CHECK_ARG(slots == sumsq_slots(numel, count), "grad_sumsq: the partials buffer has %lld slots, these tensors need %lld (dcn_grad_sumsq_slots)",
+                (long long)slots, sumsq_slots(numel, count));
+  long long at = 0;
+  for (int base = 0; base < count; base += RMS_CHUNK) {
+    NormChunk c{};
+    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
+    long long biggest = 0;
+    for (int i = 0; i < m; ++i) {
+      c.g[i] = grads[base + i]; c.n[i] = numel[base + i];
+      if (c.n[i] > biggest) biggest = c.n[i];
+    }
+    const unsigned bx = blocks_for(biggest);
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(bx, m), dim3(256), 0, (hipStream_t)stream, c, partials + at);
+    DCN_CHECK_LAUNCH("grad_sumsq");
+    at += (long long)bx * m;
+  }
+  return DCN_OK;
+}
+
+extern "C" int dcn_grad_clip_coef(const double* partials, int64_t slots, float max_norm, int skip_nonfinite, void* ctrl, void* stream) {
+  DCN_CHECK_ARG(partials && ctrl && slots > 0, "grad_clip_coef: bad argument");
+  DCN_CHECK_ARG(max_norm > 0.f, "grad_clip_coef: max_norm %g is not a positive number", (double)max_norm);
+  hipLaunchKernelGGL(grad_clip_coef_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, partials, (long long)slots, max_norm, skip_nonfinite,
+                     (float*)ctrl);
+  DCN_CHECK_LAUNCH("grad_clip_coef");
+  return DCN_OK;
+}
+
+extern "C" int dcn_grad_scale(float* const* grads, const int64_t* numel, int count, const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(grads && numel && ctrl && count > 0, "grad_scale: bad argument");
+  for (int i = 0; i < count; ++i)
+    DCN_CHECK_ARG(grads[i] && numel[i] >= 0, "grad_scale: null tensor %d", i);
+  for (int base = 0; base < count; base += RMS_CHUNK) {
+    ScaleChunk c{};
+    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
+    long long biggest = 0;
+    for (int i = 0; i < m; ++i) {
+      c.g[i] = grads[base + i]; c.n[i] = numel[base + i];
+      if (c.n[i] > biggest) biggest = c.n[i];
+    }
+    hipLaunchKernelGGL(grad_scale_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (const float*)ctrl);
+    DCN_CHECK_LAUNCH("grad_scale");
+  }
+  return DCN_OK;
+}
+
+// The update entry points come in two forms over one body each: the plain one launches the kernels it always launched, the
+// `_clipped` one (ctl = the control block dcn_grad_clip_coef wrote, non-NULL) their clipped forms.
+static int rmsprop_step(const char* who, float* const* params, const float* const* grads, float* const* square_avgs, const int64_t* numel,
+                        int count, float lr, const float* lr_dev, float alpha, float eps, float weight_decay, const float* ctl, void* stream) {
+  DCN_CHECK_ARG(params && grads && square_avgs && numel && count > 0, "%s: bad argument", who);
   for (int base = 0; base < count; base += RMS_CHUNK) {
     RmsChunk c{};
     const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
     long long biggest = 0;
     for (int i = 0; i < m; ++i) {
-      DCN_CHECK_ARG(params[base + i] && grads[base + i] && square_avgs[base + i] && numel[base + i] >= 0, "rmsprop_step: null tensor %d", base + i);
+      DCN_CHECK_ARG(params[base + i] && grads[base + i] && square_avgs[base + i] && numel[base + i] >= 0, "%s: null tensor %d", who, base + i);
       c.p[i] = params[base + i]; c.g[i] = grads[base + i]; c.v[i] = square_avgs[base + i]; c.n[i] = numel[base + i];
       if (c.n[i] > biggest) biggest = c.n[i];
     }
-    hipLaunchKernelGGL(rmsprop_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, alpha, eps, weight_decay);
-    DCN_CHECK_LAUNCH("rmsprop_step");
+    if (ctl)
+      hipLaunchKernelGGL(rmsprop_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, alpha, eps, weight_decay, ctl);
+    else
+      hipLaunchKernelGGL(rmsprop_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, alpha, eps, weight_decay);
+    DCN_CHECK_LAUNCH(who);
+  }
+  return DCN_OK;
+}
+
+extern "C" int dcn_rmsprop_step(float* const* params, const float* const* grads, float* const* square_avgs, const int64_t* numel,
+                                int count, float lr, const float* lr_dev, float alpha, float eps, float weight_decay, void* stream) {
+  return rmsprop_step("rmsprop_step", params, grads, square_avgs, numel, count, lr, lr_dev, alpha, eps, weight_decay, nullptr, stream);
+}
+
+extern "C" int dcn_rmsprop_step_clipped(float* const* params, const float* const* grads, float* const* square_avgs, const int64_t* numel,
+                                        int count, float lr, const float* lr_dev, float alpha, float eps, float weight_decay, const void* ctrl,
+                                        void* stream) {
+  DCN_CHECK_ARG(ctrl, "rmsprop_step_clipped: no control block");
+  return rmsprop_step("rmsprop_step_clipped", params, grads, square_avgs, numel, count, lr, lr_dev, alpha, eps, weight_decay, (const float*)ctrl, stream);
+}
+
+static int adam_prepare(const char* who, int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                        const int* ctl, void* stream) {
+  DCN_CHECK_ARG(steps && scal && count > 0, "%s: bad argument", who);
+  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
+  for (int base = 0; base < count; base += STEP_CHUNK) {
+    StepChunk c{};
+    const int m = count - base < STEP_CHUNK ? count - base : STEP_CHUNK;
+    for (int i = 0; i < m; ++i) {
+      DCN_CHECK_ARG(steps[base + i] && scal[base + i], "%s: null tensor %d", who, base + i);
+      c.step[i] = steps[base + i]; c.scal[i] = scal[base + i];
+    }
+    if (ctl)
+      hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2, ctl);
+    else
+      hipLaunchKernelGGL(adam_prepare_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2);
+    DCN_CHECK_LAUNCH(who);
   }
   return DCN_OK;
 }
 
 extern "C" int dcn_adam_prepare(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
                                 void* stream) {
-  DCN_CHECK_ARG(steps && scal && count > 0, "adam_prepare: bad argument");
-  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_prepare: betas (%g, %g) outside [0, 1)", beta1, beta2);
-  for (int base = 0; base < count; base += STEP_CHUNK) {
-    StepChunk c{};
-    const int m = count - base < STEP_CHUNK ? count - base : STEP_CHUNK;
+  return adam_prepare("adam_prepare", steps, scal, count, lr, lr_dev, beta1, beta2, nullptr, stream);
+}
+
+extern "C" int dcn_adam_prepare_clipped(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                                        const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(ctrl, "adam_prepare_clipped: no control block");
+  return adam_prepare("adam_prepare_clipped", steps, scal, count, lr, lr_dev, beta1, beta2, (const int*)ctrl, stream);
+}
+
+static int adam_step(const char* who, float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                     const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, float weight_decay,
+                     const float* ctl, void* stream) {
+  DCN_CHECK_ARG(params && grads && exp_avgs && exp_avg_sqs && scal && numel && count > 0, "%s: bad argument", who);
+  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
+  DCN_CHECK_ARG(eps >= 0.f && weight_decay >= 0.f, "%s: negative eps or weight_decay", who);
+  for (int base = 0; base < count; base += RMS_CHUNK) {
+    AdamChunk c{};
+    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
+    long long biggest = 0;
     for (int i = 0; i < m; ++i) {
-      DCN_CHECK_ARG(steps[base + i] && scal[base + i], "adam_prepare: null tensor %d", base + i);
-      c.step[i] = steps[base + i]; c.scal[i] = scal[base + i];
+      const int k = base + i;
+      DCN_CHECK_ARG(params[k] && grads[k] && exp_avgs[k] && exp_avg_sqs[k] && scal[k] && numel[k] >= 0, "%s: null tensor %d", who, k);
+      c.p[i] = params[k]; c.g[i] = grads[k]; c.m[i] = exp_avgs[k]; c.v[i] = exp_avg_sqs[k]; c.s[i] = scal[k]; c.n[i] = numel[k];
+      if (c.n[i] > biggest) biggest = c.n[i];
     }
-    hipLaunchKernelGGL(adam_prepare_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2);
-    DCN_CHECK_LAUNCH("adam_prepare");
+    if (ctl)
+      hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
+                         (float)(1.0 - beta2), eps, weight_decay, ctl);
+    else
+      hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
+                         (float)(1.0 - beta2), eps, weight_decay);
+    DCN_CHECK_LAUNCH(who);
   }
   return DCN_OK;
 }
@@ -167,42 +473,47 @@ extern "C" int dcn_adam_prepare(int* const* steps, float* const* scal, int count
 extern "C" int dcn_adam_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
                              const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
                              float weight_decay, void* stream) {
-  DCN_CHECK_ARG(params && grads && exp_avgs && exp_avg_sqs && scal && numel && count > 0, "adam_step: bad argument");
-  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "adam_step: betas (%g, %g) outside [0, 1)", beta1, beta2);
-  DCN_CHECK_ARG(eps >= 0.f && weight_decay >= 0.f, "adam_step: negative eps or weight_decay");
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    AdamChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      const int k = base + i;
-      DCN_CHECK_ARG(params[k] && grads[k] && exp_avgs[k] && exp_avg_sqs[k] && scal[k] && numel[k] >= 0, "adam_step: null tensor %d", k);
-      c.p[i] = params[k]; c.g[i] = grads[k]; c.m[i] = exp_avgs[k]; c.v[i] = exp_avg_sqs[k]; c.s[i] = scal[k]; c.n[i] = numel[k];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
-                       (float)(1.0 - beta2), eps, weight_decay);
-    DCN_CHECK_LAUNCH("adam_step");
-  }
-  return DCN_OK;
+  return adam_step("adam_step", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, weight_decay, nullptr, stream);
 }
 
-extern "C" int dcn_sgd_step(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
-                            float lr, const float* lr_dev, float momentum, float weight_decay, void* stream) {
-  DCN_CHECK_ARG(params && grads && momentum_bufs && numel && count > 0, "sgd_step: bad argument");
-  DCN_CHECK_ARG(momentum >= 0.f && weight_decay >= 0.f, "sgd_step: negative momentum or weight_decay");
+extern "C" int dcn_adam_step_clipped(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                     const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
+                                     float weight_decay, const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(ctrl, "adam_step_clipped: no control block");
+  return adam_step("adam_step_clipped", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, weight_decay, (const float*)ctrl,
+                   stream);
+}
+
+static int sgd_step(const char* who, float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
+                    float lr, const float* lr_dev, float momentum, float weight_decay, const float* ctl, void* stream) {
+  DCN_CHECK_ARG(params && grads && momentum_bufs && numel && count > 0, "%s: bad argument", who);
+  DCN_CHECK_ARG(momentum >= 0.f && weight_decay >= 0.f, "%s: negative momentum or weight_decay", who);
   for (int base = 0; base < count; base += RMS_CHUNK) {
     RmsChunk c{};
     const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
     long long biggest = 0;
     for (int i = 0; i < m; ++i) {
       const int k = base + i;
-      DCN_CHECK_ARG(params[k] && grads[k] && momentum_bufs[k] && numel[k] >= 0, "sgd_step: null tensor %d", k);
+      DCN_CHECK_ARG(params[k] && grads[k] && momentum_bufs[k] && numel[k] >= 0, "%s: null tensor %d", who, k);
       c.p[i] = params[k]; c.g[i] = grads[k]; c.v[i] = momentum_bufs[k]; c.n[i] = numel[k];
       if (c.n[i] > biggest) biggest = c.n[i];
     }
-    hipLaunchKernelGGL(sgd_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, momentum, weight_decay);
-    DCN_CHECK_LAUNCH("sgd_step");
+    if (ctl)
+      hipLaunchKernelGGL(sgd_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, momentum, weight_decay, ctl);
+    else
+      hipLaunchKernelGGL(sgd_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, momentum, weight_decay);
+    DCN_CHECK_LAUNCH(who);
   }
   return DCN_OK;
+}
+
+extern "C" int dcn_sgd_step(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
+                            float lr, const float* lr_dev, float momentum, float weight_decay, void* stream) {
+  return sgd_step("sgd_step", params, grads, momentum_bufs, numel, count, lr, lr_dev, momentum, weight_decay, nullptr, stream);
+}
+
+extern "C" int dcn_sgd_step_clipped(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
+                                    float lr, const float* lr_dev, float momentum, float weight_decay, const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(ctrl, "sgd_step_clipped: no control block");
+  return sgd_step("sgd_step_clipped", params, grads, momentum_bufs, numel, count, lr, lr_dev, momentum, weight_decay, (const float*)ctrl, stream);
 }

@@ -93,6 +93,13 @@ class GraphedTrainStep:
         # of a step, with the draws made above
         self._replay_device()
 
+    @property
+    def grad_norm(self):
+        """The global gradient norm of the last step as a 0-dim device tensor, where the optimiser computes one (``max_grad_norm`` /
+        ``skip_nonfinite`` of ``dcnet_amd.optim``: norm, coefficient and skip are kernels of the captured step); else None.  Reading
+        it synchronises.  With a reducer the optimiser steps after the all-reduce: every rank sees the norm of the averaged gradient."""
+        return getattr(self.opt, "grad_norm", None)
+
     # ------------------------------------------------------------------------------------------------
     def _zero_grads(self):
         r = self.reducer

@@ -25,7 +25,8 @@ import torch
 from . import losses, ops
 
 
-def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: bool = True):
+def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: bool = True, max_grad_norm: Optional[float] = None,
+                   skip_nonfinite: bool = False):
     """The optimiser the reference builds for ``--optimizer`` (train_DCNet.py:519-534).  ``model`` may be DDP-wrapped.
 
     ``"RMSprop"`` (the default): two groups, everything except the backbone at ``lr``, the Darknet backbone at ``lr / 10``; weight
@@ -36,18 +37,29 @@ def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: b
     Every parameter is listed, in ``model.parameters()`` order, whether or not it is trainable — the reference's RMSprop
     groups hold [93, 222] tensors including the dead YOLO heads and ``feature_map`` — so that the ``optimizer`` entry
     of a ``.pth.tar`` checkpoint moves between the reference and this harness in both directions even after
-    ``parallel.freeze_gradless`` has run.  Parameters without a gradient are skipped by the step, as in torch."""
+    ``parallel.freeze_gradless`` has run.  Parameters without a gradient are skipped by the step, as in torch.
+
+    ``max_grad_norm`` / ``skip_nonfinite``: the fused classes' global-norm gradient clipping and non-finite skip, computed on the
+    device inside the step (``dcnet_amd.optim``; the reference has neither).  One norm over all groups.  In a data-parallel run the
+    optimiser steps after the gradient all-reduce, so every rank clips by the same norm of the same averaged gradient.  torch's
+    classes have no such step: with ``fused=False`` call ``dcnet_amd.optim.clip_grad_norm_`` before ``step()`` yourself."""
     from . import optim
     core = model.module if hasattr(model, "module") else model
     name = optimizer.lower()
+    clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    if not fused and (max_grad_norm is not None or skip_nonfinite):
+        raise ValueError("make_optimizer: max_grad_norm / skip_nonfinite belong to the fused optimisers; with fused=False call "
+                         "dcnet_amd.optim.clip_grad_norm_(model.parameters(), max_norm) before optimizer.step()")
     if name == "adam":
-        return (optim.Adam if fused else torch.optim.Adam)(list(core.parameters()), lr=lr, weight_decay=0.0005)
+        return optim.Adam(list(core.parameters()), lr=lr, weight_decay=0.0005, **clip) if fused else \
+            torch.optim.Adam(list(core.parameters()), lr=lr, weight_decay=0.0005)
     if name == "sgd":
-        return (optim.SGD if fused else torch.optim.SGD)(list(core.parameters()), lr=lr, momentum=0.99)
+        return optim.SGD(list(core.parameters()), lr=lr, momentum=0.99, **clip) if fused else \
+            torch.optim.SGD(list(core.parameters()), lr=lr, momentum=0.99)
     visu = list(core.visumodel.parameters())
     ids = {id(p) for p in visu}
     rest = [p for p in core.parameters() if id(p) not in ids]
-    return optim.RMSprop([{"params": rest}, {"params": visu, "lr": lr / 10.}], lr=lr, weight_decay=0.0005)
+    return optim.RMSprop([{"params": rest}, {"params": visu, "lr": lr / 10.}], lr=lr, weight_decay=0.0005, **clip)
 
 
 def lr_poly(base_lr: float, it: int, max_iter: int, power: float) -> float:
@@ -134,7 +146,7 @@ def load_pretrain(model, path: str, map_location="cpu") -> int:
     return len(take)
 
 
-def main(argv: Optional[Iterable[str]] = None) -> None:
+def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="short synthetic-data training run of the HIP-backed DCNet")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--clips", type=int, default=2)
@@ -143,7 +155,13 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--optimizer", choices=["rmsprop", "adam", "sgd"], default="rmsprop", help="train_DCNet.py's --optimizer")
     ap.add_argument("--raw-frames", action="store_true", help="feed uint8 frames through dcnet_amd.prep every step")
-    args = ap.parse_args(argv)
+    ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X", help="clip the global gradient norm to X inside the fused step")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="a step whose gradient norm is inf or NaN updates nothing")
+    return ap
+
+
+def main(argv: Optional[Iterable[str]] = None) -> None:
+    args = arg_parser().parse_args(argv)
     from .model import grounding_model
     from .parallel import freeze_gradless
     from .utils.synth import synth_boxes, synth_inputs
@@ -151,7 +169,7 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     torch.manual_seed(0); random.seed(0)
     model = grounding_model(corpus=list(range(1000)), emb_size=512, img_size=args.size, config_path="", weights_path=None).to(dev)
     freeze_gradless(model)
-    opt = make_optimizer(model, args.lr, args.optimizer)
+    opt = make_optimizer(model, args.lr, args.optimizer, max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
     n = args.clips * args.frames
     image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, args.size, seed=1))
     bbox = synth_boxes(n, args.size, seed=1).to(dev)
@@ -173,7 +191,10 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
         if it % 5 == 0 or it == args.steps - 1:
             print(f"step {it:3d} loss {float(loss):9.4f}  " + " ".join(f"{k} {float(v):.4f}" for k, v in parts.items()))
     acc, miou, _ = evaluate(model, image, word_id, word_mask, bbox, args.size)
-    print(f"Acc@0.5 {float(acc):.3f}  mIoU {float(miou):.3f} (on the training clips)")
+    line = f"Acc@0.5 {float(acc):.3f}  mIoU {float(miou):.3f} (on the training clips)"
+    if opt.grad_norm is not None:
+        line += f"  last gradient norm {float(opt.grad_norm):.4g}  skipped steps {opt.skipped_steps()}"
+    print(line)
 
 
 if __name__ == "__main__":

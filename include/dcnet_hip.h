@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 313
+#define DCN_ABI_VERSION 314
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -710,6 +710,36 @@ int dcn_adam_step(float* const* params, const float* const* grads, float* const*
  * lr_dev as in dcn_rmsprop_step. */
 int dcn_sgd_step(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
                  float lr, const float* lr_dev, float momentum, float weight_decay, void* stream);
+/* Global-norm gradient clipping and the non-finite skip of the fused steps (ABI 314; dcnet_amd/optim.py: _FusedOptimizer.step with
+ * max_grad_norm / skip_nonfinite, and clip_grad_norm_).  Everything stays on the device; nothing here synchronises.
+ * dcn_grad_sumsq: one read of `count` fp32 gradients (host arrays of device pointers and element counts, 32 tensors per launch).  Every
+ * block sums its share of one tensor's squares in double and writes one double into its own slot of `partials`; `slots` must be
+ * dcn_grad_sumsq_slots(numel, count) — a function of the element counts alone (-1 and an error text on a bad argument).  No atomics:
+ * the same bits in every run, in a captured step as in an eager one, for a 4-byte-aligned view as for an aligned tensor.
+ * dcn_grad_clip_coef: one workgroup adds the slots in a fixed order and writes the control block `ctrl`, four 32-bit words:
+ *   [0] float norm  = (float)sqrt(sum)
+ *   [1] float coef  = min(1, max_norm / (norm + 1e-6f)) in fp32, torch.nn.utils.clip_grad_norm_'s (a NaN stays a NaN);
+ *                     max_norm = +inf gives 1 for every finite norm
+ *   [2] int32 apply = 0 if skip_nonfinite != 0 and the sum is inf or NaN, else 1
+ *   [3] int32 skips   incremented when apply is 0 (the caller zeroes the block once, when it allocates it)
+ * dcn_grad_scale: g *= coef in place, one rounding (clip_grad_norm_ for a caller that keeps a torch optimiser).
+ * dcn_*_step_clipped / dcn_adam_prepare_clipped: the update entry points above with the control block: nothing is written when apply
+ * is 0 (Adam's step words and scalars included), otherwise the gradient is g * coef, rounded once in front of the weight-decay
+ * term — what grad.mul_(coef) followed by the plain step computes, without a pass that writes gradients. */
+int64_t dcn_grad_sumsq_slots(const int64_t* numel, int count);
+int dcn_grad_sumsq(const float* const* grads, const int64_t* numel, int count, double* partials, int64_t slots, void* stream);
+int dcn_grad_clip_coef(const double* partials, int64_t slots, float max_norm, int skip_nonfinite, void* ctrl, void* stream);
+int dcn_grad_scale(float* const* grads, const int64_t* numel, int count, const void* ctrl, void* stream);
+int dcn_rmsprop_step_clipped(float* const* params, const float* const* grads, float* const* square_avgs, const int64_t* numel,
+                             int count, float lr, const float* lr_dev, float alpha, float eps, float weight_decay, const void* ctrl,
+                             void* stream);
+int dcn_adam_prepare_clipped(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                             const void* ctrl, void* stream);
+int dcn_adam_step_clipped(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                          const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
+                          float weight_decay, const void* ctrl, void* stream);
+int dcn_sgd_step_clipped(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
+                         float lr, const float* lr_dev, float momentum, float weight_decay, const void* ctrl, void* stream);
 /* Keys: "precision" 4 (default): the wide tiles of the conv engine and of the weight-gradient GEMM run the f16 two-piece
  *         split (see dcn_absmax) wherever both operands carry their abs-max word, and as 1 otherwise;
  *         1: the bf16 matrix pipe with every fp32 operand cut into three bf16 pieces (exact) and the six cross terms

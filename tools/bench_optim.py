@@ -1,7 +1,7 @@
 """The fused Adam / SGD steps (csrc/optim.hip) against torch's foreach steps, on the trained parameter shapes of the real model
 (synthetic weights, random gradients), alternating in one process:
 
-    python tools/bench_optim.py [--iters 20] [--warmup 3] [--step] [--json out.json]
+    python tools/bench_optim.py [--iters 20] [--warmup 3] [--step] [--clip] [--json out.json]
 
 Per optimiser one JSON line: ms per step of ``torch.optim.{Adam,SGD}(foreach=True)`` and of ``dcnet_amd.optim.{Adam,SGD}`` (HIP events
 around ``step()`` on a warm, otherwise idle GPU; medians over --iters, the two sides measured in turns), the bytes a step has to move
@@ -10,6 +10,13 @@ around ``step()`` on a warm, otherwise idle GPU; medians over --iters, the two s
 ``--step`` adds the whole training step at configs[1]'s geometry (8 clips x T 8 at 416x416): the eager ``train_step`` with
 ``torch.optim.Adam`` — what Adam training had to run before the fused class could be captured — against the replayed hipGraph with
 the fused Adam (wall clock per step over --step-iters steps, host-synchronised at both ends).
+
+``--clip`` times global-norm gradient clipping instead: per optimiser (RMSprop, Adam, SGD) four steps on the same shapes, measured in
+turns in one process — (a) the fused step, (b) the fused step with ``max_grad_norm`` (dcn_grad_sumsq + dcn_grad_clip_coef + the clipped
+update), (c) torch's foreach step, (d) ``torch.nn.utils.clip_grad_norm_(foreach=True)`` + torch's foreach step — and reports b - a
+against d - c and against the HBM time of one read of the gradients, which is all the extra pass has to move.  With ``--step`` as
+well: the replayed RMSprop training step at configs[1]'s geometry with and without clipping, two graphs alive in one process,
+measured in alternating blocks.
 """
 from __future__ import annotations
 
@@ -42,7 +49,11 @@ def build_model(size, dev):
     return model
 
 
-def _make(name, params, fused):
+def _make(name, params, fused, **clip):
+    if name == "rmsprop":
+        return optim.RMSprop(params, lr=1e-4, weight_decay=5e-4, **clip) if fused else torch.optim.RMSprop(params, lr=1e-4, weight_decay=5e-4, foreach=True)
+    if clip:
+        return optim.Adam(params, lr=1e-4, weight_decay=5e-4, **clip) if name == "adam" else optim.SGD(params, lr=1e-4, momentum=0.99, **clip)
     if name == "adam":
         return optim.Adam(params, lr=1e-4, weight_decay=5e-4) if fused else torch.optim.Adam(params, lr=1e-4, weight_decay=5e-4, foreach=True)
     return optim.SGD(params, lr=1e-4, momentum=0.99) if fused else torch.optim.SGD(params, lr=1e-4, momentum=0.99, foreach=True)
@@ -77,6 +88,77 @@ def bench_steps(name, shapes, dev, iters, warmup):
     return {"optimizer": name, "tensors": len(shapes), "values_M": round(n / 1e6, 2), "alg_GB": round(alg / 1e9, 3),
             "torch_foreach_ms": round(t_ms, 4), "fused_ms": round(f_ms, 4), "speedup": round(t_ms / f_ms, 2),
             "fused_TBps": round(alg / f_ms / 1e9, 3), "frac_hbm_peak": round(alg / f_ms / 1e9 / (HBM_PEAK / 1e12), 3)}
+
+
+def bench_clip(name, shapes, dev, iters, warmup, max_norm=1.0):
+    """(a) fused, (b) fused + max_grad_norm, (c) torch foreach, (d) torch clip_grad_norm_(foreach=True) + foreach step; gradients
+    randn * 1e-3 (norm ~ 1e-3 * sqrt(values) = 8.6 at 74 M values), so ``max_norm`` = 1 clips.  (d) scales its gradients in place, so
+    from its second step on its coefficient is ~1; its launches and bytes are the same either way."""
+    g = torch.Generator(device=dev).manual_seed(0)
+    sides = {}
+    for key, fused, clip in (("a", True, {}), ("b", True, {"max_grad_norm": max_norm}), ("c", False, {}), ("d", False, {})):
+        ps = [torch.nn.Parameter(torch.randn(s, device=dev, generator=g) * 0.05) for s in shapes]
+        for p in ps:
+            p.grad = torch.randn(p.shape, device=dev, generator=g) * 1e-3
+        o = _make(name, ps, fused, **clip)
+        if key == "d":
+            def run(o=o, ps=ps):
+                torch.nn.utils.clip_grad_norm_(ps, max_norm, foreach=True)
+                o.step()
+            sides[key] = run
+        else:
+            sides[key] = o.step
+        if key == "b":
+            clipped = o
+    for _ in range(warmup):
+        for fn in sides.values():
+            fn()
+    torch.cuda.synchronize()
+    norm = float(clipped.grad_norm)
+    ts = {k: [] for k in sides}
+    for _ in range(iters):
+        for k, fn in sides.items():
+            ts[k].append(_timed(fn))
+    n = sum(int(torch.Size(s).numel()) for s in shapes)
+    ms = {k: statistics.median(v) for k, v in ts.items()}
+    read_ms = n * 4 / HBM_PEAK * 1e3
+    return {"optimizer": name, "clip": True, "tensors": len(shapes), "values_M": round(n / 1e6, 2), "grad_norm": round(norm, 4), "max_norm": max_norm,
+            "a_fused_ms": round(ms["a"], 4), "b_fused_clip_ms": round(ms["b"], 4), "c_torch_foreach_ms": round(ms["c"], 4),
+            "d_torch_clip_foreach_ms": round(ms["d"], 4), "b_minus_a_ms": round(ms["b"] - ms["a"], 4), "d_minus_c_ms": round(ms["d"] - ms["c"], 4),
+            "grad_read_hbm_peak_ms": round(read_ms, 4), "b_minus_a_over_grad_read": round((ms["b"] - ms["a"]) / read_ms, 2),
+            "spread_ms": {k: [round(min(v), 4), round(max(v), 4)] for k, v in ts.items()}}
+
+
+def bench_train_step_clip(dev, size, clips, iters, warmup, max_norm=1.0, rounds=3):
+    """The replayed RMSprop training step without and with ``max_grad_norm``: two models, two graphs, alternating blocks of ``iters``
+    steps (wall clock per step, host-synchronised at both ends of a block); per side the median over the blocks."""
+    from dcnet_amd.graph import GraphedTrainStep
+    from dcnet_amd.train import make_optimizer
+    from dcnet_amd.utils.synth import synth_boxes, synth_inputs
+    n = clips * 8
+    image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, size, seed=100))
+    bbox = synth_boxes(n, size, seed=100).to(dev)
+    steps = {}
+    for key, clip in (("plain", {}), ("clipped", {"max_grad_norm": max_norm})):
+        random.seed(13)
+        model = build_model(size, dev)
+        steps[key] = GraphedTrainStep(model, make_optimizer(model, 1e-4, "rmsprop", **clip), image, word_id, word_mask, bbox, size, warmup=max(1, warmup))
+        for _ in range(warmup):
+            steps[key]()
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in steps}
+    for _ in range(rounds):
+        for key, step in steps.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                step()
+            torch.cuda.synchronize()
+            blocks[key].append((time.perf_counter() - t0) / iters * 1e3)
+    return {"geometry": f"{clips} clips x T 8 at {size}x{size}", "steps_per_block": iters, "blocks": rounds, "max_norm": max_norm,
+            "grad_norm_last": round(float(steps["clipped"].grad_norm), 4),
+            "replayed_rmsprop_ms": round(statistics.median(blocks["plain"]), 3), "replayed_rmsprop_clip_ms": round(statistics.median(blocks["clipped"]), 3),
+            "blocks_ms": {k: [round(x, 3) for x in v] for k, v in blocks.items()}}
 
 
 def bench_train_step(dev, size, clips, iters, warmup):
@@ -123,6 +205,7 @@ def main(argv=None):
     ap.add_argument("--step", action="store_true", help="also time the whole step: eager torch Adam against the replayed fused Adam")
     ap.add_argument("--clips", type=int, default=8)
     ap.add_argument("--step-iters", type=int, default=10)
+    ap.add_argument("--clip", action="store_true", help="time gradient clipping: fused / fused + clip / torch foreach / torch clip + foreach")
     ap.add_argument("--json", default="")
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
@@ -131,11 +214,14 @@ def main(argv=None):
     del model
     torch.cuda.empty_cache()
     rows = []
-    for name in ("adam", "sgd"):
-        rows.append(bench_steps(name, shapes, dev, a.iters, a.warmup))
+    for name in (("rmsprop", "adam", "sgd") if a.clip else ("adam", "sgd")):
+        rows.append(bench_clip(name, shapes, dev, a.iters, a.warmup) if a.clip else bench_steps(name, shapes, dev, a.iters, a.warmup))
         print(json.dumps(rows[-1]), flush=True)
         torch.cuda.empty_cache()
-    if a.step:
+    if a.step and a.clip:
+        rows.append(bench_train_step_clip(dev, a.size, a.clips, a.step_iters, a.warmup))
+        print(json.dumps(rows[-1]), flush=True)
+    elif a.step:
         rows.append(bench_train_step(dev, a.size, a.clips, a.step_iters, a.warmup))
         print(json.dumps(rows[-1]), flush=True)
     if a.json:
