@@ -75,19 +75,11 @@ def train_bn_forward(y, stats, gamma, beta, eps, momentum, running_mean, running
     return mi, out, amax_out
 
 
-def frozen_bn_backward(y, dout, scale, gamma, beta, act, slope):
+def frozen_bn_backward(y, dout, scale, gamma, beta, act, slope, want_sums=True):
     """Backward of out = act(scale*conv + shift) with BatchNorm folded from running statistics; y holds the activation (before a
-    shortcut add).  Returns (dconv, dgamma, dbeta)."""
-    c = y.shape[-1]
-    dz = ops.act_bwd(y, dout, slope) if act == ops.ACT_LEAKY else dout
-    dy = dz * scale
-    dbeta = dz.reshape(-1, c).sum(0)
-    # dgamma = sum(dz * (conv - rm) * rsqrt(rv+eps)); recover z = scale*conv + shift from y where the activation is invertible
-    # (leaky / none are; ReLU — slope 0 — keeps y): z = y>0 ? y : y/slope
-    z = y if (act != ops.ACT_LEAKY or slope == 0) else torch.where(y > 0, y, y / slope)
-    gsafe = torch.where(gamma == 0, torch.ones_like(gamma), gamma)
-    dgamma = (dz * (z - beta) / gsafe).reshape(-1, c).sum(0)
-    return dy, dgamma, dbeta
+    shortcut add), fp32 or — bf16 storage — bf16.  Returns (dconv, dgamma, dbeta), the last two None without ``want_sums`` (gamma and
+    beta frozen).  One pass of csrc/frozen_bn.h."""
+    return ops.frozen_bn_act_bwd(y, dout, scale, gamma, beta, act, slope, want_sums=want_sums)
 
 
 def bn_tap_for(b16: bool, training: bool, cin: int, ksize: int, stride: int, prev, gamma, beta, act, slope):

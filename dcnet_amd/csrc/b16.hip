@@ -8,6 +8,7 @@
 // Roofline: HBM — scale_act 4 B/element (6 with a shortcut), backward apply 6 B/element, reduce 4 B/element.
 #include "common.h"
 #include "prof.h"
+#include "frozen_bn.h"
 
 int bn_pc_enabled();         // bn.hip: dcn_set_tuning("Bpc", 0) turns the per-thread-channel apply passes off
 
@@ -509,6 +510,34 @@ extern "C" int dcn_bn_act_bwd_apply_b16(const void* y, int y_f32, const void* do
 #undef DCN_AP
   prof_end(pid, stream);
   DCN_CHECK_LAUNCH("bn_act_bwd_apply_b16");
+  return DCN_OK;
+}
+
+// dcn_frozen_bn_act_bwd on bf16 storage: a bf16, dout bf16 or fp32 (dout_f32; lddo in elements), dy bf16; the partial sums are taken
+// from the unrounded fp32 dz.  8 channels per thread (16-byte accesses on the bf16 tensors) where c and lddo allow, else 4.
+extern "C" int dcn_frozen_bn_act_bwd_b16(const void* a, const void* dout, int dout_f32, int lddo, const float* scale, const float* gamma,
+                                         const float* beta, int act, float slope, int64_t rows, int c, int want_sums, void* dy, float* stats,
+                                         void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (lddo <= 0) lddo = c;
+  DCN_CHECK_ARG(a && dout && scale && dy && rows > 0 && c > 0 && c % 4 == 0 && lddo % 4 == 0 && lddo >= c,
+                "frozen_bn_act_bwd_b16: bad argument (c=%d / lddo=%d must be multiples of 4)", c, lddo);
+  const int v = (c % 8 == 0 && lddo % 8 == 0) ? 8 : 4;
+  DCN_CHECK_ARG((((uintptr_t)a | (uintptr_t)dy) & (2 * v - 1)) == 0 && ((uintptr_t)dout & ((dout_f32 ? 4 : 2) * v - 1) & 15) == 0,
+                "frozen_bn_act_bwd_b16: a, dout, dy must be aligned to %d elements", v);
+  DCN_CHECK_ARG(!want_sums || (gamma && beta && stats), "frozen_bn_act_bwd_b16: want_sums needs gamma, beta and stats");
+  DCN_CHECK_ARG((((uintptr_t)scale | (uintptr_t)gamma | (uintptr_t)beta) & 3) == 0, "frozen_bn_act_bwd_b16: misaligned per-channel vector");
+  const int pal = ((((uintptr_t)scale | (want_sums ? (uintptr_t)gamma | (uintptr_t)beta : 0)) & 15) == 0) ? 1 : 0;
+  const int pid = prof_begin(45, (double)rows * c * (2.0 + (dout_f32 ? 4.0 : 2.0) + 2.0), stream);
+#define DCN_FZ(TD, V, S) hipLaunchKernelGGL((frozen_bn::frozen_bn_act_bwd_kernel<__bf16, TD, __bf16, V, S>), frozen_bn::frozen_grid(rows, c, V), dim3(256), 0, \
+    stream, (const __bf16*)a, (const TD*)dout, lddo, scale, gamma, beta, pal, act, slope, rows, c, (__bf16*)dy, stats, (unsigned*)nullptr)
+#define DCN_FZ2(TD) do { if (v == 8) { if (want_sums) DCN_FZ(TD, 8, true); else DCN_FZ(TD, 8, false); } \
+    else { if (want_sums) DCN_FZ(TD, 4, true); else DCN_FZ(TD, 4, false); } } while (0)
+  if (dout_f32) DCN_FZ2(float); else DCN_FZ2(__bf16);
+#undef DCN_FZ2
+#undef DCN_FZ
+  prof_end(pid, stream);
+  DCN_CHECK_LAUNCH("frozen_bn_act_bwd_b16");
   return DCN_OK;
 }
 

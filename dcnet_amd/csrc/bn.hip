@@ -4,6 +4,7 @@
 // fastest dim so per-channel parameters are read once per thread and stay in registers.
 #include "common.h"
 #include "prof.h"
+#include "frozen_bn.h"
 
 namespace {
 
@@ -544,5 +545,31 @@ extern "C" int dcn_act_bwd(const float* out, const float* dout, int lddo, float 
   hipLaunchKernelGGL(act_bwd_kernel, dim3(stream_grid(rows * (c / 4))), dim3(256), 0, (hipStream_t)stream,
                      out, dout, lddo, slope, rows, c, dy);
   DCN_CHECK_LAUNCH("act_bwd");
+  return DCN_OK;
+}
+
+// Backward of out = act(scale*conv + shift), BatchNorm folded from running statistics (frozen_bn.h has the arithmetic): dy and, with
+// want_sums, the [dcn_channel_stats_rows(rows)][2][c] partials of dbeta / dgamma in one pass over a and dout.
+extern "C" int dcn_frozen_bn_act_bwd(const float* a, const float* dout, int lddo, const float* scale, const float* gamma, const float* beta,
+                                     int act, float slope, int64_t rows, int c, int want_sums, float* dy, float* stats, uint32_t* amax,
+                                     void* stream_) {
+  hipStream_t stream = (hipStream_t)stream_;
+  if (lddo <= 0) lddo = c;
+  DCN_CHECK_ARG(a && dout && scale && dy && rows > 0 && c > 0 && c % 4 == 0 && lddo % 4 == 0 && lddo >= c,
+                "frozen_bn_act_bwd: bad argument (c=%d / lddo=%d must be multiples of 4)", c, lddo);
+  DCN_CHECK_ARG(aligned16(a, dout, dy), "frozen_bn_act_bwd: a, dout, dy must be 16-byte aligned");
+  DCN_CHECK_ARG(!want_sums || (gamma && beta && stats), "frozen_bn_act_bwd: want_sums needs gamma, beta and stats");
+  DCN_CHECK_ARG((((uintptr_t)scale | (uintptr_t)gamma | (uintptr_t)beta) & 3) == 0, "frozen_bn_act_bwd: misaligned per-channel vector");
+  const int pal = aligned16(scale, want_sums ? gamma : nullptr, want_sums ? beta : nullptr) ? 1 : 0;
+  const int pid = prof_begin(11, (double)rows * c * 4.0 * 3, stream);
+  const dim3 g = frozen_bn::frozen_grid(rows, c, 4);
+  if (want_sums)
+    hipLaunchKernelGGL((frozen_bn::frozen_bn_act_bwd_kernel<float, float, float, 4, true>), g, dim3(256), 0, stream, a, dout, lddo, scale, gamma,
+                       beta, pal, act, slope, rows, c, dy, stats, amax);
+  else
+    hipLaunchKernelGGL((frozen_bn::frozen_bn_act_bwd_kernel<float, float, float, 4, false>), g, dim3(256), 0, stream, a, dout, lddo, scale, gamma,
+                       beta, pal, act, slope, rows, c, dy, stats, amax);
+  prof_end(pid, stream);
+  DCN_CHECK_LAUNCH("frozen_bn_act_bwd");
   return DCN_OK;
 }

@@ -511,7 +511,8 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
             else:
                 # frozen statistics: y holds act(scale*conv+shift) before the shortcut add
                 if rec.scale is not None:       # folded BN: z = scale*conv + shift
-                    dy, dgamma, d["beta"] = convblock.frozen_bn_backward(y, dout, rec.scale, p["gamma"], p["beta"], act, 0.1)
+                    dy, dgamma, d["beta"] = convblock.frozen_bn_backward(y, dout, rec.scale, p["gamma"], p["beta"], act, 0.1,
+                                                                         want_sums=p["affine_grad"])
                     d["gamma"] = dgamma          # (behind beta: the order in which the reducer's sink sees them)
                 else:
                     dy = ops.act_bwd(y, dout, 0.1) if op.leaky else dout
@@ -561,17 +562,17 @@ class _DarknetFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, net: "Darknet", training: bool, image: torch.Tensor, *flat):
         plan, taps = net._plan, net._taps
-        P = net._param_table(flat)
+        P = net._param_table(flat, ctx.needs_input_grad[3:])
         x = ops.nchw_to_nhwc(image.contiguous(), 4)
         # (needs_input_grad speaks about the parameters, not about the caller's grad mode: under torch.no_grad() — inference — nothing is
         #  saved and every layer is ONE kernel with BatchNorm, activation and shortcut in its epilogue; forward_nhwc notes the mode, since
         #  inside a Function's forward grad mode is always off)
         need_grad = any(ctx.needs_input_grad[3:]) and bool(net.__dict__.get("_grad_on", True))
         ctx.no_backward_reason = None if need_grad else "nothing was saved: the forward ran with gradients off (or no parameter requires one)"
-        if ops.storage_b16() and not training:
-            need_grad = False          # bf16 storage has no frozen-BatchNorm backward: inference only in eval mode (backward() says so)
-            ctx.no_backward_reason = ("bf16 storage has no backward in eval mode (frozen-BatchNorm fine-tuning is not built); "
-                                      "train with .train(), or use the fp32 precision mode")
+        if ops.storage_f8() and not training and need_grad:
+            need_grad = False          # fp8 storage has no frozen-BatchNorm backward: inference only with running statistics (backward() says so)
+            ctx.no_backward_reason = ("fp8 storage has no backward with BatchNorm on its running statistics (eval mode, freeze_batchnorm): "
+                                      "fp32 and bf16 storage (\"bf16s\") have it")
         save = {} if need_grad else None
         outs, tap_amax, net._early_event = _run_forward(plan, taps, x, P, training, save, net._filter_banks(P),
                                                         taps_b16=bool(net.__dict__.get("_taps_b16")))
@@ -590,7 +591,7 @@ class _DarknetFn(torch.autograd.Function):
         if ctx.save is None:
             why = getattr(ctx, "no_backward_reason", None) or ("this node's saved tensors were consumed by an earlier backward "
                                                                "(one backward per forward; retain_graph is not supported)")
-            raise (NotImplementedError if "bf16" in why else RuntimeError)("dcnet_amd.Darknet: " + why)
+            raise (NotImplementedError if "fp8 storage" in why else RuntimeError)("dcnet_amd.Darknet: " + why)
         outs = ctx.saved_tensors
         save = ctx.save
         ctx.save = None
@@ -650,18 +651,23 @@ class Darknet(nn.Module):
                 flat.append(conv.bias)
         return flat
 
-    def _param_table(self, flat):
+    def _param_table(self, flat, needs=None):
+        """needs (optional): per entry of ``flat``, does it need a gradient (default: all do)."""
         P = {}
         it = iter(flat)
+        nd = iter(needs if needs is not None else [True] * len(flat))
         for op in self._conv_ops:
             seq = self.module_list[op.slot]
-            d = dict(w=next(it).detach(), b=None, gamma=None, beta=None, rm=None, rv=None, momentum=0.1)
+            d = dict(w=next(it).detach(), b=None, gamma=None, beta=None, rm=None, rv=None, momentum=0.1, affine_grad=True)
+            next(nd)
             if op.bn:
                 bn = seq[1]
                 d["gamma"], d["beta"] = next(it).detach(), next(it).detach()
+                d["affine_grad"] = bool(next(nd)) | bool(next(nd))      # (frozen statistics: False = no partial sums in the backward)
                 d["rm"], d["rv"], d["momentum"] = bn.running_mean, bn.running_var, bn.momentum
             else:
                 d["b"] = next(it).detach()
+                next(nd)
             P[op.slot] = d
         return P
 
@@ -703,10 +709,25 @@ class Darknet(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("dcnet_amd.Darknet runs on an MI355X only: move the model and inputs to cuda "
                                "(there is no CPU path; the CPU restatement lives in oracle/ for tests)")
-        training = self.training
+        training = self.training and not self.__dict__.get("_bn_frozen", False)      # (the BatchNorm mode is all that `training` means here)
         if training:
             torch._foreach_add_([self.module_list[op.slot][1].num_batches_tracked for op in self._conv_ops if op.bn], 1)
         return list(_DarknetFn.apply(self, training, x, *self._flat_params()))
+
+    def freeze_batchnorm(self, frozen: bool = True) -> None:
+        """Hold every BatchNorm of the backbone at its running statistics whatever ``.training`` says (grounding_model.freeze_batchnorm):
+        the forward normalises with them and leaves them and num_batches_tracked alone, the backward is the frozen one, and the
+        nn.BatchNorm2d modules report ``.training == False``.  Survives train() / eval()."""
+        self.__dict__["_bn_frozen"] = bool(frozen)
+        self.train(self.training)
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        if self.__dict__.get("_bn_frozen", False):
+            for m in self.modules():
+                if isinstance(m, nn.modules.batchnorm._BatchNorm):
+                    m.training = False
+        return self
 
     def forward(self, x, targets=None):
         if targets is not None:

@@ -15,13 +15,17 @@ class ConvBNAct(torch.autograd.Function):
     + ReLU.  x may carry zero-padded channels beyond the weight's Cin (K-padding to 32)."""
 
     @staticmethod
-    def forward(ctx, x, weight, gamma, beta, bn, ksize: int, training: bool, slope: float, amax_x=None, bank=None, out_b16: bool = False):
+    def forward(ctx, x, weight, gamma, beta, bn, ksize: int, training: bool, slope: float, amax_x=None, bank=None, out_b16: bool = False,
+                grad_on: bool = True):
         """Returns (out, amax_out): amax_* are the abs-max words of ops.amax_* (None outside the f16-split precision).
         bank: this layer's entry of an ops.FilterBanks table refreshed this step (OHWI / split / transposed banks + abs-max word):
         nothing is transposed, measured or split per launch then.
         bf16-storage mode (ops.storage_b16(), a bank given): the block runs on bf16 tensors — x bf16 (an fp32 x is cast once), raw result
         and saved tensors bf16, out bf16 when ``out_b16`` (the consumer is another bf16 block) else fp32, written by the BatchNorm pass
-        itself; the input gradient comes back in x's dtype straight from the data-gradient kernel."""
+        itself; the input gradient comes back in x's dtype straight from the data-gradient kernel.
+        training = the BatchNorm mode: False normalises with the running statistics (eval mode, grounding_model.freeze_batchnorm) and
+        keeps the activation for the frozen backward — unless ``grad_on`` is False (the caller runs under torch.no_grad(), which cannot
+        be seen from inside a Function's forward)."""
         cout = weight.shape[0]
         am = ops.use_amax()
         if bank is not None and x.shape[3] != weight.shape[1]:
@@ -50,7 +54,11 @@ class ConvBNAct(torch.autograd.Function):
                                                                                        bn.running_var, bn.eps),
                                               act=ops.ACT_LEAKY, slope=slope, out_f32=not out_b16, amax_x=ax, amax_w=aw, amax_out=ao, w_split=wsp)
             y = out
-        if training or not ctx.b16:        # (bf16 storage has no backward in eval mode: nothing is kept)
+            if ctx.b16 and ops.storage_f8():
+                y = None                   # (fp8 storage has no backward with frozen statistics: nothing is kept, backward() says so)
+            elif ctx.b16 and grad_on and any(ctx.needs_input_grad[:4]):
+                y = ops.to_b16(out)        # bf16 storage keeps the activation in 2 bytes (out itself when the next block reads bf16)
+        if y is not None:
             ctx.save_for_backward(x, y, aux, w, gamma, beta)
         ctx.bank = bank
         ctx.meta = (ksize, training, slope, tuple(weight.shape))
@@ -63,8 +71,9 @@ class ConvBNAct(torch.autograd.Function):
     def backward(ctx, dout, _ga=None):
         """bf16 storage: dout bf16 or fp32 (read as it is), dy / saved tensors bf16, dw fp32."""
         ksize, training, slope, wshape = ctx.meta
-        if ctx.b16 and not training:
-            raise NotImplementedError("ConvBNAct, bf16 storage: no backward in eval mode (frozen-BatchNorm fine-tuning is not built)")
+        if ctx.b16 and not training and not ctx.saved_tensors:
+            raise NotImplementedError("ConvBNAct, fp8 storage: no backward with BatchNorm on its running statistics (eval mode, "
+                                      "freeze_batchnorm); fp32 and bf16 storage (\"bf16s\") have it")
         x, y, aux, w, gamma, beta = ctx.saved_tensors
         gamma, beta = gamma.detach(), beta.detach()
         ax, aw = ctx.amax
@@ -76,7 +85,8 @@ class ConvBNAct(torch.autograd.Function):
             dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, aux[0], aux[1], gamma, beta, ops.ACT_LEAKY, slope, amax_out=ady,
                                                quant=ctx.needs_input_grad[0] and ops.f8_takes(y.shape[3], x.shape[3], ksize))
         else:
-            dy, dgamma, dbeta = convblock.frozen_bn_backward(y, dout, aux[0], gamma, beta, ops.ACT_LEAKY, slope)
+            dy, dgamma, dbeta = convblock.frozen_bn_backward(y, dout, aux[0], gamma, beta, ops.ACT_LEAKY, slope,
+                                                             want_sums=ctx.needs_input_grad[2] or ctx.needs_input_grad[3])
 
         def dgrad():
             if not ctx.needs_input_grad[0]:
@@ -89,7 +99,7 @@ class ConvBNAct(torch.autograd.Function):
         dx, dwt = convblock.schedule_wgrad(x, dy, ksize, 1, wshape, dgrad, amax_x=ax, amax_dy=ady, direct_into=ctx.wparam)
         if ctx.wparam is None:
             ops.join_side(x.device)
-        return dx, dwt, dgamma, dbeta, None, None, None, None, None, None, None
+        return dx, dwt, dgamma, dbeta, None, None, None, None, None, None, None, None
 
 
 class ConvBias(torch.autograd.Function):
@@ -487,7 +497,8 @@ class FusionConvBNAct(torch.autograd.Function):
             ady = ops.amax_slot(dout.device) if ops.use_amax() else None
             dy, dgamma, dbeta = ops.bn_act_bwd(y, dout, aux[0], aux[1], gamma, beta, ops.ACT_LEAKY, 0.0, amax_out=ady)      # (bf16 storage: dy bf16)
         else:
-            dy, dgamma, dbeta = convblock.frozen_bn_backward(y, dout, aux[0], gamma, beta, ops.ACT_LEAKY, 0.0)
+            dy, dgamma, dbeta = convblock.frozen_bn_backward(y, dout, aux[0], gamma, beta, ops.ACT_LEAKY, 0.0,
+                                                             want_sums=ctx.needs_input_grad[4] or ctx.needs_input_grad[5])
         wd = weight.detach().view(co, -1)
 
         def dgrad():
@@ -641,7 +652,8 @@ class BatchNormRowsAct(torch.autograd.Function):
         if ctx.training:
             dx, dgamma, dbeta = ops.bn_act_bwd(a, dout, aux[0], aux[1], gamma, beta, act, 0.0)
         else:
-            dx, dgamma, dbeta = convblock.frozen_bn_backward(a, dout, aux[0], gamma, beta, act, 0.0)
+            dx, dgamma, dbeta = convblock.frozen_bn_backward(a, dout, aux[0], gamma, beta, act, 0.0,
+                                                             want_sums=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
         return dx, dgamma, dbeta, None, None, None
 
 

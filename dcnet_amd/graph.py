@@ -17,6 +17,9 @@ update (``dcnet_amd.optim``: RMSprop, Adam or SGD) — and replays them with one
 Data-parallel runs capture forward + backward only; the gradient all-reduce (one flat RCCL all-reduce,
 ``parallel.FlatGradAllReduce``) and the optimiser step follow the replay eagerly — no collective is captured.
 
+``grounding_model.freeze_batchnorm`` is respected as it stands: the setting survives the ``model.train()`` below, frozen layers run
+their frozen forward and backward inside the capture, their running statistics are not written.
+
 Everything else is unchanged: the same kernels in the same order on the same streams, so a replayed step is bitwise equal to
 an eager one (tests/test_graph_gpu.py).
 """

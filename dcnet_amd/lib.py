@@ -61,6 +61,7 @@ SIGNATURES = {
     "dcn_bn_bwd_sums": (I, [P, I, I, P, P, P]),
     "dcn_bn_act_bwd_apply": (I, [P, P, I, P, P, P, P, I, F, P, L, L, I, P, P, P]),
     "dcn_act_bwd": (I, [P, P, I, F, L, I, P, P]),
+    "dcn_frozen_bn_act_bwd": (I, [P, P, I, P, P, P, I, F, L, I, I, P, P, P, P]),
     "dcn_coattn_e_size": (L, [I, I]),
     "dcn_coattn_saved_size": (L, [I, I, I]),
     "dcn_coattn_fwd_ws": (L, [I, I, I]),
@@ -160,6 +161,7 @@ SIGNATURES = {
     "dcn_bn_act_bwd_reduce_rows_b16": (I, [L]),
     "dcn_bn_act_bwd_reduce_b16": (I, [P, I, P, I, I, P, P, P, P, I, F, L, I, P, P]),
     "dcn_bn_act_bwd_apply_b16": (I, [P, I, P, I, I, P, P, P, P, I, F, P, L, L, I, P, P]),
+    "dcn_frozen_bn_act_bwd_b16": (I, [P, P, I, I, P, P, P, I, F, L, I, I, P, P, P]),
     "dcn_cast_rows": (I, [P, I, I, P, I, I, L, I, I, P]),
     "dcn_upsample2_nhwc_b16": (I, [P, I, P, I, I, I, I, I, P]),
     "dcn_upsample2_nhwc_bwd_b16": (I, [P, I, P, I, I, I, I, I, I, P]),
@@ -182,7 +184,7 @@ _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",
                 "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes",
                 "dcn_conv1_tile", "dcn_l2norm_score_fwd_form", "dcn_bn_apply_form", "dcn_igemm_split_build", "dcn_gemm3_variant"}
-ABI_VERSION = 314        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
+ABI_VERSION = 315        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
 
 
 class DcnError(RuntimeError):

@@ -74,8 +74,9 @@ class ConvBatchNormReLU(nn.Sequential):
         if x_nhwc.dtype == torch.bfloat16 and not ops.storage_b16():
             x_nhwc = ops.to_f32(x_nhwc)          # (a bf16 producer in front of an fp32 block: mixed-precision experiments, ops.region)
         out, a = ConvBNAct.apply(x_nhwc, self.conv.weight, self.bn.weight, self.bn.bias, self.bn,
-                                 self.conv.kernel_size[0], self.training, self.slope, amax, self.__dict__.get("_dcn_bank"),
-                                 bool(self.__dict__.get("_dcn_out_b16")))          # (bf16-storage mode: the next block reads bf16)
+                                 self.conv.kernel_size[0], self.bn.training, self.slope, amax, self.__dict__.get("_dcn_bank"),
+                                 bool(self.__dict__.get("_dcn_out_b16")),          # (bf16-storage mode: the next block reads bf16)
+                                 torch.is_grad_enabled())
         out._dcn_amax = a
         return out
 
@@ -252,6 +253,38 @@ class grounding_model(nn.Module):
         self.last_choices = {}
 
     # ------------------------------------------------------------------------------------------
+    def freeze_batchnorm(self, scope: Optional[str] = "backbone", train_affine: bool = True):
+        """Train with BatchNorm held at its running statistics (the usual remedy for small per-GPU batches on a pretrained backbone).
+        scope: "backbone" (``visumodel``), "all" (also the ConvBatchNormReLU blocks, the fusion block, mapping_lang's two BatchNorm1d
+        and the two location BatchNorms) or None (undo).  In-scope layers normalise with their running statistics, leave them and
+        num_batches_tracked untouched, take the frozen backward (csrc/frozen_bn.h), and their nn.BatchNorm* modules report
+        ``.training == False``; everything else about train mode stays (the 11 outputs, the sampling heads, dropout).  The setting
+        survives train() / eval().  train_affine=False also stops the gradients of the in-scope gamma and beta (requires_grad False,
+        ``.grad`` None, no partial sums in the backward); freeze_batchnorm(None) — or another call — gives them back.  Returns self."""
+        if scope not in ("backbone", "all", None):
+            raise ValueError(f"freeze_batchnorm: scope {scope!r}: expected 'backbone', 'all' or None")
+        for p_ in self.__dict__.pop("_bn_affine_off", []):
+            p_.requires_grad_(True)
+        self.__dict__["_bn_scope"] = scope
+        self.visumodel.freeze_batchnorm(scope is not None)
+        if scope is not None and not train_affine:
+            off = [p_ for m in self._frozen_bn_modules() for p_ in (m.weight, m.bias) if p_ is not None and p_.requires_grad]
+            for p_ in off:
+                p_.requires_grad_(False)
+            self.__dict__["_bn_affine_off"] = off
+        return self.train(self.training)
+
+    def _frozen_bn_modules(self):
+        scope = self.__dict__.get("_bn_scope")
+        root = self if scope == "all" else self.visumodel if scope == "backbone" else None
+        return [] if root is None else [m for m in root.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+
+    def train(self, mode: bool = True):
+        super().train(mode)
+        for m in self._frozen_bn_modules():      # (freeze_batchnorm: these stay on their running statistics)
+            m.training = False
+        return self
+
     def finish_backward(self) -> None:
         """Second half of a backward pass when ``defer_language_backward`` is set: the language branch's backward, on its own stream,
         from the gradients loss.backward() left on the detached leaves.  The caller's stream waits for it."""
@@ -337,10 +370,10 @@ class grounding_model(nn.Module):
         raw_flang, context, embedded = self.textmodel(word_id)                  # DCNet_model.py:474-476 (untrimmed, see RNNEncoder)
         ml = self.mapping_lang                                                  # Linear, BN1d, ReLU, Dropout, Linear, BN1d, ReLU
         z = LinearAct.apply(raw_flang, ml[0].weight, ml[0].bias, False)
-        z = BatchNormRowsAct.apply(z, ml[1].weight, ml[1].bias, ml[1], self.training, True)
+        z = BatchNormRowsAct.apply(z, ml[1].weight, ml[1].bias, ml[1], ml[1].training, True)
         z = ml[3](z)
         z = LinearAct.apply(z, ml[4].weight, ml[4].bias, False)
-        z = BatchNormRowsAct.apply(z, ml[5].weight, ml[5].bias, ml[5], self.training, True)
+        z = BatchNormRowsAct.apply(z, ml[5].weight, ml[5].bias, ml[5], ml[5].training, True)
         flang = L2Norm.apply(z)                                                 # :485-487 F.normalize(dim=1), csrc/score.hip
         return word_id, flang, context, embedded
 
@@ -351,7 +384,7 @@ class grounding_model(nn.Module):
         blk0 = self.fcn_emb[s][0]                                                # [corr | tile(flang) | coord] -> 1x1
         one = ops.amax_const(corr.device, 1.0) if ops.use_amax() else None        # corr is L2-normalised: |x| <= 1
         z, za = FusionConvBNAct.apply(corr.contiguous(), flang, self._coord(h, w, corr.device), blk0.conv.weight,
-                                      blk0.bn.weight, blk0.bn.bias, blk0.bn, self.training, one)
+                                      blk0.bn.weight, blk0.bn.bias, blk0.bn, blk0.bn.training, one)
         z._dcn_amax = za
         chain = list(self.fcn_emb[s])[1:] + list(self.fcn_out[s])[:-1]           # (none of them with light=True)
         if ops.storage_b16() and self.training and chain and (not ops.FILTER_BANKS or (self.emb_size // 2) % 32):
@@ -432,7 +465,7 @@ class grounding_model(nn.Module):
         coord = self._coord_rows([(l.shape[1], l.shape[2]) for l in logits], dev)
         le, lt = self.loc_embedding, self.loc_text_embedding
         res = HeadTail.apply(*logits, *sim_score, flang_loc, coord, le[0].weight, le[0].bias, le[1].weight, le[1].bias,
-                             lt[0].weight, lt[0].bias, lt[1].weight, lt[1].bias, le[1], lt[1], self.training)
+                             lt[0].weight, lt[0].bias, lt[1].weight, lt[1].bias, le[1], lt[1], le[1].training and lt[1].training)
         return list(res[0:3]), list(res[3:6]), list(res[6:9])
 
     # ------------------------------------------------------------------------------------------

@@ -1072,6 +1072,46 @@ def act_bwd(out, dout, slope):
     return dy
 
 
+def frozen_bn_act_bwd(a, dout, scale, gamma, beta, act, slope, want_sums=True, amax_out=None):
+    """Backward of out = act(scale*conv + shift) with BatchNorm folded from its running statistics, in one pass (csrc/frozen_bn.h):
+    a = the saved activation (before a shortcut add), dout = the gradient w.r.t. it (row stride dout.stride(-2): a channel slice of a wider
+    gradient is read in place).  Returns (dy, dgamma, dbeta); want_sums=False (neither gamma nor beta needs a gradient): (dy, None, None),
+    no partial sums are formed.  fp32 a: dy fp32, amax_out (optional) receives its abs-max word.  bf16 a (bf16 storage): dout bf16 or
+    fp32, dy bf16."""
+    c = a.shape[-1]
+    rows = a.numel() // c
+    dev = a.device
+    if not (a.is_cuda and a.is_contiguous() and dout.is_cuda and _rows_ok(dout) and dout.shape[-1] == c and dout.numel() // c == rows):
+        raise ValueError(f"frozen_bn_act_bwd: contiguous a and a [rows][c] view dout of the same shape, got {tuple(a.shape)} and "
+                         f"{tuple(dout.shape)} strides {dout.stride()}")
+    if c % 4 or dout.stride(-2) % 4:
+        raise ValueError(f"frozen_bn_act_bwd: c = {c} and the row stride of dout ({dout.stride(-2)}) must be multiples of 4")
+    for t_ in (scale, gamma, beta):
+        if t_ is not None and not (t_.is_cuda and t_.dtype == torch.float32 and t_.is_contiguous() and t_.numel() == c):
+            raise ValueError("frozen_bn_act_bwd: scale, gamma, beta are contiguous fp32 vectors of c elements")
+    if not _b16(a) and _b16(dout):
+        dout = to_f32(dout)
+    part = r = None
+    if want_sums:
+        r = lib().channel_stats_rows(rows)
+        part = scratch(r * 2 * c, dev, slot=0)
+    if _b16(a):
+        dy = torch.empty(a.shape, dtype=torch.bfloat16, device=dev)
+        lib().frozen_bn_act_bwd_b16(a.data_ptr(), dout.data_ptr(), int(not _b16(dout)), dout.stride(-2), scale.data_ptr(), _p(gamma), _p(beta),
+                                    act, float(slope), rows, c, int(bool(want_sums)), dy.data_ptr(), _p(part), _s())
+    else:
+        _chk(a, "frozen_bn_act_bwd a")
+        dy = torch.empty_like(a)
+        lib().frozen_bn_act_bwd(a.data_ptr(), dout.data_ptr(), dout.stride(-2), scale.data_ptr(), _p(gamma), _p(beta), act, float(slope),
+                                rows, c, int(bool(want_sums)), dy.data_ptr(), _p(part), _p(amax_out), _s())
+    if not want_sums:
+        return dy, None, None
+    sums = torch.empty((2, c), dtype=torch.float32, device=dev)
+    ws = scratch(lib().bn_ws(c), dev, slot=2)
+    lib().bn_bwd_sums(part.data_ptr(), r, c, sums.data_ptr(), ws.data_ptr(), _s())
+    return dy, sums[1], sums[0]
+
+
 # ---- co-attention -----------------------------------------------------------------------------------
 def coattn_fwd(f1, f2, out1, out2, temperature):
     """f1,f2 (b,hw,c) views with pixel stride ldf (last dim contiguous); out1/out2 (b,hw,c) views with

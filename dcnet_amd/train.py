@@ -8,7 +8,7 @@ to drive ``grounding_model`` without the reference's data pipeline (SURVEY.md §
   * ``save_checkpoint`` / ``load_checkpoint`` / ``load_pretrain``   the reference's ``.pth.tar`` dict
     (train_DCNet.py:255-263, 485-514) including the ``module.`` key prefix left by DDP wrappers
 
-``python -m dcnet_amd.train --steps 20`` runs a short synthetic-data training loop on one GPU; with ``--raw-frames`` every step's
+``python -m dcnet_amd.train --steps 20`` (``--freeze-bn backbone|all``: BatchNorm on its running statistics) runs a short synthetic-data training loop on one GPU; with ``--raw-frames`` every step's
 ``image`` / ``bbox`` come from synthetic uint8 frames of mixed sizes (1280x720 and 500x375) through the on-device clip
 preprocessing (``dcnet_amd.prep.prepare_clips``: flip, HSV, letterbox, affine, normalisation), as real decoded frames would.
 """
@@ -157,7 +157,18 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--raw-frames", action="store_true", help="feed uint8 frames through dcnet_amd.prep every step")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X", help="clip the global gradient norm to X inside the fused step")
     ap.add_argument("--skip-nonfinite", action="store_true", help="a step whose gradient norm is inf or NaN updates nothing")
+    ap.add_argument("--freeze-bn", choices=["none", "backbone", "all"], default="none",
+                    help="hold BatchNorm at its running statistics while training (grounding_model.freeze_batchnorm): the backbone's, or every one")
+    ap.add_argument("--freeze-bn-stats-only", action="store_true",
+                    help="with --freeze-bn: freeze the statistics only, gamma and beta keep training (train_affine=True; default: they are frozen too)")
     return ap
+
+
+def freeze_bn_args(args) -> Optional[dict]:
+    """The freeze_batchnorm() arguments that --freeze-bn / --freeze-bn-stats-only ask for (None: leave BatchNorm alone)."""
+    if args.freeze_bn == "none":
+        return None
+    return dict(scope=args.freeze_bn, train_affine=bool(args.freeze_bn_stats_only))
 
 
 def main(argv: Optional[Iterable[str]] = None) -> None:
@@ -169,6 +180,9 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     torch.manual_seed(0); random.seed(0)
     model = grounding_model(corpus=list(range(1000)), emb_size=512, img_size=args.size, config_path="", weights_path=None).to(dev)
     freeze_gradless(model)
+    fz = freeze_bn_args(args)
+    if fz is not None:
+        model.freeze_batchnorm(**fz)
     opt = make_optimizer(model, args.lr, args.optimizer, max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
     n = args.clips * args.frames
     image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, args.size, seed=1))

@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 314
+#define DCN_ABI_VERSION 315
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -271,6 +271,18 @@ int dcn_bn_act_bwd_apply(const float* y, const float* dout, int lddo, const floa
                          const float* sums, int64_t count, int64_t rows, int c, float* dy, uint32_t* amax, void* stream);
 /* Backward of out = act(z) alone: dy = dout * (out > 0 ? 1 : slope). */
 int dcn_act_bwd(const float* out, const float* dout, int lddo, float slope, int64_t rows, int c, float* dy, void* stream);
+/* ABI 315: backward of out = act(scale[c]*conv + shift[c]) with BatchNorm folded from its running statistics (dcn_bn_fold), in ONE pass
+ * over the saved activation a [rows][c] (before a shortcut add) and dout (pixel stride lddo):
+ *   dz = dout * (a <= 0 ? slope : 1)   (dcn_act_bwd's rule; DCN_ACT_NONE: dz = dout),   dy = dz * scale   [rows][c]
+ *   want_sums: stats [dcn_channel_stats_rows(rows)][2][c], to be summed by dcn_bn_bwd_sums into sums[0] = dbeta = sum dz and
+ *   sums[1] = dgamma = sum dz * (z - beta) / gamma, z = a > 0 ? a : a / slope (LeakyReLU; a itself for ReLU / none); gamma == 0
+ *   divides by 1.  want_sums = 0 (neither gamma nor beta needs a gradient): gamma, beta, stats are not touched and may be NULL.
+ * amax (optional): abs-max word of dy.  c, lddo multiples of 4; a, dout, dy 16-byte aligned; scale, gamma, beta need only 4.
+ * Frozen-BatchNorm fine-tuning (grounding_model.freeze_batchnorm) and the eval-mode backward; the autograd of F.batch_norm(training=False)
+ * + LeakyReLU / ReLU at model/darknet.py:189-191 and model/DCNet_model.py:258-259,270,274.  Called through
+ * dcnet_amd/convblock.py frozen_bn_backward by darknet._run_backward, functions.ConvBNAct, the fusion block and BatchNormRowsAct. */
+int dcn_frozen_bn_act_bwd(const float* a, const float* dout, int lddo, const float* scale, const float* gamma, const float* beta,
+                          int act, float slope, int64_t rows, int c, int want_sums, float* dy, float* stats, uint32_t* amax, void* stream);
 
 /* ---- inter-frame co-attention ----------------------------------------------------------- */
 /* f1,f2: [b][hw][c] NHWC (pixel stride ldf), unit L2 norm over c.  With A[i,j] = <f1_i, f2_j>:
@@ -503,6 +515,11 @@ int dcn_bn_act_bwd_reduce_b16(const void* y, int y_f32, const void* dout, int do
 int dcn_bn_act_bwd_apply_b16(const void* y, int y_f32, const void* dout, int dout_f32, int lddo, const float* mean, const float* invstd,
                              const float* gamma, const float* beta, int act, float slope, const float* sums, int64_t count,
                              int64_t rows, int c, void* dy, void* stream);
+/* ABI 315: dcn_frozen_bn_act_bwd on bf16 storage: a, dy bf16; dout bf16 or fp32 (dout_f32; lddo in elements); the partial sums are taken
+ * from the unrounded fp32 dz.  Same call sites, with ops.PRECISION "bf16s". */
+int dcn_frozen_bn_act_bwd_b16(const void* a, const void* dout, int dout_f32, int lddo, const float* scale, const float* gamma,
+                              const float* beta, int act, float slope, int64_t rows, int c, int want_sums, void* dy, float* stats,
+                              void* stream);
 /* dst[r][:c] (+)= src[r][:c], element types by flag (0 fp32, 1 bf16), element strides lds / ldd: casts at the fp32 boundary,
  * channel-slice copies of the route concat and their accumulating backward. */
 int dcn_cast_rows(const void* src, int src_b16, int lds, void* dst, int dst_b16, int ldd, int64_t rows, int c, int accumulate,
