@@ -66,15 +66,112 @@ void base_params(IgemmParams& p) {
   p.osy = p.osx = 1; p.isy = p.isx = 1; p.dense_out = 1;
 }
 
+// "same" padding, taps and output size of a k x k convolution over an h x wd map
+struct ConvShape {
+  int pad, T, ho, wo;
+  ConvShape(int h, int wd, int ksize, int stride)
+      : pad((ksize - 1) / 2), T(ksize * ksize), ho((h + 2 * pad - ksize) / stride + 1), wo((wd + 2 * pad - ksize) / stride + 1) {}
+};
+
+// forward: y[i,j] = sum_{r,s} x[i*stride + r - pad, j*stride + s - pad] . w[:,r,s,:]
+void fwd_geometry(IgemmParams& p, int n, int h, int wd, int cin, int cout, int ksize, int stride, int ldy, int ldr) {
+  const ConvShape g(h, wd, ksize, stride);
+  p.N = n; p.Hi = h; p.Wi = wd; p.Ci = cin; p.ldi = cin;
+  p.Ho = g.ho; p.Wo = g.wo; p.Hs = g.ho; p.Ws = g.wo; p.isy = p.isx = stride;
+  p.Co = cout; p.ldo = ldy > 0 ? ldy : cout; p.ldr = ldr > 0 ? ldr : cout;
+  p.M = n * g.ho * g.wo; p.ntaps = g.T;
+  if (cin == 4) {       // the stem: weights are [Co][64], 9 taps x 4 channels then zero padding (host prepares them); no tap table
+    p.ldw = 64;
+    return;
+  }
+  p.ldw = g.T * cin;
+  for (int r = 0; r < ksize; ++r)
+    for (int s = 0; s < ksize; ++s) {
+      const int t = r * ksize + s;
+      p.tap_dy[t] = r - g.pad; p.tap_dx[t] = s - g.pad; p.tap_w[t] = t * cin;
+    }
+}
+
+// data gradient: a convolution of dy (n x ho x wo x cout, pixel stride lddy) with the transposed bank [cin][T][cout] towards dx (dense)
+void dgrad_geometry(IgemmParams& p, const ConvShape& g, int n, int h, int wd, int cin, int cout, int lddy, int accumulate) {
+  p.N = n; p.Hi = g.ho; p.Wi = g.wo; p.Ci = cout; p.ldi = lddy;
+  p.Ho = h; p.Wo = wd; p.Co = cin; p.ldo = cin; p.ldr = cin; p.ldw = g.T * cout;
+  p.accumulate = accumulate;
+}
+
+// ... at stride 1 (p: as dgrad_geometry left it): dx[hi,wi] = sum_{r,s} dy[hi+pad-r, wi+pad-s] . w[:,r,s,:]
+void dgrad_s1_taps(IgemmParams& p, const ConvShape& g, int ksize) {
+  p.Hs = p.Ho; p.Ws = p.Wo; p.M = p.N * p.Ho * p.Wo; p.ntaps = g.T;
+  for (int r = 0; r < ksize; ++r)
+    for (int s = 0; s < ksize; ++s) {
+      const int t = r * ksize + s;
+      p.tap_dy[t] = g.pad - r; p.tap_dx[t] = g.pad - s; p.tap_w[t] = t * p.Ci;
+    }
+}
+
+// A stride-1 data gradient IS a forward convolution on the transposed bank, so the statistics epilogues can take a BatchNorm tap: the
+// launch goes out with it when there is one and its buffer holds the `rows` partial rows (one per M-tile) of this launch, and without
+// statistics otherwise (the caller reduces by itself).  launch: the engine, IgemmParams -> rc.
+template <class Launch>
+int dgrad_s1_launch(IgemmParams& p, const DcnBnTap* tap, int rows, int* tap_rows, Launch launch) {
+  if (!tap || rows <= 0 || tap->stats_rows < rows) {
+    p.stats = nullptr;
+    return launch(p);
+  }
+  p.stats = tap->stats; p.bt_y = tap->y; p.bt_mean = tap->mean; p.bt_invstd = tap->invstd; p.bt_gamma = tap->gamma; p.bt_beta = tap->beta;
+  p.bt_act = tap->act; p.bt_slope = tap->slope;
+  const int rc = launch(p);
+  if (rc == DCN_OK && tap_rows) *tap_rows = rows;
+  return rc;
+}
+
+// stride 2: the output pixels (2i + a, 2j + b) of parity class (a, b) only see the taps with (a + pad - r) and (b + pad - s) even, at
+// dy pixel (i + (a + pad - r) / 2, j + (b + pad - s) / 2).  Writes them into the caller's slots, returns how many: 1 / 2 / 2 / 4 of a
+// 3x3 filter, 1 / 0 / 0 / 0 of a 1x1.
+int parity_class_taps(int a, int b, int ksize, int pad, int cout, int* tap_dy, int* tap_dx, int* tap_w) {
+  int nt = 0;
+  for (int r = 0; r < ksize; ++r)
+    for (int s = 0; s < ksize; ++s) {
+      if (((a + pad - r) & 1) || ((b + pad - s) & 1)) continue;
+      tap_dy[nt] = (a + pad - r) / 2; tap_dx[nt] = (b + pad - s) / 2; tap_w[nt] = (r * ksize + s) * cout;
+      ++nt;
+    }
+  return nt;
+}
+
+// stride-2 data gradient, one launch per parity class (p: as dgrad_geometry left it): four dense sub-problems instead of one 9-tap
+// problem that is 3/4 zeros.  launch: the engine, IgemmParams -> rc; who / elem: the entry point's name and the bytes per element of dx.
+template <class Launch>
+int dgrad_s2_per_class(const IgemmParams& p, int ksize, int pad, const char* who, int elem, Launch launch, hipStream_t stream) {
+  // 1x1: only the even-even pixels receive a gradient; the other three classes have no tap and are never visited below, so
+  // they must be zeroed here (not a DCNet layer shape, but the entry points are general).
+  if (ksize == 1 && !p.accumulate &&
+      hipMemsetAsync(p.out, 0, (size_t)p.N * p.Ho * p.Wo * p.Co * elem, stream) != hipSuccess) {
+    dcn_set_error("%s: memset failed", who); return DCN_ERR_LAUNCH;
+  }
+  for (int a = 0; a < 2; ++a)
+    for (int b = 0; b < 2; ++b) {
+      IgemmParams q = p;
+      q.dense_out = 0; q.oy0 = a; q.ox0 = b; q.osy = q.osx = 2;
+      q.Hs = (p.Ho - a + 1) / 2; q.Ws = (p.Wo - b + 1) / 2;
+      if (q.Hs <= 0 || q.Ws <= 0) continue;        // a one-row / one-column map has no odd class
+      q.M = p.N * q.Hs * q.Ws;
+      q.ntaps = parity_class_taps(a, b, ksize, pad, p.Ci, q.tap_dy, q.tap_dx, q.tap_w);
+      if (q.ntaps == 0) continue;
+      const int rc = launch(q);
+      if (rc != DCN_OK) return rc;
+    }
+  return DCN_OK;
+}
+
 }  // namespace
 
 DCN_KNOB(g_n1_b16, "Nb16", 1, "conv.hip: bf16-storage 32 <-> 64 3x3 layers on the register-bank kernels of nconv.hip (0 = gathered tiles of conv1.hip)");
 DCN_KNOB(g_d2_b16, "Db16", 1, "conv.hip: bf16-storage stride-2 data gradients of the narrow layers on nconv.hip (0 = gathered parity classes)");
 
 extern "C" int dcn_conv2d_stats_rows(int n, int h, int wd, int cout, int ksize, int stride) {
-  const int pad = (ksize - 1) / 2;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
-  return igemm_grid_m(n * ho * wo, cout, ksize * ksize);
+  const ConvShape g(h, wd, ksize, stride);
+  return igemm_grid_m(n * g.ho * g.wo, cout, g.T);
 }
 
 // Forward of a convolution whose input is the RAW output of the conv + BatchNorm layer in front: that layer's per-channel scale / shift
@@ -109,29 +206,13 @@ extern "C" int dcn_conv2d_fwd(const float* x, const float* w, float* y,
   DCN_CHECK_ARG(n > 0 && h > 0 && wd > 0 && cin > 0 && cout > 0, "conv2d_fwd: bad shape");
   DCN_CHECK_ARG(cin == 4 || cin % 32 == 0, "conv2d_fwd: cin=%d must be 4 or a multiple of 32 (pad channels)", cin);
   DCN_CHECK_ARG(cin != 4 || (ksize == 3 && stride == 1), "conv2d_fwd: cin=4 path is the 3x3 stride-1 stem only");
-  const int pad = (ksize - 1) / 2;
   IgemmParams p; base_params(p);
   p.amax_a = cin == 4 ? nullptr : amax_x; p.amax_b = cin == 4 ? nullptr : amax_w; p.amax_out = amax_y;
   p.in = x; p.wt = w; p.f8 = cin == 4 ? nullptr : f8_scales; p.out = y; p.scale = scale; p.shift = shift; p.residual = residual; p.stats = stats;
-  p.N = n; p.Hi = h; p.Wi = wd; p.Ci = cin; p.ldi = cin;
-  p.Ho = (h + 2 * pad - ksize) / stride + 1; p.Wo = (wd + 2 * pad - ksize) / stride + 1;
-  p.Hs = p.Ho; p.Ws = p.Wo; p.isy = p.isx = stride;
-  p.Co = cout; p.ldo = ldy > 0 ? ldy : cout; p.ldr = ldr > 0 ? ldr : cout;
+  fwd_geometry(p, n, h, wd, cin, cout, ksize, stride, ldy, ldr);
   DCN_CHECK_ARG(p.ldo >= cout, "conv2d_fwd: ldy=%d < cout=%d", ldy, cout);
-  p.M = n * p.Ho * p.Wo;
-  p.ntaps = ksize * ksize;
   p.act = act; p.slope = slope; p.accumulate = accumulate;
-  if (cin == 4) {
-    // weights are [Co][64]: 9 taps x 4 channels then zero padding (host prepares them)
-    p.c4 = 1; p.ldw = 64;
-  } else {
-    p.ldw = p.ntaps * cin; 
-    for (int r = 0; r < ksize; ++r)
-      for (int s = 0; s < ksize; ++s) {
-        const int t = r * ksize + s;
-        p.tap_dy[t] = r - pad; p.tap_dx[t] = s - pad; p.tap_w[t] = t * cin;
-      }
-  }
+  p.c4 = cin == 4 ? 1 : 0;
   if (p.c4 && stem_applicable(p, w_split)) return stem_launch(p, w_split, (hipStream_t)stream);      // (w_split: scratch of >= 27*32 floats)
   // the 32 -> 64 3x3 layers of the 416x416 / 208x208 maps, raw result + BatchNorm partial sums: filter bank in registers (nconv.hip)
   if (amax_x && amax_w && !amax_y && !f8_scales && !scale && !shift && !residual && act == DCN_ACT_NONE && !accumulate &&
@@ -198,8 +279,8 @@ int bwd_data_impl(const float* dy, int lddy, const float* w, float* wt, float* d
   DCN_CHECK_ARG(stride == 1 || stride == 2, "conv2d_bwd_data: stride=%d", stride);
   DCN_CHECK_ARG(cout % 32 == 0, "conv2d_bwd_data: cout=%d must be a multiple of 32 (pad the filter bank)", cout);
   DCN_CHECK_ARG(dy && w && wt && dx, "conv2d_bwd_data: null pointer");
-  const int pad = (ksize - 1) / 2, T = ksize * ksize;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
+  const ConvShape g(h, wd, ksize, stride);
+  const int T = g.T;
   if (lddy <= 0) lddy = cout;
   // wt_ready: wt already holds the transposed bank (dcn_prepare_filters) and, when given, wt_split its split form with the
   // scale behind it; nothing is written to either here
@@ -222,9 +303,7 @@ int bwd_data_impl(const float* dy, int lddy, const float* w, float* wt, float* d
     return nconv1_launch(1, dy, lddy, wt, dx, cin, nullptr, 0, n, h, wd, 1, amax_dy, amax_w, nullptr, stream);
   IgemmParams p; base_params(p);
   p.in = dy; p.wt = wt; p.f8 = f8_scales; p.out = dx; p.amax_a = amax_dy; p.amax_b = amax_w;
-  p.N = n; p.Hi = ho; p.Wi = wo; p.Ci = cout; p.ldi = lddy;
-  p.Ho = h; p.Wo = wd; p.Co = cin; p.ldo = cin; p.ldr = cin; p.ldw = T * cout;
-  p.accumulate = accumulate;
+  dgrad_geometry(p, g, n, h, wd, cin, cout, lddy, accumulate);
   if (wt_ready == 2) {            // bf16-operand mode: wt = transposed fp32 bank, wt_split = the same bank in bf16 (strip kernel only)
     p.wt16 = wt_split; wt_split = nullptr;
   }
@@ -249,38 +328,18 @@ int bwd_data_impl(const float* dy, int lddy, const float* w, float* wt, float* d
       p.b_scale = wt + numel;
     }
   }
+  const auto launch = [stream](const IgemmParams& q) { return igemm_launch(q, stream); };
   if (stride == 1) {
-    // dx[hi,wi] = sum_{r,s} dy[hi+pad-r, wi+pad-s] . w[:,r,s,:]
-    p.Hs = h; p.Ws = wd; p.M = n * h * wd; p.ntaps = T;
-    for (int r = 0; r < ksize; ++r)
-      for (int s = 0; s < ksize; ++s) {
-        const int t = r * ksize + s;
-        p.tap_dy[t] = pad - r; p.tap_dx[t] = pad - s; p.tap_w[t] = t * cout;
-      }
+    dgrad_s1_taps(p, g, ksize);
     if (tap) {
-      // a stride-1 data gradient IS a forward convolution on the transposed bank: the BatchNorm partial-sum epilogues of conv1.hip /
-      // conv3.hip take the tap (one partial row per M-tile, as dcn_conv2d_stats_rows counts them for the mirrored forward)
-      const int rows = igemm_grid_m(p.M, cin, T);
+      // the BatchNorm partial-sum epilogues of conv1.hip / conv3.hip take the tap (one partial row per M-tile, as dcn_conv2d_stats_rows
+      // counts them for the mirrored forward): ask with the buffer attached, as the launch would go out
       p.stats = tap->stats;
-      if (tap->stats_rows >= rows && igemm_tap_capable(p)) {
-        p.bt_y = tap->y; p.bt_mean = tap->mean; p.bt_invstd = tap->invstd; p.bt_gamma = tap->gamma; p.bt_beta = tap->beta;
-        p.bt_act = tap->act; p.bt_slope = tap->slope;
-        const int rc = igemm_launch(p, stream);
-        if (rc == DCN_OK && tap_rows) *tap_rows = rows;
-        return rc;
-      }
-      p.stats = nullptr;
+      if (!igemm_tap_capable(p)) tap = nullptr;
     }
-    return igemm_launch(p, stream);
+    return dgrad_s1_launch(p, tap, tap ? igemm_grid_m(p.M, cin, T) : 0, tap_rows, launch);
   }
-  // 1x1 stride 2: only the even-even pixels receive a gradient; the other three parity classes have no tap and are
-  // never visited below, so they must be zeroed here (not a DCNet layer shape, but the entry point is general).
-  if (ksize == 1 && !accumulate &&
-      hipMemsetAsync(dx, 0, (size_t)n * h * wd * cin * sizeof(float), stream) != hipSuccess) {
-    dcn_set_error("conv2d_bwd_data: memset failed"); return DCN_ERR_LAUNCH;
-  }
-  // stride 2: output pixels of parity class (a,b) only see taps with (a+pad-r), (b+pad-s) even.
-  // Four dense sub-problems with 1/2/2/4 taps (3x3) instead of one 9-tap problem that is 3/4 zeros.
+  // stride 2: four dense parity classes with 1 / 2 / 2 / 4 taps (3x3) ...
   if (merged) {
     // ... all in ONE launch (igemm.h ncls): block order (M-tile, class, N-tile) keeps the four classes of a region on one XCD
     // at the same time, so dY is fetched from HBM once instead of once per tap (nine times a tensor that does not fit the
@@ -293,14 +352,7 @@ int bwd_data_impl(const float* dy, int lddy, const float* w, float* wt, float* d
         q.cls_oy0[c] = a; q.cls_ox0[c] = b;
         q.cls_Hs[c] = (h - a + 1) / 2; q.cls_Ws[c] = (wd - b + 1) / 2;
         q.cls_M[c] = n * q.cls_Hs[c] * q.cls_Ws[c];
-        int nt = 0;
-        for (int r = 0; r < ksize; ++r)
-          for (int s = 0; s < ksize; ++s) {
-            if (((a + pad - r) & 1) || ((b + pad - s) & 1)) continue;
-            q.tap_dy[4 * c + nt] = (a + pad - r) / 2; q.tap_dx[4 * c + nt] = (b + pad - s) / 2;
-            q.tap_w[4 * c + nt] = (r * ksize + s) * cout;
-            ++nt;
-          }
+        const int nt = parity_class_taps(a, b, ksize, g.pad, cout, q.tap_dy + 4 * c, q.tap_dx + 4 * c, q.tap_w + 4 * c);
         q.cls_ntaps[c] = nt;
         if (q.cls_M[c] > q.M) { q.M = q.cls_M[c]; q.Hs = q.cls_Hs[c]; q.Ws = q.cls_Ws[c]; }
         if (nt > q.ntaps) q.ntaps = nt;
@@ -308,30 +360,7 @@ int bwd_data_impl(const float* dy, int lddy, const float* w, float* wt, float* d
     q.oy0 = q.ox0 = 0;
     return igemm_launch(q, stream);
   }
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      IgemmParams q = p;
-      q.dense_out = 0; q.oy0 = a; q.ox0 = b; q.osy = q.osx = 2;
-      q.Hs = (h - a + 1) / 2; q.Ws = (wd - b + 1) / 2;
-      if (q.Hs <= 0 || q.Ws <= 0) continue;
-      q.M = n * q.Hs * q.Ws;
-      q.ntaps = 0;
-      for (int r = 0; r < ksize; ++r)
-        for (int s = 0; s < ksize; ++s) {
-          if (((a + pad - r) & 1) || ((b + pad - s) & 1)) continue;
-          // hi = 2i+a  ->  ho = (2i + a + pad - r)/2 = i + (a+pad-r)/2
-          q.tap_dy[q.ntaps] = (a + pad - r) / 2; q.tap_dx[q.ntaps] = (b + pad - s) / 2;
-          q.tap_w[q.ntaps] = (r * ksize + s) * cout;
-          ++q.ntaps;
-        }
-      if (q.ntaps == 0) {
-        // 1x1 stride 2: odd pixels get no gradient.  (Not used by DCNet; keep semantics right.)
-        continue;
-      }
-      int rc = igemm_launch(q, stream);
-      if (rc != DCN_OK) return rc;
-    }
-  return DCN_OK;
+  return dgrad_s2_per_class(p, ksize, g.pad, "conv2d_bwd_data", sizeof(float), launch, stream);
 }
 }  // namespace
 
@@ -342,9 +371,8 @@ int bwd_data_impl(const float* dy, int lddy, const float* w, float* wt, float* d
 // stored).  All launches run on conv1.hip's ring kernel in its bf16 form; cin must be a multiple of 32 (the 3-channel stem keeps its
 // fp32 input and kernel).
 extern "C" int dcn_conv2d_stats_rows_b16(int n, int h, int wd, int cout, int ksize, int stride) {
-  const int pad = (ksize - 1) / 2;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
-  return conv1b_grid_m(n * ho * wo, cout, ksize * ksize, (ksize == 3 && stride == 1) ? wd : 0);
+  const ConvShape g(h, wd, ksize, stride);
+  return conv1b_grid_m(n * g.ho * g.wo, cout, g.T, (ksize == 3 && stride == 1) ? wd : 0);
 }
 
 extern "C" int dcn_conv2d_fwd_b16(const void* x, const void* w16, void* y, int y_f32, int n, int h, int wd, int cin, int cout, int ksize,
@@ -354,22 +382,12 @@ extern "C" int dcn_conv2d_fwd_b16(const void* x, const void* w16, void* y, int y
   DCN_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "conv2d_fwd_b16: ksize=%d stride=%d", ksize, stride);
   DCN_CHECK_ARG(n > 0 && h > 0 && wd > 0 && cin > 0 && cin % 32 == 0 && cout > 0 && cout % 32 == 0,
                 "conv2d_fwd_b16: cin=%d / cout=%d must be multiples of 32", cin, cout);
-  const int pad = (ksize - 1) / 2;
   IgemmParams p; base_params(p);
   p.in = (const float*)x; p.wt = (const float*)w16; p.out = (float*)y; p.scale = scale; p.shift = shift; p.residual = (const float*)residual;
   p.stats = stats;
-  p.N = n; p.Hi = h; p.Wi = wd; p.Ci = cin; p.ldi = cin;
-  p.Ho = (h + 2 * pad - ksize) / stride + 1; p.Wo = (wd + 2 * pad - ksize) / stride + 1;
-  p.Hs = p.Ho; p.Ws = p.Wo; p.isy = p.isx = stride;
-  p.Co = cout; p.ldo = ldy > 0 ? ldy : cout; p.ldr = ldr > 0 ? ldr : cout;
+  fwd_geometry(p, n, h, wd, cin, cout, ksize, stride, ldy, ldr);
   DCN_CHECK_ARG(p.ldo >= cout, "conv2d_fwd_b16: ldy=%d < cout=%d", ldy, cout);
-  p.M = n * p.Ho * p.Wo; p.ntaps = ksize * ksize; p.ldw = p.ntaps * cin;
   p.act = act; p.slope = slope; p.accumulate = accumulate;
-  for (int r = 0; r < ksize; ++r)
-    for (int s = 0; s < ksize; ++s) {
-      const int t = r * ksize + s;
-      p.tap_dy[t] = r - pad; p.tap_dx[t] = s - pad; p.tap_w[t] = t * cin;
-    }
   // the raw forward of the 32 -> 64 layers on the 416 / 208-wide maps: the register-bank kernel (nconv.hip), x read once instead of nine times
   if (g_n1_b16 && !y_f32 && !scale && !shift && act == DCN_ACT_NONE && !residual && !accumulate && p.ldo == cout &&
       nconv1_applicable(0, n, h, wd, cin, cout, ksize, stride))
@@ -387,65 +405,26 @@ extern "C" int dcn_conv2d_bwd_data_b16(const void* dy, int lddy, const void* wt1
   DCN_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "conv2d_bwd_data_b16: ksize=%d stride=%d", ksize, stride);
   DCN_CHECK_ARG(cout % 32 == 0 && cin % 32 == 0, "conv2d_bwd_data_b16: cin=%d / cout=%d must be multiples of 32", cin, cout);
   if (tap_rows) *tap_rows = 0;
-  const int pad = (ksize - 1) / 2, T = ksize * ksize;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
+  const ConvShape g(h, wd, ksize, stride);
   if (lddy <= 0) lddy = cout;
   IgemmParams p; base_params(p);
   p.in = (const float*)dy; p.wt = (const float*)wt16; p.out = (float*)dx;
-  p.N = n; p.Hi = ho; p.Wi = wo; p.Ci = cout; p.ldi = lddy;
-  p.Ho = h; p.Wo = wd; p.Co = cin; p.ldo = cin; p.ldr = cin; p.ldw = T * cout;
-  p.accumulate = accumulate;
+  dgrad_geometry(p, g, n, h, wd, cin, cout, lddy, accumulate);
+  const auto launch = [dx_f32, stream](const IgemmParams& q) { return conv1b_launch(q, dx_f32, stream); };
   // the data gradient 64 -> 32 of the stride-1 layer on the 208-wide map: the register-bank kernel (no tap there: the caller reduces)
   if (g_n1_b16 && stride == 1 && !dx_f32 && !accumulate && lddy == cout && nconv1_applicable(1, n, h, wd, cin, cout, ksize, stride))
     return nconv1_launch_b16(1, dy, lddy, wt16, dx, cin, nullptr, 0, n, h, wd, 1, stream);
   if (stride == 1) {
-    p.Hs = h; p.Ws = wd; p.M = n * h * wd; p.ntaps = T;
-    for (int r = 0; r < ksize; ++r)
-      for (int s = 0; s < ksize; ++s) {
-        const int t = r * ksize + s;
-        p.tap_dy[t] = pad - r; p.tap_dx[t] = pad - s; p.tap_w[t] = t * cout;
-      }
-    if (tap_y && tap_stats && tap_mean && tap_invstd) {
-      const int rows = conv1b_grid_m(p.M, cin, T, ksize == 3 ? wd : 0);
-      if (rows > 0 && tap_stats_rows >= rows) {
-        p.stats = tap_stats; p.bt_y = (const float*)tap_y; p.bt_mean = tap_mean; p.bt_invstd = tap_invstd; p.bt_gamma = tap_gamma;
-        p.bt_beta = tap_beta; p.bt_act = tap_act; p.bt_slope = tap_slope;
-        const int rc = conv1b_launch(p, dx_f32, stream);
-        if (rc == DCN_OK && tap_rows) *tap_rows = rows;
-        return rc;
-      }
-    }
-    return conv1b_launch(p, dx_f32, stream);
+    dgrad_s1_taps(p, g, ksize);
+    const DcnBnTap tap{(const float*)tap_y, tap_mean, tap_invstd, tap_gamma, tap_beta, tap_act, tap_slope, tap_stats, tap_stats_rows};
+    const bool tapped = tap_y && tap_stats && tap_mean && tap_invstd;
+    return dgrad_s1_launch(p, tapped ? &tap : nullptr, tapped ? conv1b_grid_m(p.M, cin, g.T, ksize == 3 ? wd : 0) : 0, tap_rows, launch);
   }
   // the 32 <- 64 / 64 <- 128 stride-2 layers on the 416 / 208-wide maps: the register-bank kernel (nconv.hip), all four parity classes of a
   // position stored by the workgroup that computed them (the four gathered launches below: 1.14 ms against 0.2 ms of HBM traffic)
   if (g_d2_b16 && !dx_f32 && lddy == cout && dgrad2_applicable(n, h, wd, cin, cout, ksize, stride, accumulate))
     return dgrad2_launch_b16(dy, lddy, wt16, dx, n, h, wd, cin, accumulate, stream);
-  if (ksize == 1 && !accumulate &&
-      hipMemsetAsync(dx, 0, (size_t)n * h * wd * cin * (dx_f32 ? 4 : 2), stream) != hipSuccess) {
-    dcn_set_error("conv2d_bwd_data_b16: memset failed"); return DCN_ERR_LAUNCH;
-  }
-  // stride 2: four dense parity classes with 1 / 2 / 2 / 4 taps (see bwd_data_impl)
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      IgemmParams q = p;
-      q.dense_out = 0; q.oy0 = a; q.ox0 = b; q.osy = q.osx = 2;
-      q.Hs = (h - a + 1) / 2; q.Ws = (wd - b + 1) / 2;
-      if (q.Hs <= 0 || q.Ws <= 0) continue;
-      q.M = n * q.Hs * q.Ws;
-      q.ntaps = 0;
-      for (int r = 0; r < ksize; ++r)
-        for (int s = 0; s < ksize; ++s) {
-          if (((a + pad - r) & 1) || ((b + pad - s) & 1)) continue;
-          q.tap_dy[q.ntaps] = (a + pad - r) / 2; q.tap_dx[q.ntaps] = (b + pad - s) / 2;
-          q.tap_w[q.ntaps] = (r * ksize + s) * cout;
-          ++q.ntaps;
-        }
-      if (q.ntaps == 0) continue;
-      const int rc = conv1b_launch(q, dx_f32, stream);
-      if (rc != DCN_OK) return rc;
-    }
-  return DCN_OK;
+  return dgrad_s2_per_class(p, ksize, g.pad, "conv2d_bwd_data_b16", dx_f32 ? 4 : 2, launch, stream);
 }
 
 // ---- fp8 storage (BASELINE.json configs[4]): forward / data gradient on e4m3 operands with one e8m0 scale per pixel / per filter ---------
@@ -453,9 +432,8 @@ extern "C" int dcn_conv2d_bwd_data_b16(const void* dy, int lddy, const void* wt1
 // transposed bank [Cin][k*k*Cout] (data gradient) as e4m3 bytes with ws: e8m0 per bank row.  y / dx, residual, the BatchNorm tap: bf16
 // tensors exactly as in dcn_conv2d_*_b16 (fp32 accumulate, fp32 statistics of the values as stored).  cin, cout multiples of 64 / 32.
 extern "C" int dcn_conv2d_stats_rows_f8(int n, int h, int wd, int cout, int ksize, int stride) {
-  const int pad = (ksize - 1) / 2;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
-  return conv1q_grid_m(n * ho * wo, cout);
+  const ConvShape g(h, wd, ksize, stride);
+  return conv1q_grid_m(n * g.ho * g.wo, cout);
 }
 
 extern "C" int dcn_conv2d_fwd_f8(const void* x8, const void* xs, const void* w8, const void* ws, void* y, int y_f32, int n, int h, int wd, int cin,
@@ -465,23 +443,13 @@ extern "C" int dcn_conv2d_fwd_f8(const void* x8, const void* xs, const void* w8,
   DCN_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "conv2d_fwd_f8: ksize=%d stride=%d", ksize, stride);
   DCN_CHECK_ARG(n > 0 && h > 0 && wd > 0 && cin > 0 && cin % 64 == 0 && cout > 0 && cout % 32 == 0,
                 "conv2d_fwd_f8: cin=%d must be a multiple of 64, cout=%d of 32", cin, cout);
-  const int pad = (ksize - 1) / 2;
   IgemmParams p; base_params(p);
   p.in = (const float*)x8; p.wt = (const float*)w8; p.out = (float*)y; p.scale = scale; p.shift = shift; p.residual = (const float*)residual;
   p.a_scale8 = (const unsigned char*)xs; p.b_scale8 = (const unsigned char*)ws;
   p.stats = stats;
-  p.N = n; p.Hi = h; p.Wi = wd; p.Ci = cin; p.ldi = cin;
-  p.Ho = (h + 2 * pad - ksize) / stride + 1; p.Wo = (wd + 2 * pad - ksize) / stride + 1;
-  p.Hs = p.Ho; p.Ws = p.Wo; p.isy = p.isx = stride;
-  p.Co = cout; p.ldo = ldy > 0 ? ldy : cout; p.ldr = ldr > 0 ? ldr : cout;
+  fwd_geometry(p, n, h, wd, cin, cout, ksize, stride, ldy, ldr);
   DCN_CHECK_ARG(p.ldo >= cout, "conv2d_fwd_f8: ldy=%d < cout=%d", ldy, cout);
-  p.M = n * p.Ho * p.Wo; p.ntaps = ksize * ksize; p.ldw = p.ntaps * cin;
   p.act = act; p.slope = slope; p.accumulate = accumulate;
-  for (int r = 0; r < ksize; ++r)
-    for (int s = 0; s < ksize; ++s) {
-      const int t = r * ksize + s;
-      p.tap_dy[t] = r - pad; p.tap_dx[t] = s - pad; p.tap_w[t] = t * cin;
-    }
   return conv1q_launch(p, y_f32, (hipStream_t)stream);
 }
 
@@ -494,56 +462,17 @@ extern "C" int dcn_conv2d_bwd_data_f8(const void* dy8, const void* dys, const vo
   DCN_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "conv2d_bwd_data_f8: ksize=%d stride=%d", ksize, stride);
   DCN_CHECK_ARG(cout % 64 == 0 && cin % 32 == 0, "conv2d_bwd_data_f8: cout=%d must be a multiple of 64, cin=%d of 32", cout, cin);
   if (tap_rows) *tap_rows = 0;
-  const int pad = (ksize - 1) / 2, T = ksize * ksize;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
+  const ConvShape g(h, wd, ksize, stride);
   IgemmParams p; base_params(p);
   p.in = (const float*)dy8; p.wt = (const float*)wt8; p.out = (float*)dx;
   p.a_scale8 = (const unsigned char*)dys; p.b_scale8 = (const unsigned char*)wts;
-  p.N = n; p.Hi = ho; p.Wi = wo; p.Ci = cout; p.ldi = cout;
-  p.Ho = h; p.Wo = wd; p.Co = cin; p.ldo = cin; p.ldr = cin; p.ldw = T * cout;
-  p.accumulate = accumulate;
+  dgrad_geometry(p, g, n, h, wd, cin, cout, cout, accumulate);        // (dy8 is dense: one scale byte per pixel)
+  const auto launch = [dx_f32, stream](const IgemmParams& q) { return conv1q_launch(q, dx_f32, stream); };
   if (stride == 1) {
-    p.Hs = h; p.Ws = wd; p.M = n * h * wd; p.ntaps = T;
-    for (int r = 0; r < ksize; ++r)
-      for (int s = 0; s < ksize; ++s) {
-        const int t = r * ksize + s;
-        p.tap_dy[t] = pad - r; p.tap_dx[t] = pad - s; p.tap_w[t] = t * cout;
-      }
-    if (tap_y && tap_stats && tap_mean && tap_invstd) {
-      const int rows = conv1q_grid_m(p.M, cin);
-      if (rows > 0 && tap_stats_rows >= rows) {
-        p.stats = tap_stats; p.bt_y = (const float*)tap_y; p.bt_mean = tap_mean; p.bt_invstd = tap_invstd; p.bt_gamma = tap_gamma;
-        p.bt_beta = tap_beta; p.bt_act = tap_act; p.bt_slope = tap_slope;
-        const int rc = conv1q_launch(p, dx_f32, stream);
-        if (rc == DCN_OK && tap_rows) *tap_rows = rows;
-        return rc;
-      }
-    }
-    return conv1q_launch(p, dx_f32, stream);
+    dgrad_s1_taps(p, g, ksize);
+    const DcnBnTap tap{(const float*)tap_y, tap_mean, tap_invstd, tap_gamma, tap_beta, tap_act, tap_slope, tap_stats, tap_stats_rows};
+    const bool tapped = tap_y && tap_stats && tap_mean && tap_invstd;
+    return dgrad_s1_launch(p, tapped ? &tap : nullptr, tapped ? conv1q_grid_m(p.M, cin) : 0, tap_rows, launch);
   }
-  if (ksize == 1 && !accumulate &&
-      hipMemsetAsync(dx, 0, (size_t)n * h * wd * cin * (dx_f32 ? 4 : 2), stream) != hipSuccess) {
-    dcn_set_error("conv2d_bwd_data_f8: memset failed"); return DCN_ERR_LAUNCH;
-  }
-  // stride 2: four dense parity classes with 1 / 2 / 2 / 4 taps (see dcn_conv2d_bwd_data_b16)
-  for (int a = 0; a < 2; ++a)
-    for (int b = 0; b < 2; ++b) {
-      IgemmParams q = p;
-      q.dense_out = 0; q.oy0 = a; q.ox0 = b; q.osy = q.osx = 2;
-      q.Hs = (h - a + 1) / 2; q.Ws = (wd - b + 1) / 2;
-      if (q.Hs <= 0 || q.Ws <= 0) continue;
-      q.M = n * q.Hs * q.Ws;
-      q.ntaps = 0;
-      for (int r = 0; r < ksize; ++r)
-        for (int s = 0; s < ksize; ++s) {
-          if (((a + pad - r) & 1) || ((b + pad - s) & 1)) continue;
-          q.tap_dy[q.ntaps] = (a + pad - r) / 2; q.tap_dx[q.ntaps] = (b + pad - s) / 2;
-          q.tap_w[q.ntaps] = (r * ksize + s) * cout;
-          ++q.ntaps;
-        }
-      if (q.ntaps == 0) continue;
-      const int rc = conv1q_launch(q, dx_f32, stream);
-      if (rc != DCN_OK) return rc;
-    }
-  return DCN_OK;
+  return dgrad_s2_per_class(p, ksize, g.pad, "conv2d_bwd_data_f8", dx_f32 ? 4 : 2, launch, stream);
 }

@@ -8,6 +8,7 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
+import ctypes
 import os
 
 import torch
@@ -447,7 +448,6 @@ def conv2d_bwd_data(dy, w_ohwi, in_hw, ksize, stride, out=None, accumulate=False
         wts, ready = wt_b16, 2                                            # transposed bank in bf16 (FilterBanks)
     if tap is not None:
         # BatchNorm tap (csrc/nconv.hip): the partial sums of the backward of the layer in front, formed in this launch's epilogue
-        import ctypes
         cap = lib().conv2d_bwd_data_tap_rows(n, h, wd, cin, cout, ksize, stride)
         part = torch.empty((max(cap, 1), 2, cin), dtype=torch.float32, device=dy.device)
         rows = ctypes.c_int(0)
@@ -463,6 +463,41 @@ def conv2d_bwd_data(dy, w_ohwi, in_hw, ksize, stride, out=None, accumulate=False
     return out
 
 
+def _fwd_out_stats(name, x, cout, ksize, stride, out, out_f32, stats_rows):
+    """The result tensors of a storage-mode forward of x (N,H,W,Cin): out (allocated here when None) is bf16, or fp32 with out_f32, with
+    contiguous channels; stats is the [rows][2][Cout] fp32 partial-sum buffer, rows = stats_rows(n, h, wd, cout, ksize, stride), or None
+    when stats_rows is."""
+    n, h, wd, _ = x.shape
+    dtype = torch.float32 if out_f32 else torch.bfloat16
+    if out is None:
+        out = torch.empty((n, *conv_out_hw(h, wd, ksize, stride), cout), dtype=dtype, device=x.device)
+    if out.dtype != dtype or out.stride(3) != 1:
+        raise ValueError(f"{name}: out dtype / layout")
+    stats = None
+    if stats_rows is not None:
+        stats = torch.empty((stats_rows(n, h, wd, cout, ksize, stride), 2, cout), dtype=torch.float32, device=x.device)
+    return out, stats
+
+
+def _bwd_data_tapped(fn, operands, out, out_f32, n, h, wd, cin, cout, ksize, stride, accumulate, tap, stats_rows):
+    """The call of a storage-mode data gradient fn(*operands, dx, dx_f32, <shape>, accumulate, <BatchNorm tap>, &rows, stream).  The launch
+    can take the tap at stride 1 when its y is a contiguous bf16 tensor; stats_rows(n, h, wd, cin, ksize, 1) then counts its M-tiles (rows =
+    n*h*wd, filters = cin, k*k taps: stride 1 keeps h x wd), one partial row each.  Returns out, or (out, partials | None) if tap is given."""
+    part = None
+    rows = ctypes.c_int(0)
+    cap = 0
+    if tap is not None and stride == 1 and _b16(tap["y"]) and tap["y"].is_contiguous():
+        cap = stats_rows(n, h, wd, cin, ksize, 1)
+        part = torch.empty((max(cap, 1), 2, cin), dtype=torch.float32, device=out.device)
+    fn(*operands, out.data_ptr(), int(out_f32), n, h, wd, cin, cout, ksize, stride, int(accumulate),
+       tap["y"].data_ptr() if cap else 0, tap["mean"].data_ptr() if cap else 0, tap["invstd"].data_ptr() if cap else 0,
+       _p(tap.get("gamma")) if cap else 0, _p(tap.get("beta")) if cap else 0, int(tap["act"]) if cap else 0, float(tap["slope"]) if cap else 0.0,
+       part.data_ptr() if cap else 0, cap, ctypes.addressof(rows), _s())
+    if tap is not None:
+        return out, (part[:rows.value] if rows.value > 0 else None)
+    return out
+
+
 def conv2d_fwd_b16(x, w16, cout, ksize, stride, scale=None, shift=None, act=ACT_NONE, slope=0.0, residual=None, out=None,
                    want_stats=False, accumulate=False, out_f32=False):
     """bf16 storage: x (N,H,W,Cin) bf16 NHWC, w16 the bf16 bank [Cout][k*k*Cin] (FilterBanks "b16").  Returns (y, stats): y bf16
@@ -471,18 +506,11 @@ def conv2d_fwd_b16(x, w16, cout, ksize, stride, scale=None, shift=None, act=ACT_
     n, h, wd, cin = x.shape
     if not (w16.is_cuda and w16.dtype == torch.bfloat16 and w16.is_contiguous() and w16.numel() == cout * ksize * ksize * cin):
         raise ValueError("conv2d_fwd_b16: w16 must be the contiguous bf16 bank [Cout][k*k*Cin]")
-    ho, wo = conv_out_hw(h, wd, ksize, stride)
-    if out is None:
-        out = torch.empty((n, ho, wo, cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x.device)
-    if out.dtype != (torch.float32 if out_f32 else torch.bfloat16) or out.stride(3) != 1:
-        raise ValueError("conv2d_fwd_b16: out dtype / layout")
+    out, stats = _fwd_out_stats("conv2d_fwd_b16", x, cout, ksize, stride, out, out_f32, lib().conv2d_stats_rows_b16 if want_stats else None)
     if residual is not None:
         _rows16(residual, "conv2d_fwd_b16 residual")
         if not _b16(residual):
             raise ValueError("conv2d_fwd_b16: residual must be bf16")
-    stats = None
-    if want_stats:
-        stats = torch.empty((lib().conv2d_stats_rows_b16(n, h, wd, cout, ksize, stride), 2, cout), dtype=torch.float32, device=x.device)
     lib().conv2d_fwd_b16(x.data_ptr(), w16.data_ptr(), out.data_ptr(), int(out_f32), n, h, wd, cin, cout, ksize, stride, _p(scale), _p(shift),
                          act, float(slope), _p(residual), 0 if residual is None else residual.stride(2), out.stride(2), _p(stats),
                          int(accumulate), _s())
@@ -492,7 +520,6 @@ def conv2d_fwd_b16(x, w16, cout, ksize, stride, scale=None, shift=None, act=ACT_
 def conv2d_bwd_data_b16(dy, wt16, in_hw, cin, ksize, stride, out=None, accumulate=False, tap=None, out_f32=False):
     """bf16 storage: dy (N,Ho,Wo,Cout) bf16 (pixel stride may exceed Cout), wt16 the transposed bf16 bank [Cin][k*k*Cout]
     (FilterBanks "tb16") -> dx (N,H,W,Cin) bf16 (fp32 with out_f32).  tap: as conv2d_bwd_data (y bf16); returns (dx, partials | None)."""
-    import ctypes
     n, ho, wo, cout = dy.shape
     h, wd = in_hw
     _rows16(dy, "conv2d_bwd_data_b16 dy")
@@ -502,20 +529,8 @@ def conv2d_bwd_data_b16(dy, wt16, in_hw, cin, ksize, stride, out=None, accumulat
         out = torch.empty((n, h, wd, cin), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dy.device)
     if out.dtype != (torch.float32 if out_f32 else torch.bfloat16) or not out.is_contiguous():
         raise ValueError("conv2d_bwd_data_b16: out dtype / layout")
-    part = None
-    rows = ctypes.c_int(0)
-    cap = 0
-    if tap is not None and stride == 1 and _b16(tap["y"]) and tap["y"].is_contiguous():
-        cap = lib().conv2d_stats_rows_b16(n, h, wd, cin, ksize, 1)        # M-tiles of the launch (rows = n*h*wd, filters = cin, k*k taps: stride 1 keeps h x wd)
-        part = torch.empty((max(cap, 1), 2, cin), dtype=torch.float32, device=dy.device)
-    lib().conv2d_bwd_data_b16(dy.data_ptr(), dy.stride(2), wt16.data_ptr(), out.data_ptr(), int(out_f32), n, h, wd, cin, cout, ksize, stride,
-                              int(accumulate), tap["y"].data_ptr() if cap else 0, tap["mean"].data_ptr() if cap else 0,
-                              tap["invstd"].data_ptr() if cap else 0, _p(tap.get("gamma")) if cap else 0, _p(tap.get("beta")) if cap else 0,
-                              int(tap["act"]) if cap else 0, float(tap["slope"]) if cap else 0.0, part.data_ptr() if cap else 0, cap,
-                              ctypes.addressof(rows), _s())
-    if tap is not None:
-        return out, (part[:rows.value] if rows.value > 0 else None)
-    return out
+    return _bwd_data_tapped(lib().conv2d_bwd_data_b16, (dy.data_ptr(), dy.stride(2), wt16.data_ptr()), out, out_f32, n, h, wd, cin, cout, ksize, stride,
+                            accumulate, tap, lib().conv2d_stats_rows_b16)
 
 
 # ---- fp8 storage (configs[4]): e4m3 bytes + one e8m0 scale per row -----------------------------------------------------------------
@@ -548,13 +563,9 @@ def conv2d_fwd_f8(x8, xs, w8, ws, cout, ksize, stride, scale=None, shift=None, a
     if not (x8.dtype == torch.uint8 and x8.is_contiguous() and w8.dtype == torch.uint8 and w8.is_contiguous() and w8.numel() == cout * ksize * ksize * cin
             and xs.dtype == torch.uint8 and xs.numel() == n * h * wd and ws.dtype == torch.uint8 and ws.numel() == cout):
         raise ValueError("conv2d_fwd_f8: x8 / w8 must be contiguous uint8 e4m3 tensors with one e8m0 byte per pixel / per filter")
-    ho, wo = conv_out_hw(h, wd, ksize, stride)
-    out = torch.empty((n, ho, wo, cout), dtype=torch.float32 if out_f32 else torch.bfloat16, device=x8.device)
+    out, stats = _fwd_out_stats("conv2d_fwd_f8", x8, cout, ksize, stride, None, out_f32, lib().conv2d_stats_rows_f8 if want_stats else None)
     if residual is not None and not (_b16(residual) and residual.is_contiguous()):
         raise ValueError("conv2d_fwd_f8: residual must be a contiguous bf16 tensor")
-    stats = None
-    if want_stats:
-        stats = torch.empty((lib().conv2d_stats_rows_f8(n, h, wd, cout, ksize, stride), 2, cout), dtype=torch.float32, device=x8.device)
     lib().conv2d_fwd_f8(x8.data_ptr(), xs.data_ptr(), w8.data_ptr(), ws.data_ptr(), out.data_ptr(), int(out_f32), n, h, wd, cin, cout, ksize, stride,
                         _p(scale), _p(shift), act, float(slope), _p(residual), 0, cout, _p(stats), 0, _s())
     return out, stats
@@ -563,7 +574,6 @@ def conv2d_fwd_f8(x8, xs, w8, ws, cout, ksize, stride, scale=None, shift=None, a
 def conv2d_bwd_data_f8(dy8, dys, wt8, wts, in_hw, cin, ksize, stride, out=None, accumulate=False, tap=None, out_f32=False):
     """fp8 storage: dy8 (N,Ho,Wo,Cout) uint8 e4m3 with dys per pixel, wt8 the transposed bank [Cin][k*k*Cout] e4m3 with wts per row -> dx
     (N,H,W,Cin) bf16 (fp32 with out_f32).  tap: as conv2d_bwd_data_b16; returns (dx, partials | None) then."""
-    import ctypes
     n, ho, wo, cout = dy8.shape
     h, wd = in_hw
     if not (dy8.dtype == torch.uint8 and dy8.is_contiguous() and wt8.dtype == torch.uint8 and wt8.is_contiguous()
@@ -573,20 +583,8 @@ def conv2d_bwd_data_f8(dy8, dys, wt8, wts, in_hw, cin, ksize, stride, out=None, 
         out = torch.empty((n, h, wd, cin), dtype=torch.float32 if out_f32 else torch.bfloat16, device=dy8.device)
     if out.dtype != (torch.float32 if out_f32 else torch.bfloat16) or not out.is_contiguous():
         raise ValueError("conv2d_bwd_data_f8: out dtype / layout")
-    part = None
-    rows = ctypes.c_int(0)
-    cap = 0
-    if tap is not None and stride == 1 and _b16(tap["y"]) and tap["y"].is_contiguous():
-        cap = lib().conv2d_stats_rows_f8(n, h, wd, cin, ksize, 1)
-        part = torch.empty((max(cap, 1), 2, cin), dtype=torch.float32, device=dy8.device)
-    lib().conv2d_bwd_data_f8(dy8.data_ptr(), dys.data_ptr(), wt8.data_ptr(), wts.data_ptr(), out.data_ptr(), int(out_f32), n, h, wd, cin, cout, ksize,
-                             stride, int(accumulate), tap["y"].data_ptr() if cap else 0, tap["mean"].data_ptr() if cap else 0,
-                             tap["invstd"].data_ptr() if cap else 0, _p(tap.get("gamma")) if cap else 0, _p(tap.get("beta")) if cap else 0,
-                             int(tap["act"]) if cap else 0, float(tap["slope"]) if cap else 0.0, part.data_ptr() if cap else 0, cap,
-                             ctypes.addressof(rows), _s())
-    if tap is not None:
-        return out, (part[:rows.value] if rows.value > 0 else None)
-    return out
+    return _bwd_data_tapped(lib().conv2d_bwd_data_f8, (dy8.data_ptr(), dys.data_ptr(), wt8.data_ptr(), wts.data_ptr()), out, out_f32, n, h, wd, cin, cout,
+                            ksize, stride, accumulate, tap, lib().conv2d_stats_rows_f8)
 
 
 def conv2d_bwd_weight_b16(x, dy, ksize, stride, slot: int = 0):

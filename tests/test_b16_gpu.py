@@ -65,21 +65,28 @@ def test_b16_conv_forward_dgrad_wgrad_match_their_exact_model(case, tile2b):
         _conv_case(case)
 
 
+def _exact_model(case):
+    """bf16 operands of a case on the device, and the fp64 forward / data gradient / weight gradient of those values (NHWC / OHWI)"""
+    dev = torch.device("cuda:0")
+    n, h, w, cin, cout, k, st = case
+    x = _bf(_rand(n, h, w, cin, seed=1)).to(dev)
+    wt = _bf(_rand(cout, k, k, cin, seed=2) / (cin * k * k) ** 0.5).to(dev)          # OHWI bank, bf16
+    xd = x.double().cpu().permute(0, 3, 1, 2).requires_grad_(True)
+    wd = wt.double().cpu().permute(0, 3, 1, 2).requires_grad_(True)
+    yd = F.conv2d(xd, wd, stride=st, padding=(k - 1) // 2)
+    dy = _bf(_rand(n, yd.shape[2], yd.shape[3], cout, seed=3) / 8).to(dev)
+    yd.backward(dy.double().cpu().permute(0, 3, 1, 2))
+    return x, wt, dy, yd.detach().permute(0, 2, 3, 1), xd.grad.permute(0, 2, 3, 1), wd.grad.permute(0, 2, 3, 1)
+
+
 def _conv_case(case):
     from dcnet_amd import ops
     from dcnet_amd.lib import lib
     dev = torch.device("cuda:0")
     n, h, w, cin, cout, k, st = case
     T = k * k
-    x = _bf(_rand(n, h, w, cin, seed=1)).to(dev)
-    wt = _bf(_rand(cout, k, k, cin, seed=2) / (cin * T) ** 0.5).to(dev)              # OHWI bank, bf16
-    xd = x.double().cpu().permute(0, 3, 1, 2).requires_grad_(True)
-    wd = wt.double().cpu().permute(0, 3, 1, 2).requires_grad_(True)
-    yd = F.conv2d(xd, wd, stride=st, padding=(k - 1) // 2)
-    ho, wo = yd.shape[2], yd.shape[3]
-    dy = _bf(_rand(n, ho, wo, cout, seed=3) / 8).to(dev)
-    yd.backward(dy.double().cpu().permute(0, 3, 1, 2))
-    ref_y = yd.detach().permute(0, 2, 3, 1)
+    x, wt, dy, ref_y, ref_dx, ref_dw = _exact_model(case)
+    ho, wo = ref_y.shape[1], ref_y.shape[2]
     # ---- forward: raw result bf16 + BatchNorm partial sums of the stored values ----
     y, stats = ops.conv2d_fwd_b16(x, wt.reshape(-1), cout, k, st, want_stats=True)
     assert y.dtype == torch.bfloat16 and y.shape == (n, ho, wo, cout)
@@ -97,7 +104,7 @@ def _conv_case(case):
         _ulp_close(y0, ref_y, "fwd, gathered tiles")
         assert torch.allclose(stats0.double().sum(0).cpu()[0], yf.sum(0), rtol=1e-5, atol=1e-4 * float(yf.abs().sum(0).max())) or not torch.equal(y0, y)
         _ulp_close(ops.conv2d_bwd_data_b16(_bf(_rand(n, ho, wo, cout, seed=3) / 8).to(dev), wt.reshape(cout, T, cin).permute(2, 1, 0).contiguous().reshape(-1),
-                                           (h, w), cin, k, st), xd.grad.permute(0, 2, 3, 1), "dgrad, gathered tiles")
+                                           (h, w), cin, k, st), ref_dx, "dgrad, gathered tiles")
     # ---- epilogue: scale / shift / LeakyReLU / shortcut (bf16) ----
     sc = (_rand(cout, seed=4).abs() + 0.5).to(dev); sh = _rand(cout, seed=5).to(dev)
     res = _bf(_rand(n, ho, wo, cout, seed=6)).to(dev)
@@ -107,7 +114,6 @@ def _conv_case(case):
     # ---- data gradient (transposed bank [Cin][T][Cout]) ----
     wt_t = wt.reshape(cout, T, cin).permute(2, 1, 0).contiguous().reshape(-1)
     dx = ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st)
-    ref_dx = xd.grad.permute(0, 2, 3, 1)
     _ulp_close(dx, ref_dx, "dgrad")
     base = _bf(_rand(n, h, w, cin, seed=7)).to(dev)
     acc = base.clone()
@@ -120,7 +126,6 @@ def _conv_case(case):
     assert float((dx32.double().cpu() - ref_dx).abs().max()) <= 3e-5 * max(1.0, float(ref_dx.abs().max()))
     # ---- weight gradient: fp32 out, fp32 accumulation of exact bf16 products ----
     from dcnet_amd.lib import lib
-    ref_dw = wd.grad.permute(0, 2, 3, 1)
     with tuning() as tune:
         for knob in (0, 1):                    # the per-tap tile (default) and the filter-row kernel on bf16 inputs (where its shape test admits the layer)
             tune({"w3b16": knob})
@@ -132,6 +137,38 @@ def _conv_case(case):
         tune({"9b16": 0})           # (the nine-tap kernel off: the per-tap tile for the narrow layers too)
         dw0 = ops.conv2d_bwd_weight_b16(x, dy, k, st)
         assert float((dw0.double().cpu() - ref_dw).abs().max()) <= 5e-5 * max(1.0, float(ref_dw.abs().max()))
+
+
+S2_EDGE_CASES = [
+    (1, 6, 10, 64, 64, 1, 2),         # 1x1 stride 2: one parity class has a tap, the other three receive no gradient
+    (1, 1, 8, 64, 64, 3, 2),          # a one-row map: the classes of the odd rows are empty
+]
+
+
+@pytest.mark.parametrize("case", S2_EDGE_CASES)
+def test_b16_stride2_classes_without_taps_or_pixels(case):
+    """Forward and data gradient where the parity classes of the stride-2 data gradient degenerate.  1x1: the pixels off the even-even
+    class get no tap and come back exactly zero, in a bf16 and in an fp32 dx (whatever the buffer held), and keep their content when the
+    launch accumulates.  One row: the two classes of odd rows have no pixel and are not launched.  Tolerances as for CASES."""
+    from dcnet_amd import ops
+    dev = torch.device("cuda:0")
+    n, h, w, cin, cout, k, st = case
+    x, wt, dy, ref_y, ref_dx, _ = _exact_model(case)
+    y, _ = ops.conv2d_fwd_b16(x, wt.reshape(-1), cout, k, st)
+    _ulp_close(y, ref_y, "fwd")
+    wt_t = wt.reshape(cout, k * k, cin).permute(2, 1, 0).contiguous().reshape(-1)
+    dx = ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st, out=torch.full((n, h, w, cin), 3.0, dtype=torch.bfloat16, device=dev))
+    _ulp_close(dx, ref_dx, "dgrad")
+    dx32 = ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st, out=torch.full((n, h, w, cin), 3.0, device=dev), out_f32=True)
+    assert float((dx32.double().cpu() - ref_dx).abs().max()) <= 3e-5 * max(1.0, float(ref_dx.abs().max()))
+    base = _bf(_rand(n, h, w, cin, seed=7)).to(dev)
+    acc = base.clone()
+    ops.conv2d_bwd_data_b16(dy, wt_t, (h, w), cin, k, st, out=acc, accumulate=True)
+    _ulp_close(acc, ref_dx + base.double().cpu(), "dgrad accumulate")
+    untapped = torch.ones(h, w, dtype=torch.bool, device=dev)
+    untapped[::2 if k == 1 else 1, ::2 if k == 1 else 1] = False                      # (3x3: every pixel has a tap)
+    assert int(untapped.sum()) == (h * w - ((h + 1) // 2) * ((w + 1) // 2) if k == 1 else 0)
+    assert not bool(dx[:, untapped].any()) and not bool(dx32[:, untapped].any()) and torch.equal(acc[:, untapped], base[:, untapped])
 
 
 @pytest.mark.parametrize("shape", [(2, 26, 26, 128, 256, 3), (3, 13, 13, 256, 128, 1), (1, 20, 12, 64, 64, 3)])

@@ -63,8 +63,9 @@ CASES = [
 ]
 
 
-@pytest.mark.parametrize("case", CASES)
-def test_f8_conv_forward_and_data_gradient_match_their_exact_model(case):
+def _fwd_model(case):
+    """e4m3 operands of a forward case on the device, the bf16 bank they came from, and the fp64 result / sum of |products| of the
+    dequantised values"""
     from dcnet_amd import ops
     dev = torch.device("cuda:0")
     n, h, w, cin, cout, k, st = case
@@ -77,12 +78,40 @@ def test_f8_conv_forward_and_data_gradient_match_their_exact_model(case):
     w8, ws = ops.quant_rows_e4m3(wt.reshape(cout, T * cin).to(dev))
     _, _, xd = _mx_rows(x)
     _, _, wd = _mx_rows(wt.reshape(cout, T * cin))
-    xd = xd.permute(0, 3, 1, 2).requires_grad_(True)
+    xd = xd.permute(0, 3, 1, 2)
     wdq = wd.reshape(cout, k, k, cin).permute(0, 3, 1, 2)
-    yd = F.conv2d(xd, wdq, stride=st, padding=(k - 1) // 2)
-    ref_y = yd.detach().permute(0, 2, 3, 1)
-    abs_y = F.conv2d(xd.detach().abs(), wdq.abs(), stride=st, padding=(k - 1) // 2).permute(0, 2, 3, 1)      # sum of |products| per output
-    ho, wo = yd.shape[2], yd.shape[3]
+    ref_y = F.conv2d(xd, wdq, stride=st, padding=(k - 1) // 2).permute(0, 2, 3, 1)
+    abs_y = F.conv2d(xd.abs(), wdq.abs(), stride=st, padding=(k - 1) // 2).permute(0, 2, 3, 1)               # sum of |products| per output
+    return x8, xs, w8, ws, wt, ref_y, abs_y
+
+
+def _dgrad_model(case, wt, ho, wo):
+    """the same for the data gradient: dy quantised per pixel, the transposed bank [Cin][T][Cout] of wt per row"""
+    from dcnet_amd import ops
+    dev = torch.device("cuda:0")
+    n, h, w, cin, cout, k, st = case
+    T = k * k
+    dy = _bf(_rand(n, ho, wo, cout, seed=3) / 8 * torch.logspace(-2, 0, n * ho * wo).reshape(n, ho, wo, 1))
+    wt_t = wt.reshape(cout, T, cin).permute(2, 1, 0).contiguous().reshape(cin, T * cout)
+    dy8, dys = ops.quant_rows_e4m3(dy.to(dev))
+    wt8, wts = ops.quant_rows_e4m3(wt_t.to(dev))
+    _, _, dyd = _mx_rows(dy)
+    _, _, wtd = _mx_rows(wt_t)
+    w_for_dgrad = wtd.reshape(cin, k, k, cout).permute(3, 0, 1, 2)                    # OIHW from the dequantised transposed bank
+    xg = torch.zeros(n, cin, h, w, dtype=torch.float64, requires_grad=True)
+    F.conv2d(xg, w_for_dgrad, stride=st, padding=(k - 1) // 2).backward(dyd.permute(0, 3, 1, 2))
+    xg2 = torch.zeros(n, cin, h, w, dtype=torch.float64, requires_grad=True)
+    F.conv2d(xg2, w_for_dgrad.abs(), stride=st, padding=(k - 1) // 2).backward(dyd.abs().permute(0, 3, 1, 2))
+    return dy8, dys, wt8, wts, xg.grad.permute(0, 2, 3, 1), xg2.grad.permute(0, 2, 3, 1)
+
+
+@pytest.mark.parametrize("case", CASES)
+def test_f8_conv_forward_and_data_gradient_match_their_exact_model(case):
+    from dcnet_amd import ops
+    dev = torch.device("cuda:0")
+    n, h, w, cin, cout, k, st = case
+    x8, xs, w8, ws, wt, ref_y, abs_y = _fwd_model(case)
+    ho, wo = ref_y.shape[1], ref_y.shape[2]
     # ---- forward: raw result bf16 + BatchNorm partial sums of the stored values; fp32 output; epilogue ----
     y, stats = ops.conv2d_fwd_f8(x8, xs, w8.reshape(-1), ws, cout, k, st, want_stats=True)
     assert y.dtype == torch.bfloat16 and y.shape == (n, ho, wo, cout)
@@ -102,19 +131,7 @@ def test_f8_conv_forward_and_data_gradient_match_their_exact_model(case):
     # ---- data gradient: dy quantised per pixel, the transposed bank [Cin][T][Cout] per row ----
     if cout % 64:
         return
-    dy = _bf(_rand(n, ho, wo, cout, seed=3) / 8 * torch.logspace(-2, 0, n * ho * wo).reshape(n, ho, wo, 1))
-    wt_t = wt.reshape(cout, T, cin).permute(2, 1, 0).contiguous().reshape(cin, T * cout)
-    dy8, dys = ops.quant_rows_e4m3(dy.to(dev))
-    wt8, wts = ops.quant_rows_e4m3(wt_t.to(dev))
-    _, _, dyd = _mx_rows(dy)
-    _, _, wtd = _mx_rows(wt_t)
-    w_for_dgrad = wtd.reshape(cin, k, k, cout).permute(3, 0, 1, 2)                    # OIHW from the dequantised transposed bank
-    xg = torch.zeros(n, cin, h, w, dtype=torch.float64, requires_grad=True)
-    F.conv2d(xg, w_for_dgrad, stride=st, padding=(k - 1) // 2).backward(dyd.permute(0, 3, 1, 2))
-    ref_dx = xg.grad.permute(0, 2, 3, 1)
-    xg2 = torch.zeros(n, cin, h, w, dtype=torch.float64, requires_grad=True)
-    F.conv2d(xg2, w_for_dgrad.abs(), stride=st, padding=(k - 1) // 2).backward(dyd.abs().permute(0, 3, 1, 2))
-    abs_dx = xg2.grad.permute(0, 2, 3, 1)
+    dy8, dys, wt8, wts, ref_dx, abs_dx = _dgrad_model(case, wt, ho, wo)
     dx = ops.conv2d_bwd_data_f8(dy8, dys, wt8.reshape(-1), wts, (h, w), cin, k, st)
     _close(dx, ref_dx, abs_dx, "dgrad")
     base = _bf(_rand(n, h, w, cin, seed=7)).to(dev)
@@ -137,6 +154,38 @@ def test_f8_conv_forward_and_data_gradient_match_their_exact_model(case):
         sums = part.double().sum(0).cpu()
         assert torch.allclose(sums[0], g.reshape(-1, cin).sum(0), rtol=1e-4, atol=1e-4 * float(g.abs().reshape(-1, cin).sum(0).max()))
         assert torch.allclose(sums[1], (g * xh).reshape(-1, cin).sum(0), rtol=1e-4, atol=1e-4 * float((g * xh).abs().reshape(-1, cin).sum(0).max()))
+
+
+S2_EDGE_CASES = [
+    (1, 6, 10, 64, 64, 1, 2),          # 1x1 stride 2: one parity class has a tap, the other three receive no gradient
+    (1, 1, 8, 64, 64, 3, 2),           # a one-row map: the classes of the odd rows are empty
+]
+
+
+@pytest.mark.parametrize("case", S2_EDGE_CASES)
+def test_f8_stride2_classes_without_taps_or_pixels(case):
+    """Forward and data gradient where the parity classes of the stride-2 data gradient degenerate.  1x1: the pixels off the even-even
+    class get no tap and come back exactly zero, in a bf16 and in an fp32 dx (whatever the buffer held), and keep their content when the
+    launch accumulates.  One row: the two classes of odd rows have no pixel and are not launched.  Tolerances as for CASES."""
+    from dcnet_amd import ops
+    dev = torch.device("cuda:0")
+    n, h, w, cin, cout, k, st = case
+    x8, xs, w8, ws, wt, ref_y, abs_y = _fwd_model(case)
+    _close(ops.conv2d_fwd_f8(x8, xs, w8.reshape(-1), ws, cout, k, st)[0], ref_y, abs_y, "fwd")
+    dy8, dys, wt8, wts, ref_dx, abs_dx = _dgrad_model(case, wt, ref_y.shape[1], ref_y.shape[2])
+    dx = ops.conv2d_bwd_data_f8(dy8, dys, wt8.reshape(-1), wts, (h, w), cin, k, st,
+                                out=torch.full((n, h, w, cin), 3.0, dtype=torch.bfloat16, device=dev))
+    _close(dx, ref_dx, abs_dx, "dgrad")
+    dx32 = ops.conv2d_bwd_data_f8(dy8, dys, wt8.reshape(-1), wts, (h, w), cin, k, st, out=torch.full((n, h, w, cin), 3.0, device=dev), out_f32=True)
+    _close(dx32, ref_dx, abs_dx, "dgrad fp32 out", stored_bf16=False)
+    base = _bf(_rand(n, h, w, cin, seed=7)).to(dev)
+    acc = base.clone()
+    ops.conv2d_bwd_data_f8(dy8, dys, wt8.reshape(-1), wts, (h, w), cin, k, st, out=acc, accumulate=True)
+    _close(acc, ref_dx + base.double().cpu(), abs_dx, "dgrad accumulate")
+    untapped = torch.ones(h, w, dtype=torch.bool, device=dev)
+    untapped[::2 if k == 1 else 1, ::2 if k == 1 else 1] = False                       # (3x3: every pixel has a tap)
+    assert int(untapped.sum()) == (h * w - ((h + 1) // 2) * ((w + 1) // 2) if k == 1 else 0)
+    assert not bool(dx[:, untapped].any()) and not bool(dx32[:, untapped].any()) and torch.equal(acc[:, untapped], base[:, untapped])
 
 
 @pytest.mark.parametrize("c", [64, 128, 256, 512])

@@ -117,7 +117,12 @@ def test_conv2d_fwd_into_concat_slice(dev):
     assert float(buf[..., :64].abs().max()) == 0 and float(buf[..., 128:].abs().max()) == 0
 
 
-@pytest.mark.parametrize("case", [c for c in CONV_CASES if c[3] != 3 and c[4] % 32 == 0])
+# stride 2 where parity classes degenerate: 1x1 (three of the four classes get no tap: zeroed, or kept when accumulating) and a one-row map
+# (the classes of odd rows are empty; one launch per class even with the `merge` knob on, the merged launch wants two rows)
+S2_EDGE_CASES = [(1, 6, 10, 32, 32, 1, 2), (1, 1, 8, 32, 32, 3, 2)]
+
+
+@pytest.mark.parametrize("case", [c for c in CONV_CASES if c[3] != 3 and c[4] % 32 == 0] + S2_EDGE_CASES)
 def test_conv2d_bwd_data(dev, case):
     from dcnet_amd import ops
     n, h, w, cin, cout, k, s = case
@@ -126,7 +131,7 @@ def test_conv2d_bwd_data(dev, case):
     y = F.conv2d(x, wt.double(), None, s, (k - 1) // 2)
     dy = _rand(*y.shape, seed=11)
     y.backward(dy.double())
-    dx = ops.conv2d_bwd_data(ops.nchw_to_nhwc(dy.to(dev)), ops.weight_to_ohwi(wt.to(dev)), (h, w), k, s)
+    dx = ops.conv2d_bwd_data(ops.nchw_to_nhwc(dy.to(dev)), ops.weight_to_ohwi(wt.to(dev)), (h, w), k, s, out=torch.full((n, h, w, cin), 3.0, device=dev))
     _close(ops.nhwc_to_nchw(dx), x.grad.float(), 2e-5, "dgrad")
     # accumulate form
     base = _rand(n, cin, h, w, seed=12)
