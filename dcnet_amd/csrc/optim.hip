@@ -96,6 +96,17 @@ __global__ __launch_bounds__(64) void adam_prepare_clip_kernel(const StepChunk c
   adam_prepare_body(c, lr, lr_dev, beta1, beta2);
 }
 
+// AdamW: a third scalar per tensor, scal[2] = 1 - lr * weight_decay, formed in double from the step's learning rate (the device
+// scalar under lr_dev) and rounded once — torch forms it in Python and hands param.mul_ the double.  ctl = NULL: the plain form.
+__global__ __launch_bounds__(64) void adamw_prepare_kernel(const StepChunk c, float lr, const float* __restrict__ lr_dev, double beta1, double beta2,
+                                                           double wd, const int* __restrict__ ctl) {
+  if (ctl && ctl[CTL_APPLY] == 0) return;
+  adam_prepare_body(c, lr, lr_dev, beta1, beta2);
+  if (threadIdx.x != 0) return;
+  if (lr_dev) lr = lr_dev[0];
+  c.scal[blockIdx.x][2] = (float)(1.0 - (double)lr * wd);
+}
+
 struct AdamChunk {
   float* p[RMS_CHUNK]; const float* g[RMS_CHUNK]; float* m[RMS_CHUNK]; float* v[RMS_CHUNK]; const float* s[RMS_CHUNK]; long long n[RMS_CHUNK];
 };
@@ -112,7 +123,22 @@ __device__ __forceinline__ void adam_update(float& p, const float g0, float& m, 
   p = p - step_size * (m / denom);                       // param.addcdiv_(exp_avg, denom, value=-step_size)
 }
 
-template <bool CLIP>
+// AdamW (decoupled_weight_decay = True), torch 2.10's single-tensor order: param.mul_(1 - lr * weight_decay) first, then Adam's
+// update on the unmodified gradient.  `decay` = the factor, rounded once from double (adamw_prepare_kernel; scalar slot [2]); with
+// weight_decay = 0 it is exactly 1 and p * 1 keeps p's bits, which is torch skipping the multiplication.
+__device__ __forceinline__ void adamw_update(float& p, const float g, float& m, float& v, float step_size, float inv_bc2_sqrt, float decay,
+                                             float w1, float beta2, float w2, float eps) {
+#pragma clang fp contract(off)
+  const float q = p * decay;                             // param.mul_(1 - lr * weight_decay)
+  const float d = g - m;
+  m = w1 < 0.5f ? m + w1 * d : g - d * (1.f - w1);       // exp_avg.lerp_(grad, 1 - beta1)
+  v = v * beta2 + w2 * g * g;                            // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1-beta2)
+  const float denom = sqrtf(v) * inv_bc2_sqrt + eps;     // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
+  p = q - step_size * (m / denom);                       // param.addcdiv_(exp_avg, denom, value=-step_size)
+}
+
+// DECOUPLED = false is Adam as it was (two scalars per tensor, `wd` added to the gradient); true is AdamW (three scalars, `wd` unused)
+template <bool CLIP, bool DECOUPLED = false>
 __device__ __forceinline__ void adam_body(const AdamChunk& c, float w1, float beta2, float w2, float eps, float wd, const float* __restrict__ ctl) {
   float coef = 1.f;
   if (CLIP) {
@@ -122,6 +148,7 @@ __device__ __forceinline__ void adam_body(const AdamChunk& c, float w1, float be
   const int t = blockIdx.y;
   float* __restrict__ p = c.p[t]; const float* __restrict__ g = c.g[t]; float* __restrict__ m = c.m[t]; float* __restrict__ v = c.v[t];
   const float step_size = c.s[t][0], inv_bc2_sqrt = c.s[t][1];          // (adam_prepare_kernel wrote them in the launch before this one)
+  const float decay = DECOUPLED ? c.s[t][2] : 1.f;
   const long long n = c.n[t];
   const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
   const long long n4 = vec ? n / 4 : 0;
@@ -131,13 +158,25 @@ __device__ __forceinline__ void adam_body(const AdamChunk& c, float w1, float be
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float a = pp[e], b = mm[e], d = vv[e];
-      adam_update(a, CLIP ? clip_mul(gg[e], coef) : gg[e], b, d, step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
+      const float ge = CLIP ? clip_mul(gg[e], coef) : gg[e];
+      if (DECOUPLED) adamw_update(a, ge, b, d, step_size, inv_bc2_sqrt, decay, w1, beta2, w2, eps);
+      else adam_update(a, ge, b, d, step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
       pp[e] = a; mm[e] = b; vv[e] = d;
     }
     reinterpret_cast<f32x4*>(p)[i] = pp; reinterpret_cast<f32x4*>(m)[i] = mm; reinterpret_cast<f32x4*>(v)[i] = vv;
   }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    adam_update(p[i], CLIP ? clip_mul(g[i], coef) : g[i], m[i], v[i], step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
+  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+    const float ge = CLIP ? clip_mul(g[i], coef) : g[i];
+    if (DECOUPLED) adamw_update(p[i], ge, m[i], v[i], step_size, inv_bc2_sqrt, decay, w1, beta2, w2, eps);
+    else adam_update(p[i], ge, m[i], v[i], step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
+  }
+}
+
+__global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps) {
+  adam_body<false, true>(c, w1, beta2, w2, eps, 0.f, nullptr);
+}
+__global__ __launch_bounds__(256) void adamw_clip_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, const float* __restrict__ ctl) {
+  adam_body<true, true>(c, w1, beta2, w2, eps, 0.f, ctl);
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, float wd) {
@@ -191,6 +230,85 @@ __global__ __launch_bounds__(256) void sgd_kernel(const RmsChunk c, float lr, co
 __global__ __launch_bounds__(256) void sgd_clip_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float mu, float wd,
                                                        const float* __restrict__ ctl) {
   sgd_body<true>(c, lr, lr_dev, mu, wd, ctl);
+}
+
+// ---- exponential moving average of the weights, and the in-place swap ------------------------------------------------------------
+// shadow <- lerp(shadow, src, w) over every shadowed tensor: 8 B read + 4 B written per value.  The weight w = 1 - d_t depends on the
+// count t of updates applied, which — like Adam's — lives on the device so that a replayed step advances it: ema_prepare_kernel (one
+// thread, in front of the update) advances the step word and forms w in double; a skipped step (apply = 0) leaves both words alone.
+__global__ __launch_bounds__(64) void ema_prepare_kernel(int* __restrict__ step, float* __restrict__ w, double decay, double tau,
+                                                         const int* __restrict__ ctl) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  if (ctl && ctl[CTL_APPLY] == 0) return;
+  const int t = step[0] + 1;
+  step[0] = t;
+  const double d = tau > 0.0 ? decay * (1.0 - exp(-(double)t / tau)) : decay;
+  w[0] = (float)(1.0 - d);
+}
+
+struct EmaChunk { float* s[RMS_CHUNK]; const float* x[RMS_CHUNK]; long long n[RMS_CHUNK]; };
+struct SwapChunk { float* a[RMS_CHUNK]; float* b[RMS_CHUNK]; long long n[RMS_CHUNK]; };
+
+// torch's fp32 lerp (the form adam_update uses for exp_avg).  x == s gives d = 0 and keeps s bit for bit in either form, but for
+// s = -0.0 under w < 0.5 (-0 + 0 is +0): the select keeps that one too, so a tensor nobody trains never changes a bit.
+__device__ __forceinline__ float ema_lerp(const float s, const float x, const float w) {
+#pragma clang fp contract(off)
+  const float d = x - s;
+  const float r = w < 0.5f ? s + w * d : x - d * (1.f - w);
+  return d == 0.f ? s : r;
+}
+__device__ __forceinline__ f32x4 ema_lerp4(f32x4 s, const f32x4 x, const float w) {
+#pragma unroll
+  for (int e = 0; e < 4; ++e) s[e] = ema_lerp(s[e], x[e], w);
+  return s;
+}
+
+__global__ __launch_bounds__(256) void ema_update_kernel(const EmaChunk c, const float* __restrict__ wp, const int* __restrict__ ctl) {
+  if (ctl && ctl[CTL_APPLY] == 0) return;
+  const float w = wp[0];                      // (ema_prepare_kernel wrote it in the launch before this one)
+  const int t = blockIdx.y;
+  float* __restrict__ s = c.s[t]; const float* __restrict__ x = c.x[t];
+  const long long n = c.n[t];
+  const bool vec = ((((uintptr_t)s | (uintptr_t)x) & 15) == 0);
+  const long long n4 = vec ? n / 4 : 0;
+  const long long stride = (long long)gridDim.x * 256;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  // two trips at once: four 16-byte loads in flight per thread (the pass has two streams where the optimiser updates have three or four)
+  for (; i + stride < n4; i += 2 * stride) {
+    const f32x4 s0 = reinterpret_cast<f32x4*>(s)[i], s1 = reinterpret_cast<f32x4*>(s)[i + stride];
+    const f32x4 x0 = reinterpret_cast<const f32x4*>(x)[i], x1 = reinterpret_cast<const f32x4*>(x)[i + stride];
+    reinterpret_cast<f32x4*>(s)[i] = ema_lerp4(s0, x0, w);
+    reinterpret_cast<f32x4*>(s)[i + stride] = ema_lerp4(s1, x1, w);
+  }
+  for (; i < n4; i += stride)
+    reinterpret_cast<f32x4*>(s)[i] = ema_lerp4(reinterpret_cast<f32x4*>(s)[i], reinterpret_cast<const f32x4*>(x)[i], w);
+  for (i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
+    s[i] = ema_lerp(s[i], x[i], w);
+}
+
+// a <-> b: 8 B read + 8 B written per value; every value is moved by exactly one thread
+__global__ __launch_bounds__(256) void tensor_swap_kernel(const SwapChunk c) {
+  const int t = blockIdx.y;
+  float* __restrict__ a = c.a[t]; float* __restrict__ b = c.b[t];
+  const long long n = c.n[t];
+  const bool vec = ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
+  const long long n4 = vec ? n / 4 : 0;
+  const long long stride = (long long)gridDim.x * 256;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {
+    const f32x4 a0 = reinterpret_cast<f32x4*>(a)[i], a1 = reinterpret_cast<f32x4*>(a)[i + stride];
+    const f32x4 b0 = reinterpret_cast<f32x4*>(b)[i], b1 = reinterpret_cast<f32x4*>(b)[i + stride];
+    reinterpret_cast<f32x4*>(a)[i] = b0; reinterpret_cast<f32x4*>(a)[i + stride] = b1;
+    reinterpret_cast<f32x4*>(b)[i] = a0; reinterpret_cast<f32x4*>(b)[i + stride] = a1;
+  }
+  for (; i < n4; i += stride) {
+    const f32x4 a0 = reinterpret_cast<f32x4*>(a)[i], b0 = reinterpret_cast<f32x4*>(b)[i];
+    reinterpret_cast<f32x4*>(a)[i] = b0; reinterpret_cast<f32x4*>(b)[i] = a0;
+  }
+  for (i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    const float a0 = a[i], b0 = b[i];
+    a[i] = b0; b[i] = a0;
+  }
 }
 
 // blocks along x for a chunk whose longest tensor has `biggest` values (grid-stride beyond 128)
@@ -516,4 +634,122 @@ extern "C" int dcn_sgd_step_clipped(float* const* params, const float* const* gr
                                     float lr, const float* lr_dev, float momentum, float weight_decay, const void* ctrl, void* stream) {
   DCN_CHECK_ARG(ctrl, "sgd_step_clipped: no control block");
   return sgd_step("sgd_step_clipped", params, grads, momentum_bufs, numel, count, lr, lr_dev, momentum, weight_decay, (const float*)ctrl, stream);
+}
+
+// AdamW (decoupled weight decay): its own entry points, three scalars per tensor — Adam's keep theirs and their two.
+static int adamw_prepare(const char* who, int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                         double weight_decay, const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(steps && scal && count > 0, "%s: bad argument", who);
+  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
+  DCN_CHECK_ARG(weight_decay >= 0.0, "%s: negative weight_decay", who);
+  for (int base = 0; base < count; base += STEP_CHUNK) {
+    StepChunk c{};
+    const int m = count - base < STEP_CHUNK ? count - base : STEP_CHUNK;
+    for (int i = 0; i < m; ++i) {
+      DCN_CHECK_ARG(steps[base + i] && scal[base + i], "%s: null tensor %d", who, base + i);
+      c.step[i] = steps[base + i]; c.scal[i] = scal[base + i];
+    }
+    hipLaunchKernelGGL(adamw_prepare_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2, weight_decay, (const int*)ctrl);
+    DCN_CHECK_LAUNCH(who);
+  }
+  return DCN_OK;
+}
+
+extern "C" int dcn_adamw_prepare(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                                 double weight_decay, void* stream) {
+  return adamw_prepare("adamw_prepare", steps, scal, count, lr, lr_dev, beta1, beta2, weight_decay, nullptr, stream);
+}
+
+extern "C" int dcn_adamw_prepare_clipped(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                                         double weight_decay, const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(ctrl, "adamw_prepare_clipped: no control block");
+  return adamw_prepare("adamw_prepare_clipped", steps, scal, count, lr, lr_dev, beta1, beta2, weight_decay, ctrl, stream);
+}
+
+static int adamw_step(const char* who, float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                      const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, const void* ctrl,
+                      void* stream) {
+  DCN_CHECK_ARG(params && grads && exp_avgs && exp_avg_sqs && scal && numel && count > 0, "%s: bad argument", who);
+  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
+  DCN_CHECK_ARG(eps >= 0.f, "%s: negative eps", who);
+  for (int base = 0; base < count; base += RMS_CHUNK) {
+    AdamChunk c{};
+    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
+    long long biggest = 0;
+    for (int i = 0; i < m; ++i) {
+      const int k = base + i;
+      DCN_CHECK_ARG(params[k] && grads[k] && exp_avgs[k] && exp_avg_sqs[k] && scal[k] && numel[k] >= 0, "%s: null tensor %d", who, k);
+      c.p[i] = params[k]; c.g[i] = grads[k]; c.m[i] = exp_avgs[k]; c.v[i] = exp_avg_sqs[k]; c.s[i] = scal[k]; c.n[i] = numel[k];
+      if (c.n[i] > biggest) biggest = c.n[i];
+    }
+    if (ctrl)
+      hipLaunchKernelGGL(adamw_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
+                         (float)(1.0 - beta2), eps, (const float*)ctrl);
+    else
+      hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
+                         (float)(1.0 - beta2), eps);
+    DCN_CHECK_LAUNCH(who);
+  }
+  return DCN_OK;
+}
+
+extern "C" int dcn_adamw_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                              const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, void* stream) {
+  return adamw_step("adamw_step", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, nullptr, stream);
+}
+
+extern "C" int dcn_adamw_step_clipped(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                      const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
+                                      const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(ctrl, "adamw_step_clipped: no control block");
+  return adamw_step("adamw_step_clipped", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, ctrl, stream);
+}
+
+// ---- weight EMA and swap: any count (0 launches nothing), tensors of 0 values allowed (their pointers may be NULL) -----------------
+extern "C" int dcn_ema_prepare(int* step, float* w, double decay, double tau, const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(step && w, "ema_prepare: bad argument");
+  DCN_CHECK_ARG(decay >= 0.0 && decay < 1.0, "ema_prepare: decay %g outside [0, 1)", decay);
+  DCN_CHECK_ARG(tau >= 0.0, "ema_prepare: tau %g is negative", tau);          // (a NaN fails both tests)
+  hipLaunchKernelGGL(ema_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step, w, decay, tau, (const int*)ctrl);
+  DCN_CHECK_LAUNCH("ema_prepare");
+  return DCN_OK;
+}
+
+extern "C" int dcn_ema_update(float* const* shadow, const float* const* src, const int64_t* numel, int count, const float* w, const void* ctrl,
+                              void* stream) {
+  DCN_CHECK_ARG(count >= 0 && w && (count == 0 || (shadow && src && numel)), "ema_update: bad argument");
+  for (int i = 0; i < count; ++i)
+    DCN_CHECK_ARG(numel[i] >= 0 && (numel[i] == 0 || (shadow[i] && src[i])), "ema_update: null tensor %d", i);
+  for (int base = 0; base < count; base += RMS_CHUNK) {
+    EmaChunk c{};
+    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
+    long long biggest = 0;
+    for (int i = 0; i < m; ++i) {
+      c.s[i] = shadow[base + i]; c.x[i] = src[base + i]; c.n[i] = numel[base + i];
+      if (c.n[i] > biggest) biggest = c.n[i];
+    }
+    if (biggest == 0) continue;                // a chunk of empty tensors
+    hipLaunchKernelGGL(ema_update_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, w, (const int*)ctrl);
+    DCN_CHECK_LAUNCH("ema_update");
+  }
+  return DCN_OK;
+}
+
+extern "C" int dcn_tensor_swap(float* const* a, float* const* b, const int64_t* numel, int count, void* stream) {
+  DCN_CHECK_ARG(count >= 0 && (count == 0 || (a && b && numel)), "tensor_swap: bad argument");
+  for (int i = 0; i < count; ++i)
+    DCN_CHECK_ARG(numel[i] >= 0 && (numel[i] == 0 || (a[i] && b[i])), "tensor_swap: null tensor %d", i);
+  for (int base = 0; base < count; base += RMS_CHUNK) {
+    SwapChunk c{};
+    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
+    long long biggest = 0;
+    for (int i = 0; i < m; ++i) {
+      c.a[i] = a[base + i]; c.b[i] = b[base + i]; c.n[i] = numel[base + i];
+      if (c.n[i] > biggest) biggest = c.n[i];
+    }
+    if (biggest == 0) continue;
+    hipLaunchKernelGGL(tensor_swap_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c);
+    DCN_CHECK_LAUNCH("tensor_swap");
+  }
+  return DCN_OK;
 }

@@ -131,6 +131,13 @@ SIGNATURES = {
     "dcn_adam_prepare_clipped": (I, [P, P, I, F, P, D, D, P, P]),
     "dcn_adam_step_clipped": (I, [P, P, P, P, P, P, I, D, D, F, F, P, P]),
     "dcn_sgd_step_clipped": (I, [P, P, P, P, I, F, P, F, F, P, P]),
+    "dcn_adamw_prepare": (I, [P, P, I, F, P, D, D, D, P]),
+    "dcn_adamw_step": (I, [P, P, P, P, P, P, I, D, D, F, P]),
+    "dcn_adamw_prepare_clipped": (I, [P, P, I, F, P, D, D, D, P, P]),
+    "dcn_adamw_step_clipped": (I, [P, P, P, P, P, P, I, D, D, F, P, P]),
+    "dcn_ema_prepare": (I, [P, P, D, D, P, P]),
+    "dcn_ema_update": (I, [P, P, P, I, P, P, P]),
+    "dcn_tensor_swap": (I, [P, P, P, I, P]),
     "dcn_fusion_prefill": (I, [P, P, P, I, P, I, I, I, P]),
     "dcn_fusion_bwd_ws": (L, [I, I]),
     "dcn_fusion_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
@@ -184,7 +191,7 @@ _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",
                 "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes",
                 "dcn_conv1_tile", "dcn_l2norm_score_fwd_form", "dcn_bn_apply_form", "dcn_igemm_split_build", "dcn_gemm3_variant"}
-ABI_VERSION = 315        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
+ABI_VERSION = 316        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
 
 
 class DcnError(RuntimeError):

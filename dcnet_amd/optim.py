@@ -29,9 +29,20 @@ Under ``skip_nonfinite`` the host cannot know whether a step was applied, so its
 RMSprop (whose ``step`` is bookkeeping only) subtracts the skips it has not yet accounted for, SGD has no counter.
 
 ``clip_grad_norm_`` is the stand-alone form with torch's in-place semantics, for a caller that keeps a torch optimiser.
+
+``AdamW`` (and ``Adam(decoupled_weight_decay=True)``, torch's spelling of the same thing) is torch 2.10's single-tensor AdamW:
+``param.mul_(1 - lr * weight_decay)``, then Adam's update on the unmodified gradient (dcn_adamw_prepare + dcn_adamw_step; the factor
+is formed on the device, in double, from the step's learning rate).  Groups and ``state_dict`` are ``torch.optim.AdamW``'s.
+
+``WeightEMA`` keeps an exponential moving average of a model's weights and running statistics in shadow tensors, updated by two
+launches (dcn_ema_prepare + dcn_ema_update) that the fused optimisers append to their step (``opt.attach_ema(ema)``), so the update
+is part of the replayed training step and a ``skip_nonfinite`` step skips it too.  ``ema.swap()`` / ``with ema.applied():`` exchange
+the average with the model's tensors **in place** (dcn_tensor_swap): parameter addresses, optimiser state and a captured graph
+stay valid, evaluation needs no third copy.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes
 import math
 
@@ -65,6 +76,18 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._lr_dev = {}
         self._stepped = []           # the "step" counters touched by the last step() (bump_steps: replays of a captured step)
         self._stepped_params = []    # ... and whose they are (load_state_dict replaces the counters)
+        self._ema = None             # attach_ema: a WeightEMA whose update closes every step
+
+    def attach_ema(self, ema) -> None:
+        """Make the end of every ``step()`` call ``ema.update(ctl)`` (a ``WeightEMA``; ``None`` detaches) with the address of the step's
+        clipping control block (0 without clipping): the average follows the parameters inside the step — eager or captured — and a
+        step that ``skip_nonfinite`` turned into a no-op leaves the average and its update count alone.  Attach BEFORE building a
+        ``GraphedTrainStep``: the capture records the launches ``step()`` makes at that moment, so an EMA attached afterwards would
+        never run in the replays (and one detached afterwards would keep running).  A step without any gradient updates nothing,
+        the average included.  With no EMA attached ``step()`` launches exactly what it launched before there was one."""
+        if ema is not None and not isinstance(ema, WeightEMA):
+            raise TypeError(f"{self._name()}.attach_ema: a dcnet_amd.optim.WeightEMA or None, not {type(ema).__name__}")
+        self._ema = ema
 
     def sync_lr(self, device=None) -> None:
         """Upload every group's current ``lr`` into its device scalar when it changed (async, from page-locked memory).
@@ -208,6 +231,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 if "step" in st:
                     st["step"] += 1
                     self._stepped.append(st["step"]); self._stepped_params.append(p)
+        if self._ema is not None:
+            self._ema.update(ctl)
         return loss
 
     def load_state_dict(self, state_dict) -> None:
@@ -253,17 +278,22 @@ class Adam(_FusedOptimizer):
     ``step`` scalar of the state (torch's layout: what ``state_dict()`` carries) every parameter has a device step word, which the
     step's own first launch advances and turns into the step's two scalars (``lr / (1 - beta1^t)``, ``1 / sqrt(1 - beta2^t)``) — in
     an eager step and in a captured one alike.  The words are made from the host counters when a group first steps and again by
-    ``load_state_dict``; a parameter without a gradient is left out of the launches and keeps its count, as in torch."""
+    ``load_state_dict``; a parameter without a gradient is left out of the launches and keeps its count, as in torch.
+
+    ``decoupled_weight_decay=True`` (constructor argument and group key, torch's) makes a group's step AdamW's: dcn_adamw_prepare +
+    dcn_adamw_step, three scalars per parameter instead of two (the third: ``1 - lr * weight_decay``).  A group without it runs the
+    entry points, kernels and two-scalar slots it always ran."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 amsgrad: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False):
+                 amsgrad: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False,
+                 decoupled_weight_decay: bool = False):
         if amsgrad or maximize:
-            raise NotImplementedError("dcnet_amd.optim.Adam implements amsgrad=False, maximize=False (the reference's setting)")
+            raise NotImplementedError(f"dcnet_amd.optim.{type(self).__name__} implements amsgrad=False, maximize=False (the reference's setting)")
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid hyper-parameter")
         # (the keys and values of torch.optim.Adam's groups: a state_dict loaded into torch's class brings its groups along)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
-                                      capturable=False, differentiable=False, fused=None, decoupled_weight_decay=False),
+                                      capturable=False, differentiable=False, fused=None, decoupled_weight_decay=bool(decoupled_weight_decay)),
                          max_grad_norm, skip_nonfinite)
         self._tables = {}            # group index -> device step words and scalar slots of the group's parameters
 
@@ -276,19 +306,24 @@ class Adam(_FusedOptimizer):
 
     def _table(self, gi, group, device):
         tab = self._tables.get(gi)
+        width = 3 if group.get("decoupled_weight_decay") else 2
+        if tab is not None and len(tab["index"]) == len(group["params"]) and tab["scal"].shape[1] != width:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._name()}: decoupled_weight_decay of a group changed: run an eager step before capturing one")
+            tab["scal"] = torch.zeros(len(group["params"]), width, dtype=torch.float32, device=device)       # (the step words stay)
         if tab is None or len(tab["index"]) != len(group["params"]):
             if torch.cuda.is_current_stream_capturing():
                 raise RuntimeError(f"{self._name()}: the first step of a group cannot be a captured one (its device step words are made "
                                    "from the host counters); run an eager step first")
             n = len(group["params"])
-            tab = {"steps": self._host_steps(group).to(device), "scal": torch.zeros(n, 2, dtype=torch.float32, device=device),
+            tab = {"steps": self._host_steps(group).to(device), "scal": torch.zeros(n, width, dtype=torch.float32, device=device),
                    "index": {id(p): i for i, p in enumerate(group["params"])}}
             self._tables[gi] = tab
         return tab
 
     def _check_group(self, group):
-        if group.get("amsgrad") or group.get("maximize") or group.get("decoupled_weight_decay"):
-            raise NotImplementedError(f"{self._name()}: amsgrad / maximize / decoupled_weight_decay are not implemented")
+        if group.get("amsgrad") or group.get("maximize"):
+            raise NotImplementedError(f"{self._name()}: amsgrad / maximize are not implemented")
 
     def _reconcile_steps(self) -> None:
         """The device step words are the truth under ``skip_nonfinite`` (a skipped step does not advance them): copy them into the host
@@ -307,8 +342,20 @@ class Adam(_FusedOptimizer):
         n = len(live)
         rows = [tab["index"][id(p)] for p, _, _ in live]
         s0, c0 = tab["steps"].data_ptr(), tab["scal"].data_ptr()
-        scal = _ptrs([c0 + 8 * r for r in rows])
+        scal = _ptrs([c0 + 4 * tab["scal"].shape[1] * r for r in rows])
         b1, b2 = (float(b) for b in group["betas"])
+        if group.get("decoupled_weight_decay"):
+            prep = (_ptrs([s0 + 4 * r for r in rows]), scal, n, float(group["lr"]), lr_dev, b1, b2, float(group["weight_decay"]))
+            args = (_ptrs([p.data_ptr() for p, _, _ in live]), _ptrs([g.data_ptr() for _, g, _ in live]),
+                    _ptrs([st["exp_avg"].data_ptr() for _, _, st in live]), _ptrs([st["exp_avg_sq"].data_ptr() for _, _, st in live]), scal,
+                    (ctypes.c_int64 * n)(*[p.numel() for p, _, _ in live]), n, b1, b2, float(group["eps"]))
+            if ctl:
+                L.adamw_prepare_clipped(*prep, ctl, stream)
+                L.adamw_step_clipped(*args, ctl, stream)
+            else:
+                L.adamw_prepare(*prep, stream)
+                L.adamw_step(*args, stream)
+            return
         prep = (_ptrs([s0 + 4 * r for r in rows]), scal, n, float(group["lr"]), lr_dev, b1, b2)
         args = (_ptrs([p.data_ptr() for p, _, _ in live]), _ptrs([g.data_ptr() for _, g, _ in live]),
                 _ptrs([st["exp_avg"].data_ptr() for _, _, st in live]), _ptrs([st["exp_avg_sq"].data_ptr() for _, _, st in live]), scal,
@@ -332,6 +379,16 @@ class Adam(_FusedOptimizer):
                 del self._tables[gi]                     # (the group changed: its next eager step makes the table)
             else:
                 tab["steps"].copy_(self._host_steps(group))      # in place: a captured step keeps reading these words
+
+
+class AdamW(Adam):
+    """``torch.optim.AdamW``: ``Adam`` with ``decoupled_weight_decay=True`` and torch's defaults (``lr=1e-3``, ``weight_decay=1e-2``).
+    Groups and ``state_dict`` are ``torch.optim.AdamW``'s, so states load both ways."""
+
+    def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
+                 amsgrad: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, decoupled_weight_decay=True)
 
 
 class SGD(_FusedOptimizer):
@@ -408,3 +465,145 @@ def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_i
             raise RuntimeError(f"The total norm of order 2.0 for gradients from `parameters` is non-finite ({float(norm)}), so it cannot be clipped")
         L.grad_scale(ptrs, numel, n, ctrl.data_ptr(), stream)
     return norm
+
+
+def weight_at(t: int, decay: float, tau: float) -> float:
+    """The weight ``w_t = 1 - d_t`` of the ``t``-th applied update (t = 1, 2, ...) of a ``WeightEMA``: ``shadow <- lerp(shadow, theta, w_t)``
+    with ``d_t = decay * (1 - exp(-t / tau))`` for ``tau > 0`` (the warm-up ramp of the YOLO recipes: early averages follow the weights
+    closely) and ``d_t = decay`` for ``tau == 0``.  Host arithmetic in double — what dcn_ema_prepare rounds to fp32 on the device."""
+    return 1.0 - (decay * (1.0 - math.exp(-t / tau)) if tau > 0 else decay)
+
+
+class WeightEMA:
+    """An exponential moving average of a model's weights, kept on the device and updated inside the fused training step.
+
+    ``WeightEMA(model, decay=0.9999, tau=2000.0)`` (``model`` may be DDP-wrapped) shadows every floating-point entry of
+    ``model.state_dict()`` — parameters and BatchNorm running statistics; integer buffers such as ``num_batches_tracked`` are not
+    shadowed.  The shadows start as copies (``shadow_0 = theta_0``); they, the device step word, the weight word and the pointer
+    tables exist from construction on, so an update allocates nothing and can be captured.  Contiguous fp32 CUDA tensors only.  The
+    tables hold the addresses of the model's tensors: like a captured graph, the EMA is valid while they stay where they are
+    (``load_state_dict`` and the optimisers write in place; ``model.to(...)`` moves them).
+
+    ``update(ctl=0)``   ``shadow <- lerp(shadow, theta, w_t)``, ``w_t = weight_at(t, decay, tau)`` with ``t`` the count of applied
+                        updates, advanced on the device (dcn_ema_prepare + dcn_ema_update on the current stream).  ``ctl``: the address
+                        of a clipping control block whose ``apply`` word gates both.  ``opt.attach_ema(ema)`` makes the fused
+                        optimisers call it at the end of ``step()``; with a torch optimiser call it yourself after ``step()``.
+    ``swap()``          exchanges shadows and model tensors in place (dcn_tensor_swap).  ``swapped`` tells which way round they are;
+                        ``update`` raises while swapped.
+    ``applied()``       ``with ema.applied(): evaluate(model, ...)`` — swap, yield, swap back; the round trip is bitwise.
+    ``copy_to(model)``  the one-way case: the averages overwrite ``model``'s tensors (this model or another of the same layout).
+    ``updates()``       the device step word (synchronises).
+    ``state_dict()`` / ``load_state_dict()``   ``{"decay", "tau", "updates", "shadow": {state_dict key: tensor}}``; loading copies into the
+                        existing shadows and step word in place (a captured update keeps reading them), strict on keys and shapes.
+                        ``decay`` and ``tau`` are recorded, the constructor's stay in force."""
+
+    weight_at = staticmethod(weight_at)
+
+    def __init__(self, model, decay: float = 0.9999, tau: float = 2000.0):
+        if isinstance(decay, bool) or not isinstance(decay, (int, float)) or not 0.0 <= decay < 1.0:
+            raise ValueError(f"WeightEMA: decay must be a number in [0, 1), not {decay!r}")
+        if isinstance(tau, bool) or not isinstance(tau, (int, float)) or not (tau >= 0.0 and math.isfinite(tau)):
+            raise ValueError(f"WeightEMA: tau must be a finite number >= 0, not {tau!r}")
+        self.decay, self.tau = float(decay), float(tau)
+        core = model.module if hasattr(model, "module") else model
+        self._keys, self._src, self._shadow = [], [], []
+        for k, v in core.state_dict().items():
+            if not v.is_floating_point():
+                continue
+            if not (v.is_cuda and v.dtype == torch.float32 and v.is_contiguous()):
+                raise RuntimeError(f"dcnet_amd.optim.WeightEMA: contiguous fp32 CUDA tensors only (no CPU path): {k}")
+            self._keys.append(k); self._src.append(v.detach())
+        if not self._src:
+            raise RuntimeError("dcnet_amd.optim.WeightEMA: the model has no floating-point tensor to average")
+        self.device = self._src[0].device
+        if any(v.device != self.device for v in self._src):
+            raise RuntimeError("dcnet_amd.optim.WeightEMA: the model's tensors live on more than one device")
+        for v in self._src:
+            s = torch.empty_like(v, memory_format=torch.contiguous_format)
+            s.copy_(v)
+            self._shadow.append(s)
+        self._step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._w = torch.zeros(1, dtype=torch.float32, device=self.device)
+        n = self._count = len(self._src)
+        self._p_shadow = _ptrs([s.data_ptr() for s in self._shadow])
+        self._p_src = _ptrs([v.data_ptr() for v in self._src])
+        self._numel = (ctypes.c_int64 * n)(*[v.numel() for v in self._src])
+        self._swapped = False
+
+    def _stream(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    @property
+    def swapped(self) -> bool:
+        """True while the model holds the averages and the shadows hold the raw weights."""
+        return self._swapped
+
+    @property
+    def shadow(self) -> dict:
+        """state_dict key -> shadow tensor (the tensors themselves)."""
+        return dict(zip(self._keys, self._shadow))
+
+    def update(self, ctl: int = 0) -> None:
+        if self._swapped:
+            raise RuntimeError("dcnet_amd.optim.WeightEMA.update: the model holds the averages (swap() / applied()): swap back first")
+        L = lib()
+        stream = self._stream()
+        L.ema_prepare(self._step.data_ptr(), self._w.data_ptr(), self.decay, self.tau, ctl, stream)
+        L.ema_update(self._p_shadow, self._p_src, self._numel, self._count, self._w.data_ptr(), ctl, stream)
+
+    def swap(self) -> None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dcnet_amd.optim.WeightEMA.swap: not during a stream capture")
+        lib().tensor_swap(self._p_shadow, self._p_src, self._numel, self._count, self._stream())
+        self._swapped = not self._swapped
+
+    @contextlib.contextmanager
+    def applied(self):
+        self.swap()
+        try:
+            yield self
+        finally:
+            self.swap()
+
+    def updates(self) -> int:
+        return int(self._step.item())
+
+    def _not_swapped(self, what):
+        if self._swapped:
+            raise RuntimeError(f"dcnet_amd.optim.WeightEMA.{what}: the shadows hold the raw weights (swap() / applied()): swap back first")
+
+    def state_dict(self) -> dict:
+        self._not_swapped("state_dict")
+        return {"decay": self.decay, "tau": self.tau, "updates": self.updates(), "shadow": self.shadow}
+
+    def load_state_dict(self, state: dict) -> None:
+        self._not_swapped("load_state_dict")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("dcnet_amd.optim.WeightEMA.load_state_dict: not during a stream capture")
+        src = {(k[7:] if k.startswith("module.") else k): v for k, v in state["shadow"].items()}
+        missing, unexpected = [k for k in self._keys if k not in src], [k for k in src if k not in set(self._keys)]
+        if missing or unexpected:
+            raise KeyError(f"WeightEMA.load_state_dict: missing keys {missing[:5]}{'...' if len(missing) > 5 else ''}, "
+                           f"unexpected keys {unexpected[:5]}{'...' if len(unexpected) > 5 else ''}")
+        for k, s in zip(self._keys, self._shadow):
+            if tuple(src[k].shape) != tuple(s.shape):
+                raise ValueError(f"WeightEMA.load_state_dict: {k} has shape {tuple(src[k].shape)}, the shadow {tuple(s.shape)}")
+        updates = int(state["updates"])
+        if updates < 0:
+            raise ValueError(f"WeightEMA.load_state_dict: updates = {updates}")
+        with torch.no_grad():
+            for k, s in zip(self._keys, self._shadow):
+                s.copy_(src[k])
+            self._step.fill_(updates)
+
+    @torch.no_grad()
+    def copy_to(self, model) -> None:
+        self._not_swapped("copy_to")
+        core = model.module if hasattr(model, "module") else model
+        dst = {k: v for k, v in core.state_dict().items() if v.is_floating_point()}
+        if list(dst) != self._keys:
+            raise KeyError("WeightEMA.copy_to: the model's floating-point state_dict keys are not the shadowed ones")
+        for k, s in zip(self._keys, self._shadow):
+            if tuple(dst[k].shape) != tuple(s.shape):
+                raise ValueError(f"WeightEMA.copy_to: {k} has shape {tuple(dst[k].shape)}, the shadow {tuple(s.shape)}")
+            dst[k].copy_(s)

@@ -1,12 +1,15 @@
 """Training / evaluation harness around the hot path — the pieces of train_DCNet.py that a caller needs
 to drive ``grounding_model`` without the reference's data pipeline:
 
-  * ``make_optimizer``      RMSprop with the reference's two parameter groups, or its Adam / SGD (train_DCNet.py:519-534)
+  * ``make_optimizer``      RMSprop with the reference's two parameter groups, or its Adam / SGD (train_DCNet.py:519-534), or AdamW
   * ``adjust_learning_rate`` polynomial decay (train_DCNet.py:241-253)
   * ``train_step``          forward + five losses + backward + step, no host sync inside
   * ``evaluate``            eval forward + box decode + Acc@0.5 / mean IoU (train_DCNet.py:764-816)
   * ``save_checkpoint`` / ``load_checkpoint`` / ``load_pretrain``   the reference's ``.pth.tar`` dict
     (train_DCNet.py:255-263, 485-514) including the ``module.`` key prefix left by DDP wrappers
+
+``--ema-decay D`` / ``--ema-tau T`` keep an exponential moving average of the weights inside the fused step (``dcnet_amd.optim.WeightEMA``);
+the closing evaluation then reports the raw and the averaged weights.
 
 ``python -m dcnet_amd.train --steps 20`` (``--freeze-bn backbone|all``: BatchNorm on its running statistics) runs a short synthetic-data training loop on one GPU; with ``--raw-frames`` every step's
 ``image`` / ``bbox`` come from synthetic uint8 frames of mixed sizes (1280x720 and 500x375) through the on-device clip
@@ -30,9 +33,10 @@ def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: b
     """The optimiser the reference builds for ``--optimizer`` (train_DCNet.py:519-534).  ``model`` may be DDP-wrapped.
 
     ``"RMSprop"`` (the default): two groups, everything except the backbone at ``lr``, the Darknet backbone at ``lr / 10``; weight
-    decay 5e-4.  ``"adam"``: one group over all parameters, weight decay 5e-4.  ``"sgd"``: one group, momentum 0.99.  All three are
+    decay 5e-4.  ``"adam"``: one group over all parameters, weight decay 5e-4.  ``"sgd"``: one group, momentum 0.99.  ``"adamw"`` (not
+    in the reference; what fine-tuning recipes pair with a weight EMA): one group, decoupled weight decay 1e-2.  All are
     the fused classes of ``dcnet_amd.optim`` (torch's update as one HIP pass, torch's ``state_dict`` layout, and the protocol
-    ``graph.GraphedTrainStep`` captures); ``fused=False`` returns the ``torch.optim`` classes for Adam and SGD instead.
+    ``graph.GraphedTrainStep`` captures); ``fused=False`` returns the ``torch.optim`` classes for Adam, AdamW and SGD instead.
 
     Every parameter is listed, in ``model.parameters()`` order, whether or not it is trainable — the reference's RMSprop
     groups hold [93, 222] tensors including the dead YOLO heads and ``feature_map`` — so that the ``optimizer`` entry
@@ -53,6 +57,9 @@ def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: b
     if name == "adam":
         return optim.Adam(list(core.parameters()), lr=lr, weight_decay=0.0005, **clip) if fused else \
             torch.optim.Adam(list(core.parameters()), lr=lr, weight_decay=0.0005)
+    if name == "adamw":
+        return optim.AdamW(list(core.parameters()), lr=lr, weight_decay=0.01, **clip) if fused else \
+            torch.optim.AdamW(list(core.parameters()), lr=lr, weight_decay=0.01)
     if name == "sgd":
         return optim.SGD(list(core.parameters()), lr=lr, momentum=0.99, **clip) if fused else \
             torch.optim.SGD(list(core.parameters()), lr=lr, momentum=0.99)
@@ -109,7 +116,8 @@ def _strip_module(sd: Dict[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
 
 def save_checkpoint(state: dict, is_best: bool, filename: str, directory: str = "./saved_models") -> str:
     """Writes ``<dir>/<filename>_checkpoint.pth.tar`` (+ ``_model_best`` copy), train_DCNet.py:255-263.
-    ``state`` = {'epoch', 'state_dict', 'best_loss', 'optimizer'}."""
+    ``state`` = {'epoch', 'state_dict', 'best_loss', 'optimizer'}, and optionally ``'ema'``: a ``dcnet_amd.optim.WeightEMA``'s
+    ``state_dict()`` (its shadows and update count), which ``load_checkpoint(..., ema=ema)`` restores."""
     for t_ in state.get("state_dict", {}).values():
         if torch.is_tensor(t_) and t_.is_cuda:
             ops.check_bilstm(t_.device)         # (host-synchronising anyway: nothing is written after a timed-out BiLSTM hand-off)
@@ -122,14 +130,20 @@ def save_checkpoint(state: dict, is_best: bool, filename: str, directory: str = 
     return ckpt
 
 
-def load_checkpoint(model, path: str, optimizer=None, map_location="cpu") -> Tuple[int, float]:
+def load_checkpoint(model, path: str, optimizer=None, map_location="cpu", ema=None) -> Tuple[int, float]:
     """``--resume`` (train_DCNet.py:500-514): strict load of model (+ optimizer).  Accepts checkpoints saved
-    from a DDP/DataParallel wrapper (``module.`` prefix) into a bare model and vice versa."""
+    from a DDP/DataParallel wrapper (``module.`` prefix) into a bare model and vice versa.  ``ema``: a ``dcnet_amd.optim.WeightEMA``
+    that takes the checkpoint's ``"ema"`` entry (in place: its shadows and step word keep their addresses); ``KeyError`` if the
+    checkpoint has none.  Without ``ema`` the entry is ignored, and a checkpoint without one loads as it always did."""
     ck = torch.load(path, map_location=map_location, weights_only=False)
     core = model.module if hasattr(model, "module") else model
     core.load_state_dict(_strip_module(ck["state_dict"]), strict=True)
     if optimizer is not None and "optimizer" in ck:
         optimizer.load_state_dict(ck["optimizer"])
+    if ema is not None:
+        if "ema" not in ck:
+            raise KeyError(f"load_checkpoint: {path} has no 'ema' entry to restore the WeightEMA from")
+        ema.load_state_dict(ck["ema"])
     return int(ck.get("epoch", 0)), float(ck.get("best_loss", float("inf")))
 
 
@@ -153,10 +167,13 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--frames", type=int, default=2)
     ap.add_argument("--size", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-4)
-    ap.add_argument("--optimizer", choices=["rmsprop", "adam", "sgd"], default="rmsprop", help="train_DCNet.py's --optimizer")
+    ap.add_argument("--optimizer", choices=["rmsprop", "adam", "sgd", "adamw"], default="rmsprop", help="train_DCNet.py's --optimizer, and adamw")
     ap.add_argument("--raw-frames", action="store_true", help="feed uint8 frames through dcnet_amd.prep every step")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X", help="clip the global gradient norm to X inside the fused step")
     ap.add_argument("--skip-nonfinite", action="store_true", help="a step whose gradient norm is inf or NaN updates nothing")
+    ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
+                    help="keep an exponential moving average of the weights inside the fused step (dcnet_amd.optim.WeightEMA) and evaluate it too")
+    ap.add_argument("--ema-tau", type=float, default=None, metavar="T", help="warm-up constant of the average: decay * (1 - exp(-t / T)); 0: none (default 2000)")
     ap.add_argument("--freeze-bn", choices=["none", "backbone", "all"], default="none",
                     help="hold BatchNorm at its running statistics while training (grounding_model.freeze_batchnorm): the backbone's, or every one")
     ap.add_argument("--freeze-bn-stats-only", action="store_true",
@@ -169,6 +186,13 @@ def freeze_bn_args(args) -> Optional[dict]:
     if args.freeze_bn == "none":
         return None
     return dict(scope=args.freeze_bn, train_affine=bool(args.freeze_bn_stats_only))
+
+
+def ema_args(args) -> Optional[dict]:
+    """The WeightEMA arguments that --ema-decay / --ema-tau ask for (None: no average; either flag alone takes the other's default)."""
+    if args.ema_decay is None and args.ema_tau is None:
+        return None
+    return dict(decay=0.9999 if args.ema_decay is None else args.ema_decay, tau=2000.0 if args.ema_tau is None else args.ema_tau)
 
 
 def main(argv: Optional[Iterable[str]] = None) -> None:
@@ -184,6 +208,11 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     if fz is not None:
         model.freeze_batchnorm(**fz)
     opt = make_optimizer(model, args.lr, args.optimizer, max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+    ema = None
+    if ema_args(args) is not None:
+        from .optim import WeightEMA
+        ema = WeightEMA(model, **ema_args(args))
+        opt.attach_ema(ema)
     n = args.clips * args.frames
     image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, args.size, seed=1))
     bbox = synth_boxes(n, args.size, seed=1).to(dev)
@@ -209,6 +238,10 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     if opt.grad_norm is not None:
         line += f"  last gradient norm {float(opt.grad_norm):.4g}  skipped steps {opt.skipped_steps()}"
     print(line)
+    if ema is not None:
+        with ema.applied():
+            acc, miou, _ = evaluate(model, image, word_id, word_mask, bbox, args.size)
+        print(f"Acc@0.5 {float(acc):.3f}  mIoU {float(miou):.3f} (averaged weights: decay {ema.decay:g}, tau {ema.tau:g}, {ema.updates()} updates)")
 
 
 if __name__ == "__main__":

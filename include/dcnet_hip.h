@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 315
+#define DCN_ABI_VERSION 316
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -757,6 +757,32 @@ int dcn_adam_step_clipped(float* const* params, const float* const* grads, float
                           float weight_decay, const void* ctrl, void* stream);
 int dcn_sgd_step_clipped(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
                          float lr, const float* lr_dev, float momentum, float weight_decay, const void* ctrl, void* stream);
+/* AdamW, and a moving average of the weights inside the step (ABI 316; dcnet_amd/optim.py: AdamW, Adam(decoupled_weight_decay=True),
+ * WeightEMA).
+ * dcn_adamw_prepare / dcn_adamw_step: torch.optim.AdamW's single-tensor step, p *= 1 - lr*weight_decay first, then Adam's update on the
+ * unmodified gradient.  As dcn_adam_prepare / dcn_adam_step, but the scalar slot of a tensor has THREE floats: prepare also writes
+ * scal[2] = (float)(1 - (double)lr * weight_decay), lr read from lr_dev when that is non-NULL; the update takes no weight_decay.  The
+ * `_clipped` forms take the control block as the other clipped entry points do (nothing written when apply is 0).
+ * dcn_ema_prepare: one thread.  Unless ctrl is non-NULL and its apply word is 0 (then both words are left alone): t = ++step[0] and
+ * w[0] = (float)(1 - d_t), d_t = decay * (1 - exp(-t / tau)) for tau > 0 and d_t = decay for tau == 0, in double.  0 <= decay < 1.
+ * dcn_ema_update: shadow[i] <- lerp(shadow[i], src[i], w[0]) in torch's fp32 form (w < 0.5: s + w*(x - s), else x - (x - s)*(1 - w)),
+ * 8 B read + 4 B written per value; a value whose source equals it keeps its bits.  Returns at once (on the device) when ctrl is
+ * non-NULL and apply is 0.  dcn_tensor_swap: exchanges the contents of a[i] and b[i], 8 B read + 8 B written per value.
+ * Both take host arrays of device pointers and element counts, 32 tensors per launch; count = 0 and tensors of 0 values (whose
+ * pointers may be NULL) are accepted.  A 4-byte-aligned view gives the bits of an aligned tensor.  Nothing synchronises. */
+int dcn_adamw_prepare(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                      double weight_decay, void* stream);
+int dcn_adamw_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                   const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, void* stream);
+int dcn_adamw_prepare_clipped(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                              double weight_decay, const void* ctrl, void* stream);
+int dcn_adamw_step_clipped(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                           const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
+                           const void* ctrl, void* stream);
+int dcn_ema_prepare(int* step, float* w, double decay, double tau, const void* ctrl, void* stream);
+int dcn_ema_update(float* const* shadow, const float* const* src, const int64_t* numel, int count, const float* w, const void* ctrl,
+                   void* stream);
+int dcn_tensor_swap(float* const* a, float* const* b, const int64_t* numel, int count, void* stream);
 /* Keys: "precision" 4 (default): the wide tiles of the conv engine and of the weight-gradient GEMM run the f16 two-piece
  *         split (see dcn_absmax) wherever both operands carry their abs-max word, and as 1 otherwise;
  *         1: the bf16 matrix pipe with every fp32 operand cut into three bf16 pieces (exact) and the six cross terms

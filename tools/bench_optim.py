@@ -1,7 +1,7 @@
 """The fused Adam / SGD steps (csrc/optim.hip) against torch's foreach steps, on the trained parameter shapes of the real model
 (synthetic weights, random gradients), alternating in one process:
 
-    python tools/bench_optim.py [--iters 20] [--warmup 3] [--step] [--clip] [--json out.json]
+    python tools/bench_optim.py [--iters 20] [--warmup 3] [--step] [--clip | --ema] [--json out.json]
 
 Per optimiser one JSON line: ms per step of ``torch.optim.{Adam,SGD}(foreach=True)`` and of ``dcnet_amd.optim.{Adam,SGD}`` (HIP events
 around ``step()`` on a warm, otherwise idle GPU; medians over --iters, the two sides measured in turns), the bytes a step has to move
@@ -17,11 +17,20 @@ update), (c) torch's foreach step, (d) ``torch.nn.utils.clip_grad_norm_(foreach=
 against d - c and against the HBM time of one read of the gradients, which is all the extra pass has to move.  With ``--step`` as
 well: the replayed RMSprop training step at configs[1]'s geometry with and without clipping, two graphs alive in one process,
 measured in alternating blocks.
+
+``--ema`` times the weight EMA instead (``dcnet_amd.optim.WeightEMA``) on the model's own tensors — every floating-point entry of its
+``state_dict()``: one update (dcn_ema_prepare + dcn_ema_update, 12 B per value), ``torch._foreach_lerp_`` on the same tensors, one
+``rmsprop_kernel`` step over tensors of the same shapes (20 B per value) and one ``swap()`` (16 B per value), measured in turns in one
+process, in --rounds rounds of --iters; per side the median of the round medians, the achieved GB/s and fraction of the HBM peak,
+and the spread of the round medians.  The EMA pass and RMSprop are both pure streaming passes over the same tensor list, so the
+figure to read is ``ema_frac_minus_rmsprop_frac`` against ``frac_round_spread``.  With ``--step`` as well: the replayed RMSprop
+training step at configs[1]'s geometry without and with an attached EMA, two graphs alive in one process, alternating blocks.
 """
 from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import random
 import statistics
@@ -161,6 +170,96 @@ def bench_train_step_clip(dev, size, clips, iters, warmup, max_norm=1.0, rounds=
             "blocks_ms": {k: [round(x, 3) for x in v] for k, v in blocks.items()}}
 
 
+def bench_ema(dev, size, iters, warmup, rounds=3):
+    """(a) WeightEMA.update, (b) torch._foreach_lerp_ on the same tensors, (c) the fused RMSprop step over tensors of the same shapes,
+    (d) WeightEMA.swap — HIP events around each, the four measured in turns; ``rounds`` rounds of ``iters``."""
+    model = build_model(size, dev)
+    ema = optim.WeightEMA(model, decay=0.9999, tau=2000.0)
+    src = list(ema._src)
+    g = torch.Generator(device=dev).manual_seed(0)
+    with torch.no_grad():
+        for v in src:                        # the weights have moved since the shadows were taken
+            v.add_(torch.randn(v.shape, device=dev, generator=g) * 1e-3)
+    lerp_shadow = [v.clone() for v in ema._shadow]
+    ps = [torch.nn.Parameter(v.clone()) for v in src]
+    for p in ps:
+        p.grad = torch.randn(p.shape, device=dev, generator=g) * 1e-3
+    rms = optim.RMSprop(ps, lr=1e-4, weight_decay=5e-4)
+    sides = {"ema": ema.update, "foreach_lerp": lambda: torch._foreach_lerp_(lerp_shadow, src, 1e-4), "rmsprop": rms.step, "swap": ema.swap}
+    bytes_per_value = {"ema": 12, "foreach_lerp": 12, "rmsprop": 20, "swap": 16}
+    for _ in range(warmup):
+        for k, fn in sides.items():
+            fn()
+            if k == "swap":
+                fn()
+    torch.cuda.synchronize()
+    n = sum(v.numel() for v in src)
+    meds = {k: [] for k in sides}
+    lo, hi = {k: math.inf for k in sides}, {k: 0.0 for k in sides}
+    for _ in range(rounds):
+        ts = {k: [] for k in sides}
+        for _ in range(iters):
+            for k, fn in sides.items():
+                ts[k].append(_timed(fn))
+                if k == "swap":
+                    ts[k].append(_timed(fn))         # ... and back: the next update sees the model the right way round
+        for k, v in ts.items():
+            meds[k].append(statistics.median(v)); lo[k] = min(lo[k], min(v)); hi[k] = max(hi[k], max(v))
+    assert not ema.swapped
+    ms = {k: statistics.median(v) for k, v in meds.items()}
+    frac = {k: n * bytes_per_value[k] / ms[k] / 1e9 / (HBM_PEAK / 1e12) for k in sides}
+    frac_rounds = {k: [n * bytes_per_value[k] / m / 1e9 / (HBM_PEAK / 1e12) for m in meds[k]] for k in sides}
+    spread = max(max(v) - min(v) for k, v in frac_rounds.items() if k in ("ema", "rmsprop"))
+    out = {"ema": True, "tensors": len(src), "values_M": round(n / 1e6, 2), "rounds": rounds, "iters": iters, "updates": ema.updates()}
+    for k in sides:
+        out[k + "_ms"] = round(ms[k], 4)
+        out[k + "_GBps"] = round(n * bytes_per_value[k] / ms[k] / 1e6, 1)
+        out[k + "_frac_hbm_peak"] = round(frac[k], 3)
+    out["ema_frac_minus_rmsprop_frac"] = round(frac["ema"] - frac["rmsprop"], 3)
+    out["frac_round_spread"] = round(spread, 3)
+    out["round_medians_ms"] = {k: [round(x, 4) for x in v] for k, v in meds.items()}
+    out["spread_ms"] = {k: [round(lo[k], 4), round(hi[k], 4)] for k in sides}
+    return out
+
+
+def bench_train_step_ema(dev, size, clips, iters, warmup, rounds=3):
+    """The replayed RMSprop training step without and with an attached ``WeightEMA``: two models, two graphs, alternating blocks of
+    ``iters`` steps (wall clock per step, host-synchronised at both ends of a block); per side the median over the blocks."""
+    from dcnet_amd.graph import GraphedTrainStep
+    from dcnet_amd.train import make_optimizer
+    from dcnet_amd.utils.synth import synth_boxes, synth_inputs
+    n = clips * 8
+    image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, size, seed=100))
+    bbox = synth_boxes(n, size, seed=100).to(dev)
+    steps, emas = {}, {}
+    for key in ("plain", "ema"):
+        random.seed(13)
+        model = build_model(size, dev)
+        opt = make_optimizer(model, 1e-4, "rmsprop")
+        if key == "ema":
+            emas[key] = optim.WeightEMA(model)
+            opt.attach_ema(emas[key])                # before the capture
+        steps[key] = GraphedTrainStep(model, opt, image, word_id, word_mask, bbox, size, warmup=max(1, warmup))
+        for _ in range(warmup):
+            steps[key]()
+    torch.cuda.synchronize()
+    blocks = {k: [] for k in steps}
+    for _ in range(rounds):
+        for key, step in steps.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                step()
+            torch.cuda.synchronize()
+            blocks[key].append((time.perf_counter() - t0) / iters * 1e3)
+    med = {k: statistics.median(v) for k, v in blocks.items()}
+    return {"geometry": f"{clips} clips x T 8 at {size}x{size}", "steps_per_block": iters, "blocks": rounds, "ema_updates": emas["ema"].updates(),
+            "replayed_rmsprop_ms": round(med["plain"], 3), "replayed_rmsprop_ema_ms": round(med["ema"], 3),
+            "ema_minus_plain_ms": round(med["ema"] - med["plain"], 3),
+            "block_spread_ms": round(max(max(v) - min(v) for v in blocks.values()), 3),
+            "blocks_ms": {k: [round(x, 3) for x in v] for k, v in blocks.items()}}
+
+
 def bench_train_step(dev, size, clips, iters, warmup):
     from dcnet_amd.graph import GraphedTrainStep
     from dcnet_amd.train import make_optimizer, train_step
@@ -206,9 +305,24 @@ def main(argv=None):
     ap.add_argument("--clips", type=int, default=8)
     ap.add_argument("--step-iters", type=int, default=10)
     ap.add_argument("--clip", action="store_true", help="time gradient clipping: fused / fused + clip / torch foreach / torch clip + foreach")
+    ap.add_argument("--ema", action="store_true", help="time the weight EMA: update / torch._foreach_lerp_ / rmsprop_kernel / swap on the model's tensors")
+    ap.add_argument("--rounds", type=int, default=3, help="--ema: rounds of --iters (the spread of their medians is reported)")
     ap.add_argument("--json", default="")
     a = ap.parse_args(argv)
+    if a.ema and a.clip:
+        ap.error("--ema and --clip are separate measurements")
     dev = torch.device("cuda:0")
+    if a.ema:
+        rows = [bench_ema(dev, a.size, a.iters, a.warmup, a.rounds)]
+        print(json.dumps(rows[-1]), flush=True)
+        torch.cuda.empty_cache()
+        if a.step:
+            rows.append(bench_train_step_ema(dev, a.size, a.clips, a.step_iters, a.warmup, a.rounds))
+            print(json.dumps(rows[-1]), flush=True)
+        if a.json:
+            with open(a.json, "w") as fh:
+                json.dump(rows, fh, indent=1)
+        return
     model = build_model(a.size, dev)
     shapes = [tuple(p.shape) for p in model.parameters() if p.requires_grad]
     del model
