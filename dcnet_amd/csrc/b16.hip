@@ -9,37 +9,13 @@
 #include "common.h"
 #include "prof.h"
 #include "frozen_bn.h"
+#include "b16_pack.h"
 
 int bn_pc_enabled();         // bn.hip: dcn_set_tuning("Bpc", 0) turns the per-thread-channel apply passes off
 
 namespace {
 
-typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
-struct F8 { float v[8]; };
-
-template <typename T> __device__ __forceinline__ F8 ld8(const T* p);
-template <> __device__ __forceinline__ F8 ld8<float>(const float* p) {
-  const f32x4 a = *reinterpret_cast<const f32x4*>(p), b = *reinterpret_cast<const f32x4*>(p + 4);
-  return F8{{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]}};
-}
-template <> __device__ __forceinline__ F8 ld8<__bf16>(const __bf16* p) {
-  const bf16x8_t a = *reinterpret_cast<const bf16x8_t*>(p);
-  F8 r;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) r.v[k] = (float)a[k];
-  return r;
-}
-template <typename T> __device__ __forceinline__ void st8(T* p, const F8& x);
-template <> __device__ __forceinline__ void st8<float>(float* p, const F8& x) {
-  *reinterpret_cast<f32x4*>(p) = f32x4{x.v[0], x.v[1], x.v[2], x.v[3]};
-  *reinterpret_cast<f32x4*>(p + 4) = f32x4{x.v[4], x.v[5], x.v[6], x.v[7]};
-}
-template <> __device__ __forceinline__ void st8<__bf16>(__bf16* p, const F8& x) {
-  bf16x8_t a;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) a[k] = (__bf16)x.v[k];               // round to nearest even
-  *reinterpret_cast<bf16x8_t*>(p) = a;
-}
+using namespace b16io;      // b16_pack.h: bf16x8_t, F8, ld8 / st8 (the mode's one fp32 -> bf16 conversion; video.hip's bank passes share it)
 
 inline int grid_for(int64_t items) {
   int64_t b = (items + 255) / 256;

@@ -186,12 +186,16 @@ SIGNATURES = {
     "dcn_bank_write": (I, [P, I, P, P, L, I, P]),
     "dcn_coattn_bank_fwd": (I, [P, P, P, P, L, P, P, I, L, P, P, P, P, I, I, I, F, P]),
     "dcn_post_fusion_bank": (I, [P, P, I, I, I, I, P, P, P]),
+    "dcn_bank_write_b16": (I, [P, I, P, P, P, L, I, P]),
+    "dcn_bank_concat_b16": (I, [P, L, P, I, L, P, I, I, I, P]),
+    "dcn_coattn_bank_form": (I, [I, I]),
 }
 _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap_rows", "dcn_conv2d_pre_supported",
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",
                 "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes",
-                "dcn_conv1_tile", "dcn_l2norm_score_fwd_form", "dcn_bn_apply_form", "dcn_igemm_split_build", "dcn_gemm3_variant"}
-ABI_VERSION = 316        # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
+                "dcn_conv1_tile", "dcn_l2norm_score_fwd_form", "dcn_bn_apply_form", "dcn_igemm_split_build", "dcn_gemm3_variant",
+                "dcn_coattn_bank_form"}
+ABI_VERSION = 317       # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
 
 
 class DcnError(RuntimeError):

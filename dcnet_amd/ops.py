@@ -1657,10 +1657,69 @@ def bank_write(x, bank, split):
 COATTN_BANK_WS_BYTES = 2 << 30       # budget of the affinity workspace E of one coattn_bank_fwd launch sequence (it sub-batches)
 
 
+def bank_write_b16(x, rows16, bank=None, split=None):
+    """bank_write on bf16 storage: x (..., c) fp32 rows -> rows16 (bf16, dense [rows][c]) = the normalised rows rounded once, and — each
+    only if given — bank / split, bitwise bank_write's.  One pass.  A scale keeps the one of bank / split that coattn_bank_form names."""
+    c = x.shape[-1]
+    rows = x.numel() // c
+    _rows(x, "bank_write_b16 x"); _chk16(rows16, "bank_write_b16 rows16")
+    for t, nm in ((bank, "bank"), (split, "split")):
+        if t is not None:
+            _chk(t, "bank_write_b16 " + nm)
+    if any(t is not None and (t.shape[-1] != c or t.numel() != rows * c) for t in (rows16, bank, split)):
+        raise ValueError(f"bank_write_b16: rows16 / bank / split must hold the {rows} rows of x "
+                         f"({[None if t is None else tuple(t.shape) for t in (rows16, bank, split)]})")
+    lib().bank_write_b16(x.data_ptr(), x.stride(-2), rows16.data_ptr(), _p(bank), _p(split), rows, c, _s())
+    return rows16, bank, split
+
+
+def bank_concat_b16(rows16, a0, attn, cat=None):
+    """rows16 (F, hw, c) bf16 contiguous (bank_write_b16), attn (n, hw, c) fp32 view with a contiguous last dimension (what
+    coattn_bank_fwd wrote) -> cat (n, hw, 2c) bf16 contiguous = [rows16[a0:a0 + n] | bf16(attn)]: corr_conv's input on bf16 storage,
+    one pass."""
+    _chk16(rows16, "bank_concat_b16 rows16")
+    if rows16.dim() != 3:
+        raise ValueError(f"bank_concat_b16: rows16 must be (F, hw, c), got {tuple(rows16.shape)}")
+    F_, hw, c = rows16.shape
+    if not (attn.is_cuda and attn.dtype == torch.float32 and attn.dim() == 3 and tuple(attn.shape[1:]) == (hw, c) and attn.stride(2) == 1):
+        raise ValueError(f"bank_concat_b16: attn must be an fp32 CUDA (n, {hw}, {c}) view with a contiguous last dimension, got "
+                         f"{attn.dtype} shape {tuple(attn.shape)} strides {attn.stride()}")
+    n = attn.shape[0]
+    if n <= 0 or a0 < 0 or a0 + n > F_:
+        raise ValueError(f"bank_concat_b16: centres {a0} .. {a0 + n - 1} outside a bank of {F_} frames")
+    if cat is None:
+        cat = torch.empty((n, hw, 2 * c), dtype=torch.bfloat16, device=rows16.device)
+    _chk16(cat, "bank_concat_b16 cat")
+    if tuple(cat.shape) != (n, hw, 2 * c):
+        raise ValueError(f"bank_concat_b16: cat must be ({n}, {hw}, {2 * c}), got {tuple(cat.shape)}")
+    lib().bank_concat_b16(rows16.data_ptr() + 2 * a0 * hw * c, hw * c, attn.data_ptr(), attn.stride(1), attn.stride(0), cat.data_ptr(),
+                          n, hw, c, _s())
+    return cat
+
+
+def coattn_bank_form(hw, c) -> int:
+    """1: coattn_bank_fwd runs the products of an (hw, c) problem on gemm3.hip and reads the split bank; 0: it goes through coattn_fwd on
+    the fp32 rows.  The launcher's own answer under the current precision mode (dcn_coattn_bank_form)."""
+    return int(lib().coattn_bank_form(int(hw), int(c)))
+
+
 def coattn_bank_fwd(bank, split, a0, d, n, out1, out2, temperature):
     """bank / split (F, hw, c) contiguous fp32 (bank_write).  The n pairs (a, a + d), a = a0 ... a0 + n - 1: out1[i] (n, hw, c view,
     last dim contiguous) = what frame a takes from frame a + d, out2[i] = what frame a + d takes from frame a; either may be None.
-    One affinity per pair; sub-batched so that E stays within COATTN_BANK_WS_BYTES (at least one pair per launch)."""
+    One affinity per pair; sub-batched so that E stays within COATTN_BANK_WS_BYTES (at least one pair per launch).
+    bank or split may be None when the form that runs (coattn_bank_form) does not read it; ValueError if it does."""
+    if bank is None or split is None:
+        live = bank if bank is not None else split
+        if live is None:
+            raise ValueError("coattn_bank_fwd: neither bank nor split given")
+        _chk(live, "coattn_bank " + ("bank" if bank is not None else "split"))
+        if live.dim() == 3:
+            form = coattn_bank_form(live.shape[1], live.shape[2])
+            if (split if form else bank) is None:
+                raise ValueError(f"coattn_bank_fwd: the products of (hw = {live.shape[1]}, c = {live.shape[2]}) "
+                                 + ("run on gemm3.hip and read the split bank: split is None" if form else
+                                    "go through coattn_fwd on the fp32 rows: bank is None"))
+        bank = split = live           # (the unused pointer pair gets the live tensor: the launcher wants four pointers)
     _chk(bank, "coattn_bank bank"); _chk(split, "coattn_bank split")
     F_, hw, c = bank.shape
     if tuple(split.shape) != (F_, hw, c) or n <= 0 or a0 < 0 or d < 0 or a0 + d + n > F_:

@@ -21,7 +21,14 @@ The window rule is the reference's (``getChunk``):
     # or incrementally, for streams and long videos:
     vg.reset(word_id); out = vg.push(image_chunk); ...; out = vg.flush()
 
-``python -m dcnet_amd.video --synthetic --frames 64 --n-frame 5`` runs it on synthetic frames and prints frames/s.
+Precision modes (``ops.set_precision``; latched at ``reset``): "fp32" as above, and "bf16s" (bf16 storage), where the bank of a scale
+holds the rows in bf16 (the centre half of ``corr_conv``'s bf16 input) plus ONE fp32-sized operand of the co-attention — the split
+form where its products run on gemm3.hip, the fp32 rows where they do not (``dcn_bank_write_b16``, ``dcn_coattn_bank_form``): 6 bytes
+per value instead of 8.  The attended features land in a dense fp32 scratch and ``dcn_bank_concat_b16`` writes the bf16 concat that
+``corr_conv`` reads as it is.  The rounding points are those of the windowed model on bf16 storage: ``mapping_visu`` hands out fp32,
+normalised in fp32; the co-attention reads the f16 high piece of 8192 f; the concat is rounded to bf16 once.
+
+``python -m dcnet_amd.video --synthetic --frames 64 --n-frame 5 [--precision bf16s]`` runs it on synthetic frames and prints frames/s.
 """
 from __future__ import annotations
 
@@ -33,6 +40,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 BORDERS = ("valid", "replicate")
+BANK_BYTES_PER_VALUE = {"fp32": 4 + 4, "bf16s": 2 + 4}      # precision modes that have the path: fp32 rows + split | bf16 rows + one of the two
 
 
 # ---- host logic (pure Python) -------------------------------------------------------------------------------------------------
@@ -217,15 +225,16 @@ class VideoGrounder:
     """Grounds every frame of a video against one or more sentences (module docstring).
 
     model    a ``dcnet_amd.model.grounding_model`` (``model.DCNet_model`` and ``model.test_DCNet_model`` hand out the same class)
-             in eval mode.  Precision: the default "fp32" mode only — the feature bank holds fp32 rows and their f16 two-piece
-             split; any other mode of ``ops.set_precision`` raises a RuntimeError that names it.
+             in eval mode.  Precision: "fp32" (the feature bank holds fp32 rows and their f16 two-piece split) or "bf16s" (bf16
+             rows and one of the two, module docstring), whichever is set at ``reset``; any other mode of ``ops.set_precision``
+             raises a RuntimeError that names it, and so does a ``push`` / ``flush`` under another mode than its ``reset``.
     n_frame  K, frames per window (>= 2); border "valid" | "replicate" (``centres``)
     chunk    frames encoded per step: bounds the memory of the bank rows, concat buffers and the affinity workspace (the
              co-attention sub-batches by ``ops.COATTN_BANK_WS_BYTES`` on its own)
     topk     k: also the k best candidates of every centre and their temporal fusion over windows of n_frame centres
              (n_frame <= 32, k <= 64)
 
-    ``push`` keeps the bank rows of the last n_frame // 2 frames (no pair reaches further back; per scale, fp32 and split) and the
+    ``push`` keeps the bank rows of the last n_frame // 2 frames (no pair reaches further back; per scale, both tensors of the mode) and the
     unfinished means of the last ceil(n_frame / 2) - 1 centres between calls, so chunked and streamed runs encode every frame once
     too.  Nothing here synchronises the host with the device."""
 
@@ -253,9 +262,10 @@ class VideoGrounder:
             raise ValueError("model is in train mode: VideoGrounder is the inference path, call model.eval() first")
         if not (isinstance(word_id, torch.Tensor) and word_id.is_cuda):
             raise ValueError("word_id: expected a CUDA tensor of token ids (Q,L) or (L,) (HIP kernels only, no CPU path)")
-        if ops.get_precision() != "fp32":
-            raise RuntimeError(f"VideoGrounder runs in the \"fp32\" precision mode only (feature banks are fp32 + f16 split); the "
-                               f"current mode is {ops.get_precision()!r}")
+        if ops.get_precision() not in BANK_BYTES_PER_VALUE:
+            raise RuntimeError(f"VideoGrounder runs in the \"fp32\" and \"bf16s\" precision modes (the two that have the feature-bank "
+                               f"path); the current mode is {ops.get_precision()!r}")
+        self._mode = ops.get_precision()                          # latched: the banks of a video are in ONE mode's layout
         if word_id.dim() == 1:
             word_id = word_id.unsqueeze(0)
         dev = word_id.device
@@ -271,7 +281,8 @@ class VideoGrounder:
         self._lang = {"side": side, "joined": side is main, "flang": flang, "attn": flang_attn, "loc": flang_loc, "Q": word_id.shape[0]}
         K = self.n_frame
         self._total, self._seen = total, 0
-        self._bank = None                                         # per scale (bank, split) of frames [_seen - keep, _seen)
+        self._bank = None                                         # per scale (bank, split) of frames [_seen - keep, _seen); "bf16s":
+        self._form = None                                         # (rows16, split if _form[s] else bank), _form[s] = coattn_bank_form
         self._acc = None                                          # per scale: unfinished means of centres [_acc_lo, ...)
         self._acc_lo = K // 2 if self.border == "valid" else 0    # first centre not handed out yet
         self._meta = []                                           # device (ratio, dw, dh, frame_hw) of frames [_meta_lo, ...)
@@ -286,6 +297,26 @@ class VideoGrounder:
                 t_.record_stream(main)
             st["joined"] = True
 
+    def _check_mode(self, where: str) -> None:
+        from . import ops
+        if ops.get_precision() != self._mode:
+            raise RuntimeError(f"VideoGrounder.{where}: the precision mode is {ops.get_precision()!r} but this video was reset under "
+                               f"{self._mode!r}; its banks are in that mode's layout (reset again, or set the mode back)")
+
+    def bank_bytes_per_frame(self, size: Optional[int] = None) -> int:
+        """Bytes of feature bank the grounder keeps per frame, all three scales: (size/32 * 2^s)^2 pixels of emb_size values, 8 bytes
+        per value in "fp32" (fp32 rows + split), 6 in "bf16s" (bf16 rows + split OR fp32 rows).  The mode is the latched one while a
+        video is open, else the current one; ``size`` defaults to the frame size of the last ``push``."""
+        from . import ops
+        mode = self._mode if self._lang is not None else ops.get_precision()
+        if mode not in BANK_BYTES_PER_VALUE:
+            raise RuntimeError(f"bank_bytes_per_frame: no feature-bank path in the precision mode {mode!r} (\"fp32\" and \"bf16s\" have it)")
+        if size is None:
+            size = getattr(self, "_size", None)
+            if size is None:
+                raise ValueError("bank_bytes_per_frame: size not given and no frame pushed yet")
+        return sum((size // 32 * 2 ** s) ** 2 for s in range(3)) * self.model.emb_size * BANK_BYTES_PER_VALUE[mode]
+
     # ---- one step -------------------------------------------------------------------------------------------------------------
     def _contribute(self, s, bank, split, base, acc, h, w, plan: PairPlan):
         from . import ops
@@ -293,7 +324,23 @@ class VideoGrounder:
         hw, e = bank.shape[1], bank.shape[2]
         lo = self._acc_lo
 
+        def one_b16(a, d, n, fwd, bwd, w_f, w_b):
+            # bank = the bf16 rows, split = the one operand form the co-attention of this scale reads (_form[s])
+            attn = torch.empty(((int(fwd) + int(bwd)) * n, hw, e), dtype=torch.float32, device=bank.device)
+            af = attn[:n] if fwd else None
+            ab = attn[n if fwd else 0:] if bwd else None
+            on3 = self._form[s]
+            ops.coattn_bank_fwd(None if on3 else split, split if on3 else None, a - base, d, n, af, ab, m.temperature)
+            if fwd:
+                cat = ops.bank_concat_b16(bank, a - base, af)
+                m._corr_accumulate(s, cat.view(n, h, w, 2 * e), acc[a - lo:a - lo + n].view(n, h, w, e), w_f / (K - 1))
+            if bwd:
+                cat = ops.bank_concat_b16(bank, a + d - base, ab)
+                m._corr_accumulate(s, cat.view(n, h, w, 2 * e), acc[a + d - lo:a + d - lo + n].view(n, h, w, e), w_b / (K - 1))
+
         def one(a, d, n, fwd, bwd, w_f, w_b):
+            if self._mode == "bf16s":
+                return one_b16(a, d, n, fwd, bwd, w_f, w_b)
             cat = torch.empty(((int(fwd) + int(bwd)) * n, hw, 2 * e), dtype=torch.float32, device=bank.device)
             cf = cat[:n] if fwd else None
             cb = cat[n if fwd else 0:] if bwd else None
@@ -378,6 +425,7 @@ class VideoGrounder:
             raise RuntimeError("VideoGrounder.push: call reset(word_id) first")
         if not (isinstance(image, torch.Tensor) and image.is_cuda and image.dim() == 4 and image.shape[0] >= 1):
             raise ValueError("image: expected a CUDA tensor (n,3,S,S) (HIP kernels only, no CPU path)")
+        self._check_mode("push")
         if image.shape[0] > self.chunk:
             parts = []
             for i0 in range(0, image.shape[0], self.chunk):
@@ -402,14 +450,27 @@ class VideoGrounder:
         plan = pair_plan(p0, p1, K, self.border, self._total)
         n_acc = max(0, p1 - self._acc_lo)
         banks, accs = [], []
+        b16 = self._mode == "bf16s"
+        if b16 and self._form is None:
+            self._form = [None] * 3
         for s in range(3):
-            x = m._map_scale(s, raw[s])
+            x = m._map_scale(s, raw[s])                           # (fp32 in either mode: the bank normalises in fp32)
             _, h, w, e = x.shape
-            bank = torch.empty((keep + n_new, h * w, e), dtype=torch.float32, device=dev)
-            split = torch.empty_like(bank)
+            bank = torch.empty((keep + n_new, h * w, e), dtype=torch.bfloat16 if b16 else torch.float32, device=dev)
+            split = torch.empty((keep + n_new, h * w, e), dtype=torch.float32, device=dev)
             if keep:
                 bank[:keep].copy_(self._bank[s][0]); split[:keep].copy_(self._bank[s][1])
-            ops.bank_write(x, bank[keep:], split[keep:])
+            if b16:
+                if m.corr_conv[s][0].__dict__.get("_dcn_bank") is None:
+                    raise RuntimeError("VideoGrounder, \"bf16s\": corr_conv reads the bf16 concat through its prepared filter bank "
+                                       "(ops.FILTER_BANKS is off)")
+                form = ops.coattn_bank_form(h * w, e)
+                if self._form[s] is not None and self._form[s] != form:
+                    raise RuntimeError(f"VideoGrounder.push: the co-attention form of scale {s} changed within a video (a tuning knob?)")
+                self._form[s] = form
+                ops.bank_write_b16(x, bank[keep:], bank=None if form else split[keep:], split=split[keep:] if form else None)
+            else:
+                ops.bank_write(x, bank[keep:], split[keep:])
             acc = torch.zeros((n_acc, h * w, e), dtype=torch.float32, device=dev)
             if self._acc is not None and self._acc[s].shape[0]:
                 acc[:self._acc[s].shape[0]].copy_(self._acc[s])
@@ -428,6 +489,7 @@ class VideoGrounder:
         dropped.  Returns their results, or None; the grounder needs a ``reset`` before the next video."""
         if self._lang is None:
             raise RuntimeError("VideoGrounder.flush: call reset(word_id) first")
+        self._check_mode("flush")
         out = None
         if self.border == "replicate" and self._seen > self._acc_lo:
             if self._total is None:
@@ -494,8 +556,6 @@ def synthetic_model(size: int, device):
 
 def main(argv=None):
     import argparse
-    import time
-    import numpy as np
     ap = argparse.ArgumentParser(description="whole-video grounding on synthetic frames")
     ap.add_argument("--synthetic", action="store_true", help="synthetic weights and frames (the only source this tool has)")
     ap.add_argument("--frames", type=int, default=64)
@@ -507,9 +567,21 @@ def main(argv=None):
     ap.add_argument("--topk", type=int, default=None)
     ap.add_argument("--raw-frames", action="store_true", help="375x500 uint8 frames through prep.prepare_clips(augment=False); prints source-pixel boxes")
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--precision", default="fp32", choices=sorted(BANK_BYTES_PER_VALUE), help="ops.set_precision mode of the run")
     a = ap.parse_args(argv)
     if not a.synthetic:
         ap.error("only --synthetic input is built in; use VideoGrounder from Python for real videos")
+    from . import ops
+    ops.set_precision(a.precision)                   # (before the model is built; "fp32" again at the end)
+    try:
+        _main_run(a)
+    finally:
+        ops.set_precision("fp32")
+
+
+def _main_run(a):
+    import time
+    import numpy as np
     from .utils.synth import synth_inputs
     dev = torch.device("cuda:0")
     m = synthetic_model(a.size, dev)
@@ -531,9 +603,9 @@ def main(argv=None):
         torch.cuda.synchronize()
         times.append(time.perf_counter() - t0)
     t = float(np.median(times[1:])) if len(times) > 1 else times[0]
-    print(f"{a.frames} frames {a.size}x{a.size}, n_frame {a.n_frame}, border {a.border}, {a.queries} quer{'y' if a.queries == 1 else 'ies'}: "
-          f"{res.centres.numel()} centres in {t * 1e3:.1f} ms = {a.frames / t:.1f} frames/s, peak memory "
-          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB")
+    print(f"{a.frames} frames {a.size}x{a.size}, n_frame {a.n_frame}, border {a.border}, {a.queries} quer{'y' if a.queries == 1 else 'ies'}, "
+          f"{a.precision}: {res.centres.numel()} centres in {t * 1e3:.1f} ms = {a.frames / t:.1f} frames/s, peak memory "
+          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB, bank {vg.bank_bytes_per_frame(a.size) / 2 ** 20:.2f} MiB per frame")
     if a.raw_frames:
         b = (res.fused_boxes if a.topk is not None else res.boxes)[0].cpu()
         for i, c in enumerate(res.centres.cpu().tolist()):

@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 316
+#define DCN_ABI_VERSION 317
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -605,6 +605,20 @@ int dcn_coattn_bank_fwd(const float* f1, const float* f2, const float* f1s, cons
  * gathered tensors.  k <= 64, r <= 32. */
 int dcn_post_fusion_bank(const float* feats, const float* scores, int n, int k, int r, int e, float* fused, int64_t* best,
                          void* stream);
+/* ---- the feature bank on bf16 storage (ABI 317) ----
+ * dcn_bank_write_b16: dcn_bank_write's pass with a third output, rows16 [rows][c] bf16 (dense, required) = the normalised row rounded
+ * to nearest even from the very fp32 value dcn_bank_write stores (the conversion of dcn_cast_rows).  bank and split keep their
+ * meaning and their bits; either may be NULL (at most one of them is needed: split where dcn_coattn_bank_form says 1, bank where 0).
+ * Same limits: c a multiple of 8, <= 1024; 16-byte aligned tensors; ldx <= 0: c. */
+int dcn_bank_write_b16(const float* x, int ldx, void* rows16, float* bank, float* split, int64_t rows, int c, void* stream);
+/* The input of corr_conv on bf16 storage in one pass: cat [n][hw][2c] bf16, dense;  cat[i][p][0:c] = rows16[i][p][:] (the centres'
+ * bf16 bank rows, frame stride bs16 elements, <= 0: hw*c), cat[i][p][c:2c] = bf16(attn[i][p][:]) with attn fp32, pixel stride ld_attn
+ * (<= 0: c) and batch stride bs_attn (<= 0: hw*ld_attn) as dcn_coattn_bank_fwd writes it.  c a multiple of 8; 16-byte aligned. */
+int dcn_bank_concat_b16(const void* rows16, int64_t bs16, const float* attn, int ld_attn, int64_t bs_attn, void* cat, int n, int hw,
+                        int c, void* stream);
+/* Read-only dispatch query: 1 = dcn_coattn_bank_fwd runs the products of an (hw, c) problem on gemm3.hip and reads the SPLIT bank,
+ * 0 = it goes through dcn_coattn_fwd on the fp32 rows — under the current precision mode and knobs. */
+int dcn_coattn_bank_form(int hw, int c);
 
 /* ---- clip preprocessing: letterbox, flip, HSV and affine warp of decoded frames (ABI 309) ---------------------------- */
 /* One record per frame of the batch (host-built by dcnet_amd/prep.py; dataset/vid_loader.py:333-395 draws the parameters,

@@ -3,6 +3,7 @@
     python tools/bench_video.py                    # F = 64 frames, 416x416, n_frame = 5, one query, fp32, forward only
     python tools/bench_video.py --baseline-only    # arm (b) alone: runs on a tree without dcnet_amd.video as well
     python tools/bench_video.py --frames 32 --size 608 --n-frame 16 --windows 4      # BASELINE configs[3]'s geometry
+    python tools/bench_video.py --precision bf16s  # both arms on bf16 storage, plus arm (c): VideoGrounder in fp32 on its own model
 
 Arm (a): ``VideoGrounder.run`` on the whole video.  Arm (b): the same "valid" centres as explicit windows through
 ``model(windows, word_id, None, n_frame)`` in batches of ``--windows`` windows — every frame is encoded once per window it appears
@@ -48,7 +49,19 @@ def main():
     ap.add_argument("--repeat", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--baseline-only", action="store_true")
+    ap.add_argument("--precision", default="fp32", choices=("fp32", "bf16s"),
+                    help="ops.set_precision mode of both arms; bf16s adds a third arm, VideoGrounder in fp32 on a model of its own")
     a = ap.parse_args()
+    from dcnet_amd import ops
+    ops.set_precision(a.precision)                   # (before the model is built)
+    try:
+        run(a)
+    finally:
+        ops.set_precision("fp32")
+
+
+def run(a):
+    from dcnet_amd import ops
     from dcnet_amd.utils.synth import synth_inputs
     dev = torch.device("cuda:0")
     m = build_model(a.size, dev)
@@ -72,6 +85,22 @@ def main():
         from dcnet_amd.video import VideoGrounder
         vg = VideoGrounder(m, n_frame=K, border="valid", chunk=a.chunk)
         arms["video"] = lambda: vg.run(image, word_id)
+        bank = {"video": vg.bank_bytes_per_frame(a.size)}
+        if a.precision != "fp32":
+            ops.set_precision("fp32")
+            try:
+                vg32 = VideoGrounder(build_model(a.size, dev), n_frame=K, border="valid", chunk=a.chunk)
+                bank["video_fp32"] = vg32.bank_bytes_per_frame(a.size)
+            finally:
+                ops.set_precision(a.precision)
+
+            def video_fp32():
+                ops.set_precision("fp32")
+                try:
+                    return vg32.run(image, word_id)
+                finally:
+                    ops.set_precision(a.precision)
+            arms["video_fp32"] = video_fp32
     times = {k: [] for k in arms}
     peak = {}
     for it in range(a.warmup + a.repeat):
@@ -84,10 +113,13 @@ def main():
             if it >= a.warmup:
                 times[name].append(time.perf_counter() - t0)
             peak[name] = torch.cuda.max_memory_allocated() / 2 ** 30
-    res = {"frames": F, "size": a.size, "n_frame": K, "centres": len(cs), "windows_per_call": a.windows, "chunk": a.chunk}
+    res = {"frames": F, "size": a.size, "n_frame": K, "centres": len(cs), "windows_per_call": a.windows, "chunk": a.chunk,
+           "precision": a.precision}
     for name in arms:
         t = float(np.median(times[name]))
         res[name] = {"ms": round(t * 1e3, 2), "frames_per_s": round(F / t, 1), "peak_gib": round(peak[name], 2)}
+        if not a.baseline_only and name in bank:
+            res[name]["bank_bytes_per_frame"] = bank[name]
     if "video" in res:
         res["speedup"] = round(res["windowed"]["ms"] / res["video"]["ms"], 3)
     print(json.dumps(res))
