@@ -3,14 +3,61 @@
 //   RMSprop (momentum = 0, centered = False)      12 B read + 8 B written per parameter
 //   Adam (amsgrad = False, maximize = False)      16 B read + 12 B written
 //   SGD with momentum (dampening = 0, no Nesterov) 12 B read + 8 B written
+//
+// How the file is put together.  Tensors travel to the kernels as pointer chunks of 32 in the kernel arguments (Chunk<K>: no table
+// upload); block (x, y) works on tensor y of its chunk.  The element walk is written once: `walk` (16-byte body where every pointer
+// of the tensor is 16-byte aligned, scalar tail, grid-stride) and around it `update_walk` (tensor selection and the clipped form's
+// prologue), so an update kernel is its update function (`rms_update`, `adam_update`, `adamw_update`, `sgd_update`) in a lambda,
+// with the values of the launch and of the tensor (the device learning rate, Adam's scalars) read in front of the walk.  `walk2` is
+// the two-trips-at-once form of the two-stream passes (EMA, swap); `grad_sumsq_kernel` keeps its own four-deep loop.  On the host
+// every entry point checks all its tensors (`check_tensors`) and then goes through one launcher (`launch_chunks`, on `for_chunks`).
+// A new optimiser is an update function, a kernel pair of a few lines and an entry-point pair.
 #include "common.h"
 
 namespace {
 
 constexpr int RMS_CHUNK = 32;                 // tensors per launch (pointers travel as kernel arguments: no table upload)
-struct RmsChunk {
-  float* p[RMS_CHUNK]; const float* g[RMS_CHUNK]; float* v[RMS_CHUNK]; long long n[RMS_CHUNK];
-};
+// K pointer tables and the element counts of up to 32 tensors.  The update kernels: table 0 the parameter, 1 the gradient, 2 ... the
+// state tensors (Adam: 4 the tensor's scalars); the others say which is which where they read them.
+template <int K> struct Chunk { float* t[K][RMS_CHUNK]; long long n[RMS_CHUNK]; };
+
+// The element walk over one tensor of `n` values, blocks of 256 along x: W tensors that are read and written, w[0 .. W), and under
+// READ one that is only read, g.  f(a, ge) updates the W values a[] of one element, ge = g's value there (0 without READ).  Four
+// elements per thread and trip through 16-byte accesses where every pointer is 16-byte aligned, else (a view into a flat buffer)
+// and for the last n % 4 values one element at a time: f must round alike on both paths (contraction off in the update functions).
+template <int W, bool READ, class F>
+__device__ __forceinline__ void walk(float* const (&w)[W], const float* __restrict__ g, const long long n, F f) {
+  uintptr_t bits = READ ? (uintptr_t)g : 0;
+#pragma unroll
+  for (int k = 0; k < W; ++k) bits |= (uintptr_t)w[k];
+  const long long n4 = (bits & 15) == 0 ? n / 4 : 0;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
+    f32x4 x[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) x[k] = reinterpret_cast<const f32x4*>(w[k])[i];
+    const f32x4 gg = READ ? reinterpret_cast<const f32x4*>(g)[i] : f32x4{};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float a[W];
+#pragma unroll
+      for (int k = 0; k < W; ++k) a[k] = x[k][e];
+      f(a, gg[e]);
+#pragma unroll
+      for (int k = 0; k < W; ++k) x[k][e] = a[k];
+    }
+#pragma unroll
+    for (int k = 0; k < W; ++k) reinterpret_cast<f32x4*>(w[k])[i] = x[k];
+  }
+  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float a[W];
+#pragma unroll
+    for (int k = 0; k < W; ++k) a[k] = w[k][i];
+    f(a, READ ? g[i] : 0.f);
+#pragma unroll
+    for (int k = 0; k < W; ++k) w[k][i] = a[k];
+  }
+}
 
 // (no FMA contraction: the 16-byte path and the scalar path of a misaligned tensor — a view into a flat gradient buffer — must
 //  round alike, or a data-parallel run with bound gradients drifts away from the single-GPU run by an ulp per step)
@@ -32,39 +79,35 @@ __device__ __forceinline__ float clip_mul(const float g0, const float coef) {
   return g0 * coef;
 }
 
-template <bool CLIP>
-__device__ __forceinline__ void rmsprop_body(const RmsChunk& c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd,
-                                             const float* __restrict__ ctl) {
+// The walk of an update kernel: tensor blockIdx.y of the chunk, parameter and NS state tensors read and written, the gradient read;
+// f(a, g) with a[0] the parameter's value, a[1 .. NS] the state's, g the gradient's (times the coefficient under CLIP).
+template <bool CLIP, int NS, int K, class F>
+__device__ __forceinline__ void update_walk(const Chunk<K>& c, const float* __restrict__ ctl, F f) {
+  static_assert(K >= 2 + NS, "parameter, gradient and NS state tables");
   float coef = 1.f;
   if (CLIP) {
     if (reinterpret_cast<const int*>(ctl)[CTL_APPLY] == 0) return;
     coef = ctl[CTL_COEF];
   }
-  if (lr_dev) lr = lr_dev[0];                 // a captured step (hipGraph) reads its learning rate from device memory
   const int t = blockIdx.y;
-  float* __restrict__ p = c.p[t]; const float* __restrict__ g = c.g[t]; float* __restrict__ v = c.v[t];
-  const long long n = c.n[t];
-  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)v) & 15) == 0);
-  const long long n4 = vec ? n / 4 : 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    f32x4 pp = reinterpret_cast<f32x4*>(p)[i], vv = reinterpret_cast<f32x4*>(v)[i];
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
+  float* w[1 + NS];
+  w[0] = c.t[0][t];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a = pp[e], b = vv[e];
-      rms_update(a, CLIP ? clip_mul(gg[e], coef) : gg[e], b, lr, alpha, eps, wd);
-      pp[e] = a; vv[e] = b;
-    }
-    reinterpret_cast<f32x4*>(p)[i] = pp; reinterpret_cast<f32x4*>(v)[i] = vv;
-  }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    rms_update(p[i], CLIP ? clip_mul(g[i], coef) : g[i], v[i], lr, alpha, eps, wd);
+  for (int k = 0; k < NS; ++k) w[1 + k] = c.t[2 + k][t];
+  walk<1 + NS, true>(w, c.t[1][t], c.n[t], [=](float (&a)[1 + NS], const float g0) { f(a, CLIP ? clip_mul(g0, coef) : g0); });
 }
 
-__global__ __launch_bounds__(256) void rmsprop_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd) {
+template <bool CLIP>
+__device__ __forceinline__ void rmsprop_body(const Chunk<3>& c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd,
+                                             const float* __restrict__ ctl) {
+  if (lr_dev) lr = lr_dev[0];                 // a captured step (hipGraph) reads its learning rate from device memory
+  update_walk<CLIP, 1>(c, ctl, [=](float (&a)[2], const float g) { rms_update(a[0], g, a[1], lr, alpha, eps, wd); });
+}
+
+__global__ __launch_bounds__(256) void rmsprop_kernel(const Chunk<3> c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd) {
   rmsprop_body<false>(c, lr, lr_dev, alpha, eps, wd, nullptr);
 }
-__global__ __launch_bounds__(256) void rmsprop_clip_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd,
+__global__ __launch_bounds__(256) void rmsprop_clip_kernel(const Chunk<3> c, float lr, const float* __restrict__ lr_dev, float alpha, float eps, float wd,
                                                            const float* __restrict__ ctl) {
   rmsprop_body<true>(c, lr, lr_dev, alpha, eps, wd, ctl);
 }
@@ -107,10 +150,6 @@ __global__ __launch_bounds__(64) void adamw_prepare_kernel(const StepChunk c, fl
   c.scal[blockIdx.x][2] = (float)(1.0 - (double)lr * wd);
 }
 
-struct AdamChunk {
-  float* p[RMS_CHUNK]; const float* g[RMS_CHUNK]; float* m[RMS_CHUNK]; float* v[RMS_CHUNK]; const float* s[RMS_CHUNK]; long long n[RMS_CHUNK];
-};
-
 // w1 = 1 - beta1, w2 = 1 - beta2 (rounded from double, as torch rounds the Python scalars it hands to lerp_ / addcmul_)
 __device__ __forceinline__ void adam_update(float& p, const float g0, float& m, float& v, float step_size, float inv_bc2_sqrt, float w1,
                                             float beta2, float w2, float eps, float wd) {
@@ -139,56 +178,31 @@ __device__ __forceinline__ void adamw_update(float& p, const float g, float& m, 
 
 // DECOUPLED = false is Adam as it was (two scalars per tensor, `wd` added to the gradient); true is AdamW (three scalars, `wd` unused)
 template <bool CLIP, bool DECOUPLED = false>
-__device__ __forceinline__ void adam_body(const AdamChunk& c, float w1, float beta2, float w2, float eps, float wd, const float* __restrict__ ctl) {
-  float coef = 1.f;
-  if (CLIP) {
-    if (reinterpret_cast<const int*>(ctl)[CTL_APPLY] == 0) return;
-    coef = ctl[CTL_COEF];
-  }
-  const int t = blockIdx.y;
-  float* __restrict__ p = c.p[t]; const float* __restrict__ g = c.g[t]; float* __restrict__ m = c.m[t]; float* __restrict__ v = c.v[t];
-  const float step_size = c.s[t][0], inv_bc2_sqrt = c.s[t][1];          // (adam_prepare_kernel wrote them in the launch before this one)
-  const float decay = DECOUPLED ? c.s[t][2] : 1.f;
-  const long long n = c.n[t];
-  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) == 0);
-  const long long n4 = vec ? n / 4 : 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    f32x4 pp = reinterpret_cast<f32x4*>(p)[i], mm = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a = pp[e], b = mm[e], d = vv[e];
-      const float ge = CLIP ? clip_mul(gg[e], coef) : gg[e];
-      if (DECOUPLED) adamw_update(a, ge, b, d, step_size, inv_bc2_sqrt, decay, w1, beta2, w2, eps);
-      else adam_update(a, ge, b, d, step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
-      pp[e] = a; mm[e] = b; vv[e] = d;
-    }
-    reinterpret_cast<f32x4*>(p)[i] = pp; reinterpret_cast<f32x4*>(m)[i] = mm; reinterpret_cast<f32x4*>(v)[i] = vv;
-  }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float ge = CLIP ? clip_mul(g[i], coef) : g[i];
-    if (DECOUPLED) adamw_update(p[i], ge, m[i], v[i], step_size, inv_bc2_sqrt, decay, w1, beta2, w2, eps);
-    else adam_update(p[i], ge, m[i], v[i], step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
-  }
+__device__ __forceinline__ void adam_body(const Chunk<5>& c, float w1, float beta2, float w2, float eps, float wd, const float* __restrict__ ctl) {
+  const float* __restrict__ s = c.t[4][blockIdx.y];                     // (adam_prepare_kernel wrote them in the launch before this one)
+  const float step_size = s[0], inv_bc2_sqrt = s[1], decay = DECOUPLED ? s[2] : 1.f;
+  update_walk<CLIP, 2>(c, ctl, [=](float (&a)[3], const float g) {
+    if (DECOUPLED) adamw_update(a[0], g, a[1], a[2], step_size, inv_bc2_sqrt, decay, w1, beta2, w2, eps);
+    else adam_update(a[0], g, a[1], a[2], step_size, inv_bc2_sqrt, w1, beta2, w2, eps, wd);
+  });
 }
 
-__global__ __launch_bounds__(256) void adamw_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps) {
+__global__ __launch_bounds__(256) void adamw_kernel(const Chunk<5> c, float w1, float beta2, float w2, float eps) {
   adam_body<false, true>(c, w1, beta2, w2, eps, 0.f, nullptr);
 }
-__global__ __launch_bounds__(256) void adamw_clip_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, const float* __restrict__ ctl) {
+__global__ __launch_bounds__(256) void adamw_clip_kernel(const Chunk<5> c, float w1, float beta2, float w2, float eps, const float* __restrict__ ctl) {
   adam_body<true, true>(c, w1, beta2, w2, eps, 0.f, ctl);
 }
 
-__global__ __launch_bounds__(256) void adam_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, float wd) {
+__global__ __launch_bounds__(256) void adam_kernel(const Chunk<5> c, float w1, float beta2, float w2, float eps, float wd) {
   adam_body<false>(c, w1, beta2, w2, eps, wd, nullptr);
 }
-__global__ __launch_bounds__(256) void adam_clip_kernel(const AdamChunk c, float w1, float beta2, float w2, float eps, float wd,
+__global__ __launch_bounds__(256) void adam_clip_kernel(const Chunk<5> c, float w1, float beta2, float w2, float eps, float wd,
                                                         const float* __restrict__ ctl) {
   adam_body<true>(c, w1, beta2, w2, eps, wd, ctl);
 }
 
 // ---- SGD with momentum --------------------------------------------------------------------------------------------------------
-// (same shape as RmsChunk: parameter, gradient, one state tensor)
 __device__ __forceinline__ void sgd_update(float& p, const float g0, float& buf, float lr, float mu, float wd) {
 #pragma clang fp contract(off)
   const float g = wd != 0.f ? g0 + wd * p : g0;          // grad = grad.add(param, alpha=weight_decay)
@@ -197,37 +211,15 @@ __device__ __forceinline__ void sgd_update(float& p, const float g0, float& buf,
 }
 
 template <bool CLIP>
-__device__ __forceinline__ void sgd_body(const RmsChunk& c, float lr, const float* __restrict__ lr_dev, float mu, float wd, const float* __restrict__ ctl) {
-  float coef = 1.f;
-  if (CLIP) {
-    if (reinterpret_cast<const int*>(ctl)[CTL_APPLY] == 0) return;
-    coef = ctl[CTL_COEF];
-  }
+__device__ __forceinline__ void sgd_body(const Chunk<3>& c, float lr, const float* __restrict__ lr_dev, float mu, float wd, const float* __restrict__ ctl) {
   if (lr_dev) lr = lr_dev[0];
-  const int t = blockIdx.y;
-  float* __restrict__ p = c.p[t]; const float* __restrict__ g = c.g[t]; float* __restrict__ b = c.v[t];
-  const long long n = c.n[t];
-  const bool vec = ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)b) & 15) == 0);
-  const long long n4 = vec ? n / 4 : 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    f32x4 pp = reinterpret_cast<f32x4*>(p)[i], bb = reinterpret_cast<f32x4*>(b)[i];
-    const f32x4 gg = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      float a = pp[e], d = bb[e];
-      sgd_update(a, CLIP ? clip_mul(gg[e], coef) : gg[e], d, lr, mu, wd);
-      pp[e] = a; bb[e] = d;
-    }
-    reinterpret_cast<f32x4*>(p)[i] = pp; reinterpret_cast<f32x4*>(b)[i] = bb;
-  }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    sgd_update(p[i], CLIP ? clip_mul(g[i], coef) : g[i], b[i], lr, mu, wd);
+  update_walk<CLIP, 1>(c, ctl, [=](float (&a)[2], const float g) { sgd_update(a[0], g, a[1], lr, mu, wd); });
 }
 
-__global__ __launch_bounds__(256) void sgd_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float mu, float wd) {
+__global__ __launch_bounds__(256) void sgd_kernel(const Chunk<3> c, float lr, const float* __restrict__ lr_dev, float mu, float wd) {
   sgd_body<false>(c, lr, lr_dev, mu, wd, nullptr);
 }
-__global__ __launch_bounds__(256) void sgd_clip_kernel(const RmsChunk c, float lr, const float* __restrict__ lr_dev, float mu, float wd,
+__global__ __launch_bounds__(256) void sgd_clip_kernel(const Chunk<3> c, float lr, const float* __restrict__ lr_dev, float mu, float wd,
                                                        const float* __restrict__ ctl) {
   sgd_body<true>(c, lr, lr_dev, mu, wd, ctl);
 }
@@ -246,8 +238,45 @@ __global__ __launch_bounds__(64) void ema_prepare_kernel(int* __restrict__ step,
   w[0] = (float)(1.0 - d);
 }
 
-struct EmaChunk { float* s[RMS_CHUNK]; const float* x[RMS_CHUNK]; long long n[RMS_CHUNK]; };
-struct SwapChunk { float* a[RMS_CHUNK]; float* b[RMS_CHUNK]; long long n[RMS_CHUNK]; };
+// The walk of the two-stream passes over tensor blockIdx.y of the chunk, a = table 0 and b = table 1: f(x, y) on the values of one
+// element; a is written back, b under WB.  `walk`'s paths, but two trips at once — four 16-byte loads in flight per thread (these
+// passes have two streams where the optimiser updates have three or four).  Every value is handled by exactly one thread.
+template <bool WB, class F>
+__device__ __forceinline__ void walk2(const Chunk<2>& c, F f) {
+  const int t = blockIdx.y;
+  float* __restrict__ a = c.t[0][t]; float* __restrict__ b = c.t[1][t];
+  const long long n = c.n[t];
+  const long long n4 = ((((uintptr_t)a | (uintptr_t)b) & 15) == 0) ? n / 4 : 0;
+  const long long stride = (long long)gridDim.x * 256;
+  f32x4* __restrict__ a4 = reinterpret_cast<f32x4*>(a); f32x4* __restrict__ b4 = reinterpret_cast<f32x4*>(b);
+  const auto f4 = [&](f32x4& x, f32x4& y) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      float xe = x[e], ye = y[e];
+      f(xe, ye);
+      x[e] = xe; y[e] = ye;
+    }
+  };
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  for (; i + stride < n4; i += 2 * stride) {
+    f32x4 x0 = a4[i], x1 = a4[i + stride], y0 = b4[i], y1 = b4[i + stride];
+    f4(x0, y0); f4(x1, y1);
+    a4[i] = x0; a4[i + stride] = x1;
+    if (WB) { b4[i] = y0; b4[i + stride] = y1; }
+  }
+  for (; i < n4; i += stride) {
+    f32x4 x0 = a4[i], y0 = b4[i];
+    f4(x0, y0);
+    a4[i] = x0;
+    if (WB) b4[i] = y0;
+  }
+  for (i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
+    float x = a[i], y = b[i];
+    f(x, y);
+    a[i] = x;
+    if (WB) b[i] = y;
+  }
+}
 
 // torch's fp32 lerp (the form adam_update uses for exp_avg).  x == s gives d = 0 and keeps s bit for bit in either form, but for
 // s = -0.0 under w < 0.5 (-0 + 0 is +0): the select keeps that one too, so a tensor nobody trains never changes a bit.
@@ -257,64 +286,17 @@ __device__ __forceinline__ float ema_lerp(const float s, const float x, const fl
   const float r = w < 0.5f ? s + w * d : x - d * (1.f - w);
   return d == 0.f ? s : r;
 }
-__device__ __forceinline__ f32x4 ema_lerp4(f32x4 s, const f32x4 x, const float w) {
-#pragma unroll
-  for (int e = 0; e < 4; ++e) s[e] = ema_lerp(s[e], x[e], w);
-  return s;
-}
 
-__global__ __launch_bounds__(256) void ema_update_kernel(const EmaChunk c, const float* __restrict__ wp, const int* __restrict__ ctl) {
+// (tables: 0 the shadow, 1 the source)
+__global__ __launch_bounds__(256) void ema_update_kernel(const Chunk<2> c, const float* __restrict__ wp, const int* __restrict__ ctl) {
   if (ctl && ctl[CTL_APPLY] == 0) return;
   const float w = wp[0];                      // (ema_prepare_kernel wrote it in the launch before this one)
-  const int t = blockIdx.y;
-  float* __restrict__ s = c.s[t]; const float* __restrict__ x = c.x[t];
-  const long long n = c.n[t];
-  const bool vec = ((((uintptr_t)s | (uintptr_t)x) & 15) == 0);
-  const long long n4 = vec ? n / 4 : 0;
-  const long long stride = (long long)gridDim.x * 256;
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  // two trips at once: four 16-byte loads in flight per thread (the pass has two streams where the optimiser updates have three or four)
-  for (; i + stride < n4; i += 2 * stride) {
-    const f32x4 s0 = reinterpret_cast<f32x4*>(s)[i], s1 = reinterpret_cast<f32x4*>(s)[i + stride];
-    const f32x4 x0 = reinterpret_cast<const f32x4*>(x)[i], x1 = reinterpret_cast<const f32x4*>(x)[i + stride];
-    reinterpret_cast<f32x4*>(s)[i] = ema_lerp4(s0, x0, w);
-    reinterpret_cast<f32x4*>(s)[i + stride] = ema_lerp4(s1, x1, w);
-  }
-  for (; i < n4; i += stride)
-    reinterpret_cast<f32x4*>(s)[i] = ema_lerp4(reinterpret_cast<f32x4*>(s)[i], reinterpret_cast<const f32x4*>(x)[i], w);
-  for (i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride)
-    s[i] = ema_lerp(s[i], x[i], w);
+  walk2<false>(c, [=](float& s, float& x) { s = ema_lerp(s, x, w); });
 }
 
-// a <-> b: 8 B read + 8 B written per value; every value is moved by exactly one thread
-__global__ __launch_bounds__(256) void tensor_swap_kernel(const SwapChunk c) {
-  const int t = blockIdx.y;
-  float* __restrict__ a = c.a[t]; float* __restrict__ b = c.b[t];
-  const long long n = c.n[t];
-  const bool vec = ((((uintptr_t)a | (uintptr_t)b) & 15) == 0);
-  const long long n4 = vec ? n / 4 : 0;
-  const long long stride = (long long)gridDim.x * 256;
-  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  for (; i + stride < n4; i += 2 * stride) {
-    const f32x4 a0 = reinterpret_cast<f32x4*>(a)[i], a1 = reinterpret_cast<f32x4*>(a)[i + stride];
-    const f32x4 b0 = reinterpret_cast<f32x4*>(b)[i], b1 = reinterpret_cast<f32x4*>(b)[i + stride];
-    reinterpret_cast<f32x4*>(a)[i] = b0; reinterpret_cast<f32x4*>(a)[i + stride] = b1;
-    reinterpret_cast<f32x4*>(b)[i] = a0; reinterpret_cast<f32x4*>(b)[i + stride] = a1;
-  }
-  for (; i < n4; i += stride) {
-    const f32x4 a0 = reinterpret_cast<f32x4*>(a)[i], b0 = reinterpret_cast<f32x4*>(b)[i];
-    reinterpret_cast<f32x4*>(a)[i] = b0; reinterpret_cast<f32x4*>(b)[i] = a0;
-  }
-  for (i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-    const float a0 = a[i], b0 = b[i];
-    a[i] = b0; b[i] = a0;
-  }
-}
-
-// blocks along x for a chunk whose longest tensor has `biggest` values (grid-stride beyond 128)
-inline unsigned blocks_for(long long biggest) {
-  const long long bx = (biggest / 4 + 255) / 256;
-  return (unsigned)(bx < 1 ? 1 : (bx > 128 ? 128 : bx));
+// a <-> b: 8 B read + 8 B written per value
+__global__ __launch_bounds__(256) void tensor_swap_kernel(const Chunk<2> c) {
+  walk2<true>(c, [](float& a, float& b) { const float a0 = a; a = b; b = a0; });
 }
 
 // ---- global gradient norm ---------------------------------------------------------------------------------------------------------
@@ -324,8 +306,6 @@ inline unsigned blocks_for(long long biggest) {
 // atomics, no arrival counters: the norm is the same bits in every run, eager or replayed.  A thread takes the same four
 // consecutive values per trip whether the pointer is 16-byte aligned (one 16-byte load) or not (four 4-byte loads), so a view
 // into a flat gradient buffer gives the same bits as an aligned tensor.
-struct NormChunk { const float* g[RMS_CHUNK]; long long n[RMS_CHUNK]; };
-struct ScaleChunk { float* g[RMS_CHUNK]; long long n[RMS_CHUNK]; };
 
 // sum over the WAVES x 64 threads of a block, in a fixed order; `red` = WAVES doubles of shared memory.  Every thread must call.
 template <int WAVES>
@@ -353,10 +333,11 @@ __device__ __forceinline__ double add_squares(double acc, const f32x4 gg) {
   return acc;
 }
 
-__global__ __launch_bounds__(256) void grad_sumsq_kernel(const NormChunk c, double* __restrict__ partials) {
+// (table 0: the gradients, read only)
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const Chunk<1> c, double* __restrict__ partials) {
   __shared__ double red[4];
   const int t = blockIdx.y;
-  const float* __restrict__ g = c.g[t];
+  const float* __restrict__ g = c.t[0][t];
   const long long n = c.n[t], n4 = n / 4;
   const bool vec = (((uintptr_t)g) & 15) == 0;
   const long long stride = (long long)gridDim.x * 256;
@@ -407,34 +388,79 @@ __global__ __launch_bounds__(1024) void grad_clip_coef_kernel(const double* __re
   if (!apply) w[CTL_SKIPS] = w[CTL_SKIPS] + 1;
 }
 
-__global__ __launch_bounds__(256) void grad_scale_kernel(const ScaleChunk c, const float* __restrict__ ctl) {
+// (table 0: the gradients, scaled in place whatever `apply` says — the stand-alone clip_grad_norm_)
+__global__ __launch_bounds__(256) void grad_scale_kernel(const Chunk<1> c, const float* __restrict__ ctl) {
   const float coef = ctl[CTL_COEF];
-  const int t = blockIdx.y;
-  float* __restrict__ g = c.g[t];
-  const long long n = c.n[t];
-  const long long n4 = ((((uintptr_t)g) & 15) == 0) ? n / 4 : 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
-    f32x4 gg = reinterpret_cast<f32x4*>(g)[i];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) gg[e] = clip_mul(gg[e], coef);
-    reinterpret_cast<f32x4*>(g)[i] = gg;
+  float* const w[1] = {c.t[0][blockIdx.y]};
+  walk<1, false>(w, nullptr, c.n[blockIdx.y], [=](float (&a)[1], float) { a[0] = clip_mul(a[0], coef); });
+}
+
+// ---- host: the chunked launches -----------------------------------------------------------------------------------------------------
+// blocks along x for a chunk whose longest tensor has `biggest` values (grid-stride beyond 128)
+inline unsigned blocks_for(long long biggest) {
+  const long long bx = (biggest / 4 + 255) / 256;
+  return (unsigned)(bx < 1 ? 1 : (bx > 128 ? 128 : bx));
+}
+inline long long longest(const int64_t* numel, int m) {
+  long long biggest = 0;
+  for (int i = 0; i < m; ++i)
+    if (numel[i] > biggest) biggest = numel[i];
+  return biggest;
+}
+
+// The chunk loop: f(base, m) for the tensors [base, base + m) of every chunk of at most `cap`, until one does not return DCN_OK.
+template <class F>
+inline int for_chunks(int count, int cap, F f) {
+  for (int base = 0; base < count; base += cap) {
+    const int e = f(base, count - base < cap ? count - base : cap);
+    if (e != DCN_OK) return e;
   }
-  for (long long i = n4 * 4 + (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256)
-    g[i] = clip_mul(g[i], coef);
+  return DCN_OK;
 }
 
 // slots of the partials buffer for `count` tensors: per chunk of 32, blocks_for(its longest tensor) x tensors in the chunk
 inline long long sumsq_slots(const int64_t* numel, int count) {
   long long total = 0;
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i)
-      if (numel[base + i] > biggest) biggest = numel[base + i];
-    total += (long long)blocks_for(biggest) * m;
-  }
+  for_chunks(count, RMS_CHUNK, [&](int base, int m) {
+    total += (long long)blocks_for(longest(numel + base, m)) * m;
+    return DCN_OK;
+  });
   return total;
 }
+
+// The K pointer tables of an entry point, in its kernel's table order.
+template <int K> using Tables = const float* const* const (&)[K];
+
+// Every tensor is looked at before the first launch: no null pointer, no negative count.  `empties`: a tensor of 0 values may be NULL.
+template <int K>
+int check_tensors(const char* who, Tables<K> tab, const int64_t* numel, int count, bool empties = false) {
+  for (int k = 0; k < count; ++k) {
+    bool there = true;
+    for (int j = 0; j < K; ++j) there = there && tab[j][k];
+    DCN_CHECK_ARG(numel[k] >= 0 && (there || (empties && numel[k] == 0)), "%s: null tensor %d", who, k);
+  }
+  return DCN_OK;
+}
+
+// The one chunked launch: 32 tensors per launch, launch(chunk, grid) with grid = (blocks_for(the chunk's longest tensor), tensors in
+// the chunk).  `empties` (EMA, swap): a chunk of empty tensors launches nothing.
+template <int K, class L>
+int launch_chunks(const char* who, Tables<K> tab, const int64_t* numel, int count, bool empties, L launch) {
+  return for_chunks(count, RMS_CHUNK, [&](int base, int m) -> int {
+    Chunk<K> c{};
+    for (int i = 0; i < m; ++i) {
+      for (int j = 0; j < K; ++j) c.t[j][i] = const_cast<float*>(tab[j][base + i]);
+      c.n[i] = numel[base + i];
+    }
+    const long long biggest = longest(numel + base, m);
+    if (empties && biggest == 0) return DCN_OK;
+    launch(c, dim3(blocks_for(biggest), m));
+    DCN_CHECK_LAUNCH(who);
+    return DCN_OK;
+  });
+}
+
+#define OPTIM_LAUNCH(kernel, ...) hipLaunchKernelGGL(kernel, grid, dim3(256), 0, (hipStream_t)stream, __VA_ARGS__)
 
 }  // namespace
 
@@ -447,25 +473,14 @@ extern "C" int64_t dcn_grad_sumsq_slots(const int64_t* numel, int count) {
 
 extern "C" int dcn_grad_sumsq(const float* const* grads, const int64_t* numel, int count, double* partials, int64_t slots, void* stream) {
   DCN_CHECK_ARG(grads && numel && partials && count > 0, "grad_sumsq: bad argument");
-  for (int i = 0; i < count; ++i)
-    DCN_CHECK_ARG(grads[i] && numel[i] >= 0, "grad_sumsq: null tensor %d", i);
+  if (const int e = check_tensors<1>("grad_sumsq", {grads}, numel, count)) return e;
   DCN_CHECK_ARG(slots == sumsq_slots(numel, count), "grad_sumsq: the partials buffer has %lld slots, these tensors need %lld (dcn_grad_sumsq_slots)",
                 (long long)slots, sumsq_slots(numel, count));
   long long at = 0;
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    NormChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      c.g[i] = grads[base + i]; c.n[i] = numel[base + i];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    const unsigned bx = blocks_for(biggest);
-    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(bx, m), dim3(256), 0, (hipStream_t)stream, c, partials + at);
-    DCN_CHECK_LAUNCH("grad_sumsq");
-    at += (long long)bx * m;
-  }
-  return DCN_OK;
+  return launch_chunks<1>("grad_sumsq", {grads}, numel, count, false, [&](const Chunk<1>& c, dim3 grid) {
+    OPTIM_LAUNCH(grad_sumsq_kernel, c, partials + at);
+    at += (long long)grid.x * grid.y;
+  });
 }
 
 extern "C" int dcn_grad_clip_coef(const double* partials, int64_t slots, float max_norm, int skip_nonfinite, void* ctrl, void* stream) {
@@ -479,20 +494,9 @@ extern "C" int dcn_grad_clip_coef(const double* partials, int64_t slots, float m
 
 extern "C" int dcn_grad_scale(float* const* grads, const int64_t* numel, int count, const void* ctrl, void* stream) {
   DCN_CHECK_ARG(grads && numel && ctrl && count > 0, "grad_scale: bad argument");
-  for (int i = 0; i < count; ++i)
-    DCN_CHECK_ARG(grads[i] && numel[i] >= 0, "grad_scale: null tensor %d", i);
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    ScaleChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      c.g[i] = grads[base + i]; c.n[i] = numel[base + i];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    hipLaunchKernelGGL(grad_scale_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (const float*)ctrl);
-    DCN_CHECK_LAUNCH("grad_scale");
-  }
-  return DCN_OK;
+  if (const int e = check_tensors<1>("grad_scale", {grads}, numel, count)) return e;
+  return launch_chunks<1>("grad_scale", {grads}, numel, count, false,
+                          [&](const Chunk<1>& c, dim3 grid) { OPTIM_LAUNCH(grad_scale_kernel, c, (const float*)ctrl); });
 }
 
 // The update entry points come in two forms over one body each: the plain one launches the kernels it always launched, the
@@ -500,22 +504,11 @@ extern "C" int dcn_grad_scale(float* const* grads, const int64_t* numel, int cou
 static int rmsprop_step(const char* who, float* const* params, const float* const* grads, float* const* square_avgs, const int64_t* numel,
                         int count, float lr, const float* lr_dev, float alpha, float eps, float weight_decay, const float* ctl, void* stream) {
   DCN_CHECK_ARG(params && grads && square_avgs && numel && count > 0, "%s: bad argument", who);
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    RmsChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      DCN_CHECK_ARG(params[base + i] && grads[base + i] && square_avgs[base + i] && numel[base + i] >= 0, "%s: null tensor %d", who, base + i);
-      c.p[i] = params[base + i]; c.g[i] = grads[base + i]; c.v[i] = square_avgs[base + i]; c.n[i] = numel[base + i];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    if (ctl)
-      hipLaunchKernelGGL(rmsprop_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, alpha, eps, weight_decay, ctl);
-    else
-      hipLaunchKernelGGL(rmsprop_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, alpha, eps, weight_decay);
-    DCN_CHECK_LAUNCH(who);
-  }
-  return DCN_OK;
+  if (const int e = check_tensors<3>(who, {params, grads, square_avgs}, numel, count)) return e;
+  return launch_chunks<3>(who, {params, grads, square_avgs}, numel, count, false, [&](const Chunk<3>& c, dim3 grid) {
+    if (ctl) OPTIM_LAUNCH(rmsprop_clip_kernel, c, lr, lr_dev, alpha, eps, weight_decay, ctl);
+    else OPTIM_LAUNCH(rmsprop_kernel, c, lr, lr_dev, alpha, eps, weight_decay);
+  });
 }
 
 extern "C" int dcn_rmsprop_step(float* const* params, const float* const* grads, float* const* square_avgs, const int64_t* numel,
@@ -530,75 +523,90 @@ extern "C" int dcn_rmsprop_step_clipped(float* const* params, const float* const
   return rmsprop_step("rmsprop_step_clipped", params, grads, square_avgs, numel, count, lr, lr_dev, alpha, eps, weight_decay, (const float*)ctrl, stream);
 }
 
-static int adam_prepare(const char* who, int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
-                        const int* ctl, void* stream) {
+// Adam and AdamW (`decoupled`: its own entry points, three scalars per tensor — Adam's keep theirs and their two) differ in the
+// weight-decay check, in `weight_decay` (Adam: an argument of the update; AdamW: of the prepare launch, the third scalar) and in the kernels.
+static int adam_prepare(const char* who, bool decoupled, int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1,
+                        double beta2, double weight_decay, const int* ctl, void* stream) {
   DCN_CHECK_ARG(steps && scal && count > 0, "%s: bad argument", who);
   DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
-  for (int base = 0; base < count; base += STEP_CHUNK) {
+  DCN_CHECK_ARG(!decoupled || weight_decay >= 0.0, "%s: negative weight_decay", who);
+  for (int k = 0; k < count; ++k)
+    DCN_CHECK_ARG(steps[k] && scal[k], "%s: null tensor %d", who, k);
+  return for_chunks(count, STEP_CHUNK, [&](int base, int m) -> int {
     StepChunk c{};
-    const int m = count - base < STEP_CHUNK ? count - base : STEP_CHUNK;
-    for (int i = 0; i < m; ++i) {
-      DCN_CHECK_ARG(steps[base + i] && scal[base + i], "%s: null tensor %d", who, base + i);
-      c.step[i] = steps[base + i]; c.scal[i] = scal[base + i];
-    }
-    if (ctl)
-      hipLaunchKernelGGL(adam_prepare_clip_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2, ctl);
-    else
-      hipLaunchKernelGGL(adam_prepare_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2);
+    for (int i = 0; i < m; ++i) { c.step[i] = steps[base + i]; c.scal[i] = scal[base + i]; }
+    const dim3 grid(m), block(64);
+    if (decoupled) hipLaunchKernelGGL(adamw_prepare_kernel, grid, block, 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2, weight_decay, ctl);
+    else if (ctl) hipLaunchKernelGGL(adam_prepare_clip_kernel, grid, block, 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2, ctl);
+    else hipLaunchKernelGGL(adam_prepare_kernel, grid, block, 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2);
     DCN_CHECK_LAUNCH(who);
-  }
-  return DCN_OK;
+    return DCN_OK;
+  });
 }
 
 extern "C" int dcn_adam_prepare(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
                                 void* stream) {
-  return adam_prepare("adam_prepare", steps, scal, count, lr, lr_dev, beta1, beta2, nullptr, stream);
+  return adam_prepare("adam_prepare", false, steps, scal, count, lr, lr_dev, beta1, beta2, 0.0, nullptr, stream);
 }
 
 extern "C" int dcn_adam_prepare_clipped(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
                                         const void* ctrl, void* stream) {
   DCN_CHECK_ARG(ctrl, "adam_prepare_clipped: no control block");
-  return adam_prepare("adam_prepare_clipped", steps, scal, count, lr, lr_dev, beta1, beta2, (const int*)ctrl, stream);
+  return adam_prepare("adam_prepare_clipped", false, steps, scal, count, lr, lr_dev, beta1, beta2, 0.0, (const int*)ctrl, stream);
 }
 
-static int adam_step(const char* who, float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                     const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, float weight_decay,
-                     const float* ctl, void* stream) {
+extern "C" int dcn_adamw_prepare(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                                 double weight_decay, void* stream) {
+  return adam_prepare("adamw_prepare", true, steps, scal, count, lr, lr_dev, beta1, beta2, weight_decay, nullptr, stream);
+}
+
+extern "C" int dcn_adamw_prepare_clipped(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
+                                         double weight_decay, const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(ctrl, "adamw_prepare_clipped: no control block");
+  return adam_prepare("adamw_prepare_clipped", true, steps, scal, count, lr, lr_dev, beta1, beta2, weight_decay, (const int*)ctrl, stream);
+}
+
+static int adam_step(const char* who, bool decoupled, float* const* params, const float* const* grads, float* const* exp_avgs,
+                     float* const* exp_avg_sqs, const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
+                     float weight_decay, const float* ctl, void* stream) {
   DCN_CHECK_ARG(params && grads && exp_avgs && exp_avg_sqs && scal && numel && count > 0, "%s: bad argument", who);
   DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
-  DCN_CHECK_ARG(eps >= 0.f && weight_decay >= 0.f, "%s: negative eps or weight_decay", who);
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    AdamChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      const int k = base + i;
-      DCN_CHECK_ARG(params[k] && grads[k] && exp_avgs[k] && exp_avg_sqs[k] && scal[k] && numel[k] >= 0, "%s: null tensor %d", who, k);
-      c.p[i] = params[k]; c.g[i] = grads[k]; c.m[i] = exp_avgs[k]; c.v[i] = exp_avg_sqs[k]; c.s[i] = scal[k]; c.n[i] = numel[k];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    if (ctl)
-      hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
-                         (float)(1.0 - beta2), eps, weight_decay, ctl);
-    else
-      hipLaunchKernelGGL(adam_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
-                         (float)(1.0 - beta2), eps, weight_decay);
-    DCN_CHECK_LAUNCH(who);
-  }
-  return DCN_OK;
+  if (decoupled) DCN_CHECK_ARG(eps >= 0.f, "%s: negative eps", who);
+  else DCN_CHECK_ARG(eps >= 0.f && weight_decay >= 0.f, "%s: negative eps or weight_decay", who);
+  if (const int e = check_tensors<5>(who, {params, grads, exp_avgs, exp_avg_sqs, scal}, numel, count)) return e;
+  const float w1 = (float)(1.0 - beta1), b2 = (float)beta2, w2 = (float)(1.0 - beta2);
+  return launch_chunks<5>(who, {params, grads, exp_avgs, exp_avg_sqs, scal}, numel, count, false, [&](const Chunk<5>& c, dim3 grid) {
+    if (decoupled && ctl) OPTIM_LAUNCH(adamw_clip_kernel, c, w1, b2, w2, eps, ctl);
+    else if (decoupled) OPTIM_LAUNCH(adamw_kernel, c, w1, b2, w2, eps);
+    else if (ctl) OPTIM_LAUNCH(adam_clip_kernel, c, w1, b2, w2, eps, weight_decay, ctl);
+    else OPTIM_LAUNCH(adam_kernel, c, w1, b2, w2, eps, weight_decay);
+  });
 }
 
 extern "C" int dcn_adam_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
                              const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
                              float weight_decay, void* stream) {
-  return adam_step("adam_step", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, weight_decay, nullptr, stream);
+  return adam_step("adam_step", false, params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, weight_decay, nullptr, stream);
 }
 
 extern "C" int dcn_adam_step_clipped(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
                                      const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
                                      float weight_decay, const void* ctrl, void* stream) {
   DCN_CHECK_ARG(ctrl, "adam_step_clipped: no control block");
-  return adam_step("adam_step_clipped", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, weight_decay, (const float*)ctrl,
+  return adam_step("adam_step_clipped", false, params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, weight_decay,
+                   (const float*)ctrl, stream);
+}
+
+extern "C" int dcn_adamw_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                              const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, void* stream) {
+  return adam_step("adamw_step", true, params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, 0.f, nullptr, stream);
+}
+
+extern "C" int dcn_adamw_step_clipped(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
+                                      const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
+                                      const void* ctrl, void* stream) {
+  DCN_CHECK_ARG(ctrl, "adamw_step_clipped: no control block");
+  return adam_step("adamw_step_clipped", true, params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, 0.f, (const float*)ctrl,
                    stream);
 }
 
@@ -606,23 +614,11 @@ static int sgd_step(const char* who, float* const* params, const float* const* g
                     float lr, const float* lr_dev, float momentum, float weight_decay, const float* ctl, void* stream) {
   DCN_CHECK_ARG(params && grads && momentum_bufs && numel && count > 0, "%s: bad argument", who);
   DCN_CHECK_ARG(momentum >= 0.f && weight_decay >= 0.f, "%s: negative momentum or weight_decay", who);
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    RmsChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      const int k = base + i;
-      DCN_CHECK_ARG(params[k] && grads[k] && momentum_bufs[k] && numel[k] >= 0, "%s: null tensor %d", who, k);
-      c.p[i] = params[k]; c.g[i] = grads[k]; c.v[i] = momentum_bufs[k]; c.n[i] = numel[k];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    if (ctl)
-      hipLaunchKernelGGL(sgd_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, momentum, weight_decay, ctl);
-    else
-      hipLaunchKernelGGL(sgd_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, lr, lr_dev, momentum, weight_decay);
-    DCN_CHECK_LAUNCH(who);
-  }
-  return DCN_OK;
+  if (const int e = check_tensors<3>(who, {params, grads, momentum_bufs}, numel, count)) return e;
+  return launch_chunks<3>(who, {params, grads, momentum_bufs}, numel, count, false, [&](const Chunk<3>& c, dim3 grid) {
+    if (ctl) OPTIM_LAUNCH(sgd_clip_kernel, c, lr, lr_dev, momentum, weight_decay, ctl);
+    else OPTIM_LAUNCH(sgd_kernel, c, lr, lr_dev, momentum, weight_decay);
+  });
 }
 
 extern "C" int dcn_sgd_step(float* const* params, const float* const* grads, float* const* momentum_bufs, const int64_t* numel, int count,
@@ -634,75 +630,6 @@ extern "C" int dcn_sgd_step_clipped(float* const* params, const float* const* gr
                                     float lr, const float* lr_dev, float momentum, float weight_decay, const void* ctrl, void* stream) {
   DCN_CHECK_ARG(ctrl, "sgd_step_clipped: no control block");
   return sgd_step("sgd_step_clipped", params, grads, momentum_bufs, numel, count, lr, lr_dev, momentum, weight_decay, (const float*)ctrl, stream);
-}
-
-// AdamW (decoupled weight decay): its own entry points, three scalars per tensor — Adam's keep theirs and their two.
-static int adamw_prepare(const char* who, int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
-                         double weight_decay, const void* ctrl, void* stream) {
-  DCN_CHECK_ARG(steps && scal && count > 0, "%s: bad argument", who);
-  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
-  DCN_CHECK_ARG(weight_decay >= 0.0, "%s: negative weight_decay", who);
-  for (int base = 0; base < count; base += STEP_CHUNK) {
-    StepChunk c{};
-    const int m = count - base < STEP_CHUNK ? count - base : STEP_CHUNK;
-    for (int i = 0; i < m; ++i) {
-      DCN_CHECK_ARG(steps[base + i] && scal[base + i], "%s: null tensor %d", who, base + i);
-      c.step[i] = steps[base + i]; c.scal[i] = scal[base + i];
-    }
-    hipLaunchKernelGGL(adamw_prepare_kernel, dim3(m), dim3(64), 0, (hipStream_t)stream, c, lr, lr_dev, beta1, beta2, weight_decay, (const int*)ctrl);
-    DCN_CHECK_LAUNCH(who);
-  }
-  return DCN_OK;
-}
-
-extern "C" int dcn_adamw_prepare(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
-                                 double weight_decay, void* stream) {
-  return adamw_prepare("adamw_prepare", steps, scal, count, lr, lr_dev, beta1, beta2, weight_decay, nullptr, stream);
-}
-
-extern "C" int dcn_adamw_prepare_clipped(int* const* steps, float* const* scal, int count, float lr, const float* lr_dev, double beta1, double beta2,
-                                         double weight_decay, const void* ctrl, void* stream) {
-  DCN_CHECK_ARG(ctrl, "adamw_prepare_clipped: no control block");
-  return adamw_prepare("adamw_prepare_clipped", steps, scal, count, lr, lr_dev, beta1, beta2, weight_decay, ctrl, stream);
-}
-
-static int adamw_step(const char* who, float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                      const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, const void* ctrl,
-                      void* stream) {
-  DCN_CHECK_ARG(params && grads && exp_avgs && exp_avg_sqs && scal && numel && count > 0, "%s: bad argument", who);
-  DCN_CHECK_ARG(beta1 >= 0.0 && beta1 < 1.0 && beta2 >= 0.0 && beta2 < 1.0, "%s: betas (%g, %g) outside [0, 1)", who, beta1, beta2);
-  DCN_CHECK_ARG(eps >= 0.f, "%s: negative eps", who);
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    AdamChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      const int k = base + i;
-      DCN_CHECK_ARG(params[k] && grads[k] && exp_avgs[k] && exp_avg_sqs[k] && scal[k] && numel[k] >= 0, "%s: null tensor %d", who, k);
-      c.p[i] = params[k]; c.g[i] = grads[k]; c.m[i] = exp_avgs[k]; c.v[i] = exp_avg_sqs[k]; c.s[i] = scal[k]; c.n[i] = numel[k];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    if (ctrl)
-      hipLaunchKernelGGL(adamw_clip_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
-                         (float)(1.0 - beta2), eps, (const float*)ctrl);
-    else
-      hipLaunchKernelGGL(adamw_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, (float)(1.0 - beta1), (float)beta2,
-                         (float)(1.0 - beta2), eps);
-    DCN_CHECK_LAUNCH(who);
-  }
-  return DCN_OK;
-}
-
-extern "C" int dcn_adamw_step(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                              const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps, void* stream) {
-  return adamw_step("adamw_step", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, nullptr, stream);
-}
-
-extern "C" int dcn_adamw_step_clipped(float* const* params, const float* const* grads, float* const* exp_avgs, float* const* exp_avg_sqs,
-                                      const float* const* scal, const int64_t* numel, int count, double beta1, double beta2, float eps,
-                                      const void* ctrl, void* stream) {
-  DCN_CHECK_ARG(ctrl, "adamw_step_clipped: no control block");
-  return adamw_step("adamw_step_clipped", params, grads, exp_avgs, exp_avg_sqs, scal, numel, count, beta1, beta2, eps, ctrl, stream);
 }
 
 // ---- weight EMA and swap: any count (0 launches nothing), tensors of 0 values allowed (their pointers may be NULL) -----------------
@@ -718,38 +645,13 @@ extern "C" int dcn_ema_prepare(int* step, float* w, double decay, double tau, co
 extern "C" int dcn_ema_update(float* const* shadow, const float* const* src, const int64_t* numel, int count, const float* w, const void* ctrl,
                               void* stream) {
   DCN_CHECK_ARG(count >= 0 && w && (count == 0 || (shadow && src && numel)), "ema_update: bad argument");
-  for (int i = 0; i < count; ++i)
-    DCN_CHECK_ARG(numel[i] >= 0 && (numel[i] == 0 || (shadow[i] && src[i])), "ema_update: null tensor %d", i);
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    EmaChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      c.s[i] = shadow[base + i]; c.x[i] = src[base + i]; c.n[i] = numel[base + i];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    if (biggest == 0) continue;                // a chunk of empty tensors
-    hipLaunchKernelGGL(ema_update_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c, w, (const int*)ctrl);
-    DCN_CHECK_LAUNCH("ema_update");
-  }
-  return DCN_OK;
+  if (const int e = check_tensors<2>("ema_update", {shadow, src}, numel, count, true)) return e;
+  return launch_chunks<2>("ema_update", {shadow, src}, numel, count, true,
+                          [&](const Chunk<2>& c, dim3 grid) { OPTIM_LAUNCH(ema_update_kernel, c, w, (const int*)ctrl); });
 }
 
 extern "C" int dcn_tensor_swap(float* const* a, float* const* b, const int64_t* numel, int count, void* stream) {
   DCN_CHECK_ARG(count >= 0 && (count == 0 || (a && b && numel)), "tensor_swap: bad argument");
-  for (int i = 0; i < count; ++i)
-    DCN_CHECK_ARG(numel[i] >= 0 && (numel[i] == 0 || (a[i] && b[i])), "tensor_swap: null tensor %d", i);
-  for (int base = 0; base < count; base += RMS_CHUNK) {
-    SwapChunk c{};
-    const int m = count - base < RMS_CHUNK ? count - base : RMS_CHUNK;
-    long long biggest = 0;
-    for (int i = 0; i < m; ++i) {
-      c.a[i] = a[base + i]; c.b[i] = b[base + i]; c.n[i] = numel[base + i];
-      if (c.n[i] > biggest) biggest = c.n[i];
-    }
-    if (biggest == 0) continue;
-    hipLaunchKernelGGL(tensor_swap_kernel, dim3(blocks_for(biggest), m), dim3(256), 0, (hipStream_t)stream, c);
-    DCN_CHECK_LAUNCH("tensor_swap");
-  }
-  return DCN_OK;
+  if (const int e = check_tensors<2>("tensor_swap", {a, b}, numel, count, true)) return e;
+  return launch_chunks<2>("tensor_swap", {a, b}, numel, count, true, [&](const Chunk<2>& c, dim3 grid) { OPTIM_LAUNCH(tensor_swap_kernel, c); });
 }

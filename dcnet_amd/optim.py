@@ -55,6 +55,23 @@ def _ptrs(addresses):
     return (ctypes.c_void_p * len(addresses))(*addresses)
 
 
+def _tables(live, keys, *more):
+    """The leading arguments of an update entry point for a group's ``live`` parameters: the pointer tables of the parameters, the
+    gradients, the state tensors named by ``keys`` and ``more`` (tables that follow the state's), the element counts, the count."""
+    n = len(live)
+    return (_ptrs([p.data_ptr() for p, _, _ in live]), _ptrs([g.data_ptr() for _, g, _ in live]),
+            *(_ptrs([st[k].data_ptr() for _, _, st in live]) for k in keys), *more, (ctypes.c_int64 * n)(*[p.numel() for p, _, _ in live]), n)
+
+
+def _call(L, name, args, ctl, stream) -> None:
+    """Entry point ``name`` of the library, or with a control block its ``_clipped`` form (``ctl`` in front of ``stream``); looked up
+    on ``L`` at the call."""
+    if ctl:
+        getattr(L, name + "_clipped")(*args, ctl, stream)
+    else:
+        getattr(L, name)(*args, stream)
+
+
 class _FusedOptimizer(torch.optim.Optimizer):
     """What the fused optimisers share: the device learning rates, the ``step`` bookkeeping and the walk over the groups.
     A subclass names its state in ``_new_state`` and launches one group's update in ``_launch``."""
@@ -261,14 +278,8 @@ class RMSprop(_FusedOptimizer):
         return {"step": torch.zeros((), dtype=torch.float32), "square_avg": torch.zeros_like(p, memory_format=torch.preserve_format)}
 
     def _launch(self, L, gi, group, live, lr_dev, ctl, stream):
-        n = len(live)
-        args = (_ptrs([p.data_ptr() for p, _, _ in live]), _ptrs([g.data_ptr() for _, g, _ in live]),
-                _ptrs([st["square_avg"].data_ptr() for _, _, st in live]), (ctypes.c_int64 * n)(*[p.numel() for p, _, _ in live]), n,
-                float(group["lr"]), lr_dev, float(group["alpha"]), float(group["eps"]), float(group["weight_decay"]))
-        if ctl:
-            L.rmsprop_step_clipped(*args, ctl, stream)
-        else:
-            L.rmsprop_step(*args, stream)
+        _call(L, "rmsprop_step", (*_tables(live, ("square_avg",)), float(group["lr"]), lr_dev, float(group["alpha"]), float(group["eps"]),
+                                  float(group["weight_decay"])), ctl, stream)
 
 
 class Adam(_FusedOptimizer):
@@ -339,33 +350,16 @@ class Adam(_FusedOptimizer):
     def _launch(self, L, gi, group, live, lr_dev, ctl, stream):
         self._check_group(group)
         tab = self._table(gi, group, live[0][0].device)
-        n = len(live)
         rows = [tab["index"][id(p)] for p, _, _ in live]
         s0, c0 = tab["steps"].data_ptr(), tab["scal"].data_ptr()
         scal = _ptrs([c0 + 4 * tab["scal"].shape[1] * r for r in rows])
         b1, b2 = (float(b) for b in group["betas"])
-        if group.get("decoupled_weight_decay"):
-            prep = (_ptrs([s0 + 4 * r for r in rows]), scal, n, float(group["lr"]), lr_dev, b1, b2, float(group["weight_decay"]))
-            args = (_ptrs([p.data_ptr() for p, _, _ in live]), _ptrs([g.data_ptr() for _, g, _ in live]),
-                    _ptrs([st["exp_avg"].data_ptr() for _, _, st in live]), _ptrs([st["exp_avg_sq"].data_ptr() for _, _, st in live]), scal,
-                    (ctypes.c_int64 * n)(*[p.numel() for p, _, _ in live]), n, b1, b2, float(group["eps"]))
-            if ctl:
-                L.adamw_prepare_clipped(*prep, ctl, stream)
-                L.adamw_step_clipped(*args, ctl, stream)
-            else:
-                L.adamw_prepare(*prep, stream)
-                L.adamw_step(*args, stream)
-            return
-        prep = (_ptrs([s0 + 4 * r for r in rows]), scal, n, float(group["lr"]), lr_dev, b1, b2)
-        args = (_ptrs([p.data_ptr() for p, _, _ in live]), _ptrs([g.data_ptr() for _, g, _ in live]),
-                _ptrs([st["exp_avg"].data_ptr() for _, _, st in live]), _ptrs([st["exp_avg_sq"].data_ptr() for _, _, st in live]), scal,
-                (ctypes.c_int64 * n)(*[p.numel() for p, _, _ in live]), n, b1, b2, float(group["eps"]), float(group["weight_decay"]))
-        if ctl:
-            L.adam_prepare_clipped(*prep, ctl, stream)
-            L.adam_step_clipped(*args, ctl, stream)
-        else:
-            L.adam_prepare(*prep, stream)
-            L.adam_step(*args, stream)
+        # weight_decay: AdamW's goes into the prepare launch (the third scalar), Adam's into the update
+        decoupled, wd = bool(group.get("decoupled_weight_decay")), (float(group["weight_decay"]),)
+        kind = "adamw" if decoupled else "adam"
+        _call(L, kind + "_prepare", (_ptrs([s0 + 4 * r for r in rows]), scal, len(live), float(group["lr"]), lr_dev, b1, b2, *(wd if decoupled else ())),
+              ctl, stream)
+        _call(L, kind + "_step", (*_tables(live, ("exp_avg", "exp_avg_sq"), scal), b1, b2, float(group["eps"]), *(() if decoupled else wd)), ctl, stream)
 
     def load_state_dict(self, state_dict) -> None:
         super().load_state_dict(state_dict)
@@ -413,14 +407,8 @@ class SGD(_FusedOptimizer):
         for p, _, st in live:
             if st.get("momentum_buffer") is None:        # (a state written by torch before the parameter's first step)
                 st["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-        n = len(live)
-        args = (_ptrs([p.data_ptr() for p, _, _ in live]), _ptrs([g.data_ptr() for _, g, _ in live]),
-                _ptrs([st["momentum_buffer"].data_ptr() for _, _, st in live]), (ctypes.c_int64 * n)(*[p.numel() for p, _, _ in live]), n,
-                float(group["lr"]), lr_dev, float(group["momentum"]), float(group["weight_decay"]))
-        if ctl:
-            L.sgd_step_clipped(*args, ctl, stream)
-        else:
-            L.sgd_step(*args, stream)
+        _call(L, "sgd_step", (*_tables(live, ("momentum_buffer",)), float(group["lr"]), lr_dev, float(group["momentum"]), float(group["weight_decay"])),
+              ctl, stream)
 
 
 def clip_grad_norm_(parameters, max_norm: float, norm_type: float = 2.0, error_if_nonfinite: bool = False):

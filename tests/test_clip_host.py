@@ -153,3 +153,22 @@ def test_new_entry_points_reject_bad_arguments_with_a_message():
     refused(L.adam_step_clipped, host, host, host, host, host, numel, 2, 0.9, 0.999, 1e-8, 0.0, 0, 0, match="control block")
     refused(L.adam_step_clipped, host, host, host, host, host, numel, 0, 0.9, 0.999, 1e-8, 0.0, some, 0, match="adam_step_clipped: bad argument")
     refused(L.adam_step_clipped, host, host, host, host, 0, numel, 2, 0.9, 0.999, 1e-8, 0.0, some, 0, match="adam_step_clipped: bad argument")
+
+
+def test_update_entry_points_check_every_tensor_before_the_first_launch():
+    """33 tensors — a second chunk of 32 — of 0 values each, a null gradient at index 32: the update entry points name tensor 32 and
+    launch nothing before they do (without a GPU a launch of the first chunk would fail with another text).  With 0 values per
+    tensor a launch that did happen would dereference nothing."""
+    from dcnet_amd.lib import DcnError, lib
+    L = lib()
+    n = 33
+    numel = (ctypes.c_int64 * n)(*([0] * n))
+    some = ctypes.addressof(numel)
+    host = (ctypes.c_void_p * n)(*([some] * n))
+    grads = (ctypes.c_void_p * n)(*([some] * (n - 1) + [None]))
+    for fn, args in ((L.rmsprop_step, (host, grads, host, numel, n, 1e-3, 0, 0.99, 1e-8, 0.0, 0)),
+                     (L.sgd_step, (host, grads, host, numel, n, 1e-3, 0, 0.9, 0.0, 0)),
+                     (L.adam_step, (host, grads, host, host, host, numel, n, 0.9, 0.999, 1e-8, 0.0, 0)),
+                     (L.adamw_step, (host, grads, host, host, host, numel, n, 0.9, 0.999, 1e-8, 0))):
+        with pytest.raises(DcnError, match="null tensor 32"):
+            fn(*args)

@@ -84,14 +84,20 @@ def test_fused_sgd_matches_torch(dev, wd):
     _agree(pa, pb, oa, ob, ("momentum_buffer",))
 
 
-@pytest.mark.parametrize("name", ["adam", "sgd"])
-def test_misaligned_views_round_like_aligned_tensors(dev, name):
+@pytest.mark.parametrize("clip", [None, 100.0])
+@pytest.mark.parametrize("name", ["rmsprop", "adam", "adamw", "sgd"])
+def test_misaligned_views_round_like_aligned_tensors(dev, name, clip):
     """The same values once in 16-byte-aligned tensors (the float4 path) and once as views one float into a flat buffer — parameter,
     gradient and state all 4-byte aligned, as gradients bound to a flat all-reduce buffer are — (the scalar path): bitwise equal
-    after 3 steps."""
+    after 3 steps, in the plain form of every update kernel and in the clipped one (``max_grad_norm`` = 100 against gradient norms of
+    several hundred: every step clips)."""
     from dcnet_amd import optim
     shapes = [(7,), (64, 33), (1,), (1024, 257), (40, 8, 3, 3)]
-    keys = ("exp_avg", "exp_avg_sq") if name == "adam" else ("momentum_buffer",)
+    keys = {"rmsprop": ("square_avg",), "adam": ("exp_avg", "exp_avg_sq"), "adamw": ("exp_avg", "exp_avg_sq"), "sgd": ("momentum_buffer",)}[name]
+    make = {"rmsprop": lambda q: optim.RMSprop(q, lr=1e-2, weight_decay=5e-4, max_grad_norm=clip),
+            "adam": lambda q: optim.Adam(q, lr=1e-2, weight_decay=5e-4, max_grad_norm=clip),
+            "adamw": lambda q: optim.AdamW(q, lr=1e-2, weight_decay=5e-4, max_grad_norm=clip),
+            "sgd": lambda q: optim.SGD(q, lr=1e-2, momentum=0.99, weight_decay=5e-4, max_grad_norm=clip)}[name]
     g = torch.Generator().manual_seed(7)
     init = [torch.randn(*s, generator=g) for s in shapes]
     grads = [[torch.randn(*s, generator=g) * (it + 1) for s in shapes] for it in range(3)]
@@ -105,16 +111,17 @@ def test_misaligned_views_round_like_aligned_tensors(dev, name):
 
     def run(place):
         ps = [torch.nn.Parameter(place(t)) for t in init]
-        make = (lambda q: optim.Adam(q, lr=1e-2, weight_decay=5e-4)) if name == "adam" else (lambda q: optim.SGD(q, lr=1e-2, momentum=0.99, weight_decay=5e-4))
         opt = make(ps)
         for p in ps:                 # the state the first step would create, placed like the parameter
             opt.state[p] = {k: place(torch.zeros(p.shape)) for k in keys}
-            if name == "adam":
+            if name != "sgd":
                 opt.state[p]["step"] = torch.zeros((), dtype=torch.float32)
         for it in range(3):
             for p, gr in zip(ps, grads[it]):
                 p.grad = place(gr)
             opt.step()
+            if clip is not None:     # (the clipped kernels ran, and with a coefficient below 1)
+                assert float(opt.grad_norm) > clip
         return ps, opt
 
     pa, oa = run(lambda t: t.clone().to(dev))
