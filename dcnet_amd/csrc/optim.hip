@@ -9,7 +9,8 @@
 // of the tensor is 16-byte aligned, scalar tail, grid-stride) and around it `update_walk` (tensor selection and the clipped form's
 // prologue), so an update kernel is its update function (`rms_update`, `adam_update`, `adamw_update`, `sgd_update`) in a lambda,
 // with the values of the launch and of the tensor (the device learning rate, Adam's scalars) read in front of the walk.  `walk2` is
-// the two-trips-at-once form of the two-stream passes (EMA, swap); `grad_sumsq_kernel` keeps its own four-deep loop.  On the host
+// the two-trips-at-once form of the two-stream passes (EMA, swap); `grad_sumsq_kernel` keeps its own four-deep loop; the gradient-
+// accumulation pass (`grad_accumulate_kernel`) is three lambdas on `walk`, chosen by a phase word on the device.  On the host
 // every entry point checks all its tensors (`check_tensors`) and then goes through one launcher (`launch_chunks`, on `for_chunks`).
 // A new optimiser is an update function, a kernel pair of a few lines and an entry-point pair.
 #include "common.h"
@@ -365,9 +366,8 @@ __device__ __forceinline__ float clip_coef(const float norm, const float max_nor
 
 // one workgroup of 1024: thread i adds slots i, i + 1024, ... — four running sums (trip k into sum k mod 4: four loads in flight, the
 // sum is latency-bound), folded in a fixed order — then the block sum; thread 0 writes the control block
-__global__ __launch_bounds__(1024) void grad_clip_coef_kernel(const double* __restrict__ partials, long long slots, float max_norm, int skip_nonfinite,
-                                                              float* __restrict__ ctl) {
-  __shared__ double red[16];
+__device__ __forceinline__ void clip_coef_body(const double* __restrict__ partials, long long slots, float max_norm, int skip_nonfinite,
+                                               float* __restrict__ ctl, double* red) {
   double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
   long long i = threadIdx.x;
   for (; i + 3 * 1024 < slots; i += 4 * 1024) {
@@ -386,6 +386,77 @@ __global__ __launch_bounds__(1024) void grad_clip_coef_kernel(const double* __re
   int* w = reinterpret_cast<int*>(ctl);
   w[CTL_APPLY] = apply;
   if (!apply) w[CTL_SKIPS] = w[CTL_SKIPS] + 1;
+}
+
+__global__ __launch_bounds__(1024) void grad_clip_coef_kernel(const double* __restrict__ partials, long long slots, float max_norm, int skip_nonfinite,
+                                                              float* __restrict__ ctl) {
+  __shared__ double red[16];
+  clip_coef_body(partials, slots, max_norm, skip_nonfinite, ctl, red);
+}
+
+// ---- gradient accumulation over K calls ---------------------------------------------------------------------------------------------
+// The accumulation block, four 32-bit words on the device (include/dcnet_hip.h, dcn_accum_prepare): [0] int32 pos, the calls made in
+// the open window (0 once a window has closed), [1] int32 phase of the current call, [2] float inv_k, [3] int32 windows closed.  Like
+// Adam's step words the position lives on the device, so a replayed step walks through the window without the host:
+// accum_prepare_kernel — one thread, in front of the pass — advances it; the pass and the gated coefficient kernel read the phase.
+constexpr int ACC_POS = 0, ACC_PHASE = 1, ACC_INV_K = 2, ACC_WINDOWS = 3;
+constexpr int ACC_FIRST = 0, ACC_MIDDLE = 1, ACC_BOUNDARY = 2, ACC_ALONE = 3;      // ALONE: a window of one call (k = 1), the gradient is the mean
+
+__global__ __launch_bounds__(64) void accum_prepare_kernel(int* __restrict__ blk, int k) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  const int pos = blk[ACC_POS] + 1;
+  const bool closes = pos >= k;
+  blk[ACC_POS] = closes ? 0 : pos;
+  blk[ACC_PHASE] = closes ? (pos == 1 ? ACC_ALONE : ACC_BOUNDARY) : (pos == 1 ? ACC_FIRST : ACC_MIDDLE);
+  reinterpret_cast<float*>(blk)[ACC_INV_K] = (float)(1.0 / k);
+  if (closes) blk[ACC_WINDOWS] = blk[ACC_WINDOWS] + 1;
+}
+
+// fp32 additions in call order, one final multiplication: ((g1 + g2) + ... + gK) * inv_k, every operation rounded once
+__device__ __forceinline__ float accum_add(const float acc, const float g) {
+#pragma clang fp contract(off)
+  return acc + g;
+}
+__device__ __forceinline__ float accum_mean(const float acc, const float g, const float inv_k) {
+#pragma clang fp contract(off)
+  const float s = acc + g;
+  return s * inv_k;
+}
+
+// (tables: 0 the accumulation buffer, 1 the gradient)  One walk per block, chosen by the phase — the same for every block of the
+// launch: first acc = g (acc is not read: 8 B per value), middle acc += g (12 B), boundary g = (acc + g) * inv_k (12 B; acc is not
+// written, the next window's first call overwrites it).  The walk's alignment test covers both pointers in every phase.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const Chunk<2> c, const int* __restrict__ blk) {
+  const int phase = blk[ACC_PHASE];           // (accum_prepare_kernel wrote it in the launch before this one)
+  const int t = blockIdx.y;
+  float* const acc[1] = {c.t[0][t]};
+  float* const g[1] = {c.t[1][t]};
+  const long long n = c.n[t];
+  if (phase == ACC_FIRST) {
+    walk<1, true>(acc, g[0], n, [](float (&a)[1], const float ge) { a[0] = ge; });
+  } else if (phase == ACC_MIDDLE) {
+    walk<1, true>(acc, g[0], n, [](float (&a)[1], const float ge) { a[0] = accum_add(a[0], ge); });
+  } else if (phase == ACC_BOUNDARY) {
+    const float inv_k = reinterpret_cast<const float*>(blk)[ACC_INV_K];
+    walk<1, true>(g, acc[0], n, [=](float (&a)[1], const float ae) { a[0] = accum_mean(ae, a[0], inv_k); });
+  }
+}
+
+// grad_clip_coef_kernel behind the window: off the boundary apply = 0 and nothing else is touched (norm, coefficient and skips keep
+// the last closed window's values), on it exactly what grad_clip_coef_kernel writes.  partials = NULL (no norm was asked for):
+// coef = 1, apply = boundary, launched with one wave.
+__global__ __launch_bounds__(1024) void accum_clip_coef_kernel(const double* __restrict__ partials, long long slots, float max_norm, int skip_nonfinite,
+                                                               const int* __restrict__ blk, float* __restrict__ ctl) {
+  __shared__ double red[16];
+  const int phase = blk[ACC_PHASE];
+  const bool boundary = phase == ACC_BOUNDARY || phase == ACC_ALONE;
+  if (!boundary || !partials) {
+    if (threadIdx.x != 0) return;
+    if (!partials) ctl[CTL_COEF] = 1.f;
+    reinterpret_cast<int*>(ctl)[CTL_APPLY] = boundary ? 1 : 0;
+    return;
+  }
+  clip_coef_body(partials, slots, max_norm, skip_nonfinite, ctl, red);
 }
 
 // (table 0: the gradients, scaled in place whatever `apply` says — the stand-alone clip_grad_norm_)
@@ -654,4 +725,32 @@ extern "C" int dcn_tensor_swap(float* const* a, float* const* b, const int64_t* 
   DCN_CHECK_ARG(count >= 0 && (count == 0 || (a && b && numel)), "tensor_swap: bad argument");
   if (const int e = check_tensors<2>("tensor_swap", {a, b}, numel, count, true)) return e;
   return launch_chunks<2>("tensor_swap", {a, b}, numel, count, true, [&](const Chunk<2>& c, dim3 grid) { OPTIM_LAUNCH(tensor_swap_kernel, c); });
+}
+
+// ---- gradient accumulation: the window's position, the pass, the gated coefficient --------------------------------------------------
+extern "C" int dcn_accum_prepare(void* accum, int k, void* stream) {
+  DCN_CHECK_ARG(accum, "accum_prepare: no accumulation block");
+  DCN_CHECK_ARG(k >= 1, "accum_prepare: k = %d, a window has at least one call", k);
+  hipLaunchKernelGGL(accum_prepare_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, (int*)accum, k);
+  DCN_CHECK_LAUNCH("accum_prepare");
+  return DCN_OK;
+}
+
+extern "C" int dcn_grad_accumulate(float* const* acc, float* const* grads, const int64_t* numel, int count, const void* accum, void* stream) {
+  DCN_CHECK_ARG(count >= 0 && (count == 0 || (acc && grads && numel)), "grad_accumulate: bad argument");
+  DCN_CHECK_ARG(accum, "grad_accumulate: no accumulation block");
+  if (const int e = check_tensors<2>("grad_accumulate", {acc, grads}, numel, count, true)) return e;
+  return launch_chunks<2>("grad_accumulate", {acc, grads}, numel, count, true,
+                          [&](const Chunk<2>& c, dim3 grid) { OPTIM_LAUNCH(grad_accumulate_kernel, c, (const int*)accum); });
+}
+
+extern "C" int dcn_accum_clip_coef(const double* partials, int64_t slots, float max_norm, int skip_nonfinite, const void* accum, void* ctrl,
+                                   void* stream) {
+  DCN_CHECK_ARG(ctrl && slots >= 0 && (partials != nullptr) == (slots > 0), "accum_clip_coef: bad argument");
+  DCN_CHECK_ARG(accum, "accum_clip_coef: no accumulation block");
+  DCN_CHECK_ARG(!partials || max_norm > 0.f, "accum_clip_coef: max_norm %g is not a positive number", (double)max_norm);
+  hipLaunchKernelGGL(accum_clip_coef_kernel, dim3(1), dim3(partials ? 1024 : 64), 0, (hipStream_t)stream, partials, (long long)slots, max_norm,
+                     skip_nonfinite, (const int*)accum, (float*)ctrl);
+  DCN_CHECK_LAUNCH("accum_clip_coef");
+  return DCN_OK;
 }

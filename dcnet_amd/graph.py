@@ -17,6 +17,13 @@ update (``dcnet_amd.optim``: RMSprop, Adam or SGD) — and replays them with one
 Data-parallel runs capture forward + backward only; the gradient all-reduce (one flat RCCL all-reduce,
 ``parallel.FlatGradAllReduce``) and the optimiser step follow the replay eagerly — no collective is captured.
 
+Gradient accumulation (``accum_steps = K`` of the fused optimisers) is part of the captured step: the window's position lives on the
+device, every replay launches the same kernels, and only every K-th one updates.  The warm-up steps and the capture pass are real
+calls and advance the window (``step.window_position``).  With a reducer the order after each replay is ``opt.accumulate()``, the
+reducer **only on the call that closes a window** (``opt.at_boundary``: ``.grad`` then holds the window mean, so the all-reduce runs once
+per window), ``opt.step()``.  Hook-based reducers and a DDP wrapper keep reducing every micro-step inside the backward — correct,
+because the mean is linear, but not optimised.
+
 ``grounding_model.freeze_batchnorm`` is respected as it stands: the setting survives the ``model.train()`` below, frozen layers run
 their frozen forward and backward inside the capture, their running statistics are not written.
 
@@ -103,6 +110,12 @@ class GraphedTrainStep:
         it synchronises.  With a reducer the optimiser steps after the all-reduce: every rank sees the norm of the averaged gradient."""
         return getattr(self.opt, "grad_norm", None)
 
+    @property
+    def window_position(self) -> int:
+        """Calls made in the optimiser's open accumulation window (0 ... ``accum_steps`` - 1; the warm-up steps and the capture pass
+        count): ``accum_steps - window_position`` more calls until the next update.  0 for an optimiser that does not accumulate."""
+        return getattr(self.opt, "window_position", 0)
+
     # ------------------------------------------------------------------------------------------------
     def _zero_grads(self):
         r = self.reducer
@@ -141,15 +154,22 @@ class GraphedTrainStep:
         if self.reducer is None:
             self.opt.step()
         elif eager:
-            self.reducer()
-            self.opt.step()
+            self._reduce_and_step()
         return loss.detach(), {k: v.detach() for k, v in parts.items()}
+
+    def _reduce_and_step(self):
+        """The data-parallel order behind a backward: this call's share of the accumulation window, the reducer where the call closes
+        a window (every call without accumulation), the optimiser step."""
+        if hasattr(self.opt, "accumulate"):
+            self.opt.accumulate()
+        if getattr(self.opt, "at_boundary", True) or getattr(self.reducer, "uses_parameter_hooks", False):
+            self.reducer()
+        self.opt.step()
 
     def _replay_device(self):
         self.graph.replay()
         if self.reducer is not None:
-            self.reducer()
-            self.opt.step()
+            self._reduce_and_step()
         elif hasattr(self.opt, "bump_steps") and self.replays > 0:
             self.opt.bump_steps()
         self.replays += 1

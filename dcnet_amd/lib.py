@@ -138,6 +138,9 @@ SIGNATURES = {
     "dcn_ema_prepare": (I, [P, P, D, D, P, P]),
     "dcn_ema_update": (I, [P, P, P, I, P, P, P]),
     "dcn_tensor_swap": (I, [P, P, P, I, P]),
+    "dcn_accum_prepare": (I, [P, I, P]),
+    "dcn_grad_accumulate": (I, [P, P, P, I, P, P]),
+    "dcn_accum_clip_coef": (I, [P, L, F, I, P, P, P]),
     "dcn_fusion_prefill": (I, [P, P, P, I, P, I, I, I, P]),
     "dcn_fusion_bwd_ws": (L, [I, I]),
     "dcn_fusion_bwd": (I, [P, P, P, P, P, P, P, I, I, I, I, I, P]),
@@ -195,7 +198,7 @@ _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap
                 "dcn_conv2d_stats_rows_b16", "dcn_bn_act_bwd_reduce_rows_b16", "dcn_conv2d_stats_rows_f8", "dcn_quant_fusable", "dcn_quant_job_bytes",
                 "dcn_conv1_tile", "dcn_l2norm_score_fwd_form", "dcn_bn_apply_form", "dcn_igemm_split_build", "dcn_gemm3_variant",
                 "dcn_coattn_bank_form"}
-ABI_VERSION = 317       # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
+ABI_VERSION = 318       # include/dcnet_hip.h DCN_ABI_VERSION this table was written for      # int-returning value functions
 
 
 class DcnError(RuntimeError):

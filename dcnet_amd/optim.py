@@ -34,6 +34,23 @@ RMSprop (whose ``step`` is bookkeeping only) subtracts the skips it has not yet 
 ``param.mul_(1 - lr * weight_decay)``, then Adam's update on the unmodified gradient (dcn_adamw_prepare + dcn_adamw_step; the factor
 is formed on the device, in double, from the step's learning rate).  Groups and ``state_dict`` are ``torch.optim.AdamW``'s.
 
+Gradient accumulation (constructor option ``accum_steps = K`` of all four classes; an attribute like ``max_grad_norm``, not a group
+key).  Every K consecutive ``step()`` calls form one window.  Calls 1 ... K-1 write only an fp32 accumulation buffer per live parameter
+(4 B per trained parameter): parameters, optimiser state, Adam's device step words, an attached EMA and its count keep their bits.  Call
+K forms the window's gradient ``G = (((g_1 + g_2) + g_3) ... + g_K) * fl32(1/K)`` — fp32 additions in call order, one multiplication,
+what K backward passes on ``loss / K`` accumulate to up to the rounding order — **writes it into the parameter's contiguous ``.grad``**
+(the one place where the fused step writes ``.grad``: a post-backward reducer, or a caller who looks at ``.grad``, sees the window
+mean) and applies the unchanged update to it.  Which call is which is decided on the device (dcn_accum_prepare advances a window
+position in a four-word accumulation block, dcn_grad_accumulate takes its phase from it, dcn_accum_clip_coef gates the ``_clipped``
+updates and the EMA through the clipping control block), so every call launches the same kernels on the same addresses and the whole
+of it replays as one hipGraph.  Clipping and the non-finite skip act on ``G``: one norm per window, ``opt.grad_norm`` keeps the last
+closed window's norm in between, a window whose ``G`` has a non-finite norm is skipped as a whole (one skip, EMA untouched) and the next
+one starts clean — call 1 overwrites the buffers.  The learning rate is read at call K; host ``step`` counters, schedules and
+``skipped_steps()`` are in units of updates.  The live set (the parameters that have a gradient) is fixed per window.  Buffers and
+position are not part of ``state_dict()``; ``load_state_dict()`` and ``reset_accumulation()`` put the window back to its start.  What
+accumulation does NOT emulate is a larger batch inside the model: BatchNorm's batch statistics and running-stat updates happen per
+micro-batch, the sampling heads draw once per micro-batch, the contrastive losses take their negatives from one micro-batch.
+
 ``WeightEMA`` keeps an exponential moving average of a model's weights and running statistics in shadow tensors, updated by two
 launches (dcn_ema_prepare + dcn_ema_update) that the fused optimisers append to their step (``opt.attach_ema(ema)``), so the update
 is part of the replayed training step and a ``skip_nonfinite`` step skips it too.  ``ema.swap()`` / ``with ema.applied():`` exchange
@@ -78,7 +95,9 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
     LR_RING = 4
 
-    def __init__(self, params, defaults, max_grad_norm=None, skip_nonfinite: bool = False):
+    def __init__(self, params, defaults, max_grad_norm=None, skip_nonfinite: bool = False, accum_steps: int = 1):
+        if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+            raise ValueError(f"accum_steps must be an integer >= 1, not {accum_steps!r}")
         if max_grad_norm is not None:
             if isinstance(max_grad_norm, bool) or not isinstance(max_grad_norm, (int, float)) or not (math.isfinite(max_grad_norm) and max_grad_norm > 0):
                 raise ValueError(f"max_grad_norm must be a finite number > 0 (or None), not {max_grad_norm!r}")
@@ -94,6 +113,11 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._stepped = []           # the "step" counters touched by the last step() (bump_steps: replays of a captured step)
         self._stepped_params = []    # ... and whose they are (load_state_dict replaces the counters)
         self._ema = None             # attach_ema: a WeightEMA whose update closes every step
+        self.accum_steps = accum_steps
+        self._accum = None           # {"block": the accumulation block, "ctrl": a control block of its own (no clipping), "bufs": {parameter: buffer}}
+        self._accum_pos = 0          # host mirror of the window position: step() calls made in the open window
+        self._accum_live = None      # the live set of the open window (ids of its parameters)
+        self._pending = None         # accumulate() ran since the last step(): the live lists it worked on
 
     def attach_ema(self, ema) -> None:
         """Make the end of every ``step()`` call ``ema.update(ctl)`` (a ``WeightEMA``; ``None`` detaches) with the address of the step's
@@ -134,9 +158,108 @@ class _FusedOptimizer(torch.optim.Optimizer):
             ent["last"] = lr
 
     def bump_steps(self) -> None:
-        """Advance the per-parameter ``step`` counters once more (a replay of a captured step ran the device update)."""
-        if self._stepped:
+        """Advance the per-parameter ``step`` counters once more (a replay of a captured step ran the device update).  With
+        ``accum_steps`` > 1 the replay was one call of the window: the host's window position advances, the counters only when the
+        replay closed a window — they count updates."""
+        if self._advance_window() and self._stepped:
             torch._foreach_add_(self._stepped, 1)
+
+    # ---- gradient accumulation ----------------------------------------------------------------------------------------------
+    @property
+    def window_position(self) -> int:
+        """``step()`` calls (or replays) made in the open accumulation window: 0 ... ``accum_steps`` - 1.  A host mirror of the
+        device's position; deterministic, because a skipped window still closes."""
+        return self._accum_pos
+
+    @property
+    def at_boundary(self) -> bool:
+        """True when the next ``step()`` (the current call, between ``accumulate()`` and ``step()``) closes a window: the call that
+        updates.  Always True with ``accum_steps`` = 1."""
+        return self._accum_pos == self.accum_steps - 1
+
+    def _advance_window(self) -> bool:
+        """One call of the window is done; returns whether it closed the window."""
+        closes = self.at_boundary
+        self._accum_pos = 0 if closes else self._accum_pos + 1
+        if closes:
+            self._accum_live = None
+        return closes
+
+    def reset_accumulation(self) -> None:
+        """Put the accumulation window back to its start, on the device and on the host: the next ``accum_steps`` calls form a fresh
+        window (its first call overwrites the buffers, so what an abandoned window gathered is never read).  Not during a capture."""
+        if self._accum is not None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"{self._name()}.reset_accumulation: not during a stream capture")
+            self._accum["block"][:2].zero_()             # position and phase (in place: a captured step keeps reading these words)
+        self._accum_pos, self._accum_live, self._pending = 0, None, None
+
+    def _collect(self):
+        """[(group index, group, live)] with ``live`` = (parameter, contiguous gradient, state) of every parameter of the group that
+        has a gradient; groups without one are left out."""
+        lives = []
+        for gi, group in enumerate(self.param_groups):
+            live = []
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
+                    raise RuntimeError(f"{self._name()}: contiguous fp32 CUDA parameters only (no CPU path)")
+                st = self.state[p]
+                if len(st) == 0:
+                    st.update(self._new_state(p))
+                # (a contiguous copy of the gradient may be freed right after the launch: same-stream reuse is ordered)
+                live.append((p, p.grad if p.grad.is_contiguous() else p.grad.contiguous(), st))
+            if live:
+                lives.append((gi, group, live))
+        return lives
+
+    @torch.no_grad()
+    def accumulate(self) -> None:
+        """This call's share of the window, over the live gradients of all groups (dcn_accum_prepare + dcn_grad_accumulate): calls
+        1 ... K-1 add ``.grad`` into the accumulation buffers, call K turns ``.grad`` into the window mean ``G``.  ``step()`` calls it
+        itself unless it was called since the last ``step()`` — which is what a data-parallel loop does to put its all-reduce between
+        the two: ``opt.accumulate()``, the reducer when ``opt.at_boundary``, ``opt.step()``.  (A non-contiguous ``.grad`` is accumulated
+        through a contiguous copy, which is then the tensor that holds ``G`` and that the update reads.)  Nothing with
+        ``accum_steps`` = 1."""
+        if self.accum_steps == 1:
+            return
+        if self._pending is not None:
+            raise RuntimeError(f"{self._name()}.accumulate: already called since the last step()")
+        lives = self._collect()
+        live_ids = tuple(id(p) for _, _, live in lives for p, _, _ in live)
+        if self._accum_pos == 0:
+            if not lives:
+                self._pending = []
+                return                   # nothing has a gradient: no window is opened
+        elif live_ids != self._accum_live:
+            raise RuntimeError(f"{self._name()}: the set of parameters that have a gradient changed inside an accumulation window (call "
+                               f"{self._accum_pos + 1} of {self.accum_steps}): the live set is fixed per window; reset_accumulation() abandons the window")
+        pairs = [(p, g) for _, _, live in lives for p, g, _ in live]
+        dev = pairs[0][0].device
+        if any(p.device != dev for p, _ in pairs):
+            raise RuntimeError(f"{self._name()}: accum_steps > 1 needs all parameters on one device (one window position)")
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._accum is None or self._accum["block"].device != dev:
+            if capturing:
+                raise RuntimeError(f"{self._name()}: the first accumulating step cannot be a captured one (its accumulation block and buffers "
+                                   "are allocated then); run an eager step first")
+            self._accum = {"block": torch.zeros(4, dtype=torch.int32, device=dev), "ctrl": torch.zeros(4, dtype=torch.int32, device=dev), "bufs": {}}
+        bufs = self._accum["bufs"]
+        for p, _ in pairs:
+            if p not in bufs:
+                if capturing:
+                    raise RuntimeError(f"{self._name()}: a parameter joined the accumulation inside a capture (its buffer is allocated at its "
+                                       "first eager accumulating step); run an eager window first")
+                bufs[p] = torch.empty_like(p, memory_format=torch.contiguous_format)
+        L = lib()
+        stream = torch.cuda.current_stream().cuda_stream
+        n = len(pairs)
+        L.accum_prepare(self._accum["block"].data_ptr(), self.accum_steps, stream)
+        L.grad_accumulate(_ptrs([bufs[p].data_ptr() for p, _ in pairs]), _ptrs([g.data_ptr() for _, g in pairs]),
+                          (ctypes.c_int64 * n)(*[g.numel() for _, g in pairs]), n, self._accum["block"].data_ptr(), stream)
+        self._accum_live = live_ids
+        self._pending = lives
 
     def _name(self) -> str:
         return f"dcnet_amd.optim.{type(self).__name__}"
@@ -165,7 +288,8 @@ class _FusedOptimizer(torch.optim.Optimizer):
         return 0 if self._clip_ws is None else int(self._clip_ws["ctrl"][3].item())
 
     def _norm_launches(self, L, grads, stream) -> int:
-        """The sum-of-squares launches over ``grads`` and the coefficient launch; returns the control block's address."""
+        """The sum-of-squares launches over ``grads`` and the coefficient launch (with ``accum_steps`` > 1 its gated form: the norm is
+        the window's, formed on the boundary call); returns the control block's address."""
         numel = [g.numel() for g in grads]
         key = (grads[0].device, tuple(numel))
         if any(g.device != key[0] for g in grads):
@@ -184,8 +308,11 @@ class _FusedOptimizer(torch.optim.Optimizer):
         n = len(numel)
         part = ws["partials"]
         L.grad_sumsq(_ptrs([g.data_ptr() for g in grads]), (ctypes.c_int64 * n)(*numel), n, part.data_ptr(), part.numel(), stream)
-        L.grad_clip_coef(part.data_ptr(), part.numel(), self.max_grad_norm if self.max_grad_norm is not None else math.inf,
-                         int(self.skip_nonfinite), ws["ctrl"].data_ptr(), stream)
+        max_norm = self.max_grad_norm if self.max_grad_norm is not None else math.inf
+        if self.accum_steps > 1:
+            L.accum_clip_coef(part.data_ptr(), part.numel(), max_norm, int(self.skip_nonfinite), self._accum["block"].data_ptr(), ws["ctrl"].data_ptr(), stream)
+        else:
+            L.grad_clip_coef(part.data_ptr(), part.numel(), max_norm, int(self.skip_nonfinite), ws["ctrl"].data_ptr(), stream)
         return ws["ctrl"].data_ptr()
 
     def _reconcile_steps(self) -> None:
@@ -217,45 +344,51 @@ class _FusedOptimizer(torch.optim.Optimizer):
                 self.sync_lr()           # an eager step always sees the groups' current learning rates (a captured one: sync_lr() before the replay)
             elif not self._lr_dev:
                 raise RuntimeError(f"{self._name()}: device_lr is set but sync_lr() was never called before the capture")
-        lives = []
-        for gi, group in enumerate(self.param_groups):
-            live = []
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                if not (p.is_cuda and p.dtype == torch.float32 and p.is_contiguous()):
-                    raise RuntimeError(f"{self._name()}: contiguous fp32 CUDA parameters only (no CPU path)")
-                st = self.state[p]
-                if len(st) == 0:
-                    st.update(self._new_state(p))
-                # (a contiguous copy of the gradient may be freed right after the launch: same-stream reuse is ordered)
-                live.append((p, p.grad if p.grad.is_contiguous() else p.grad.contiguous(), st))
-            if live:
-                lives.append((gi, group, live))
+        accumulating = self.accum_steps > 1
+        if accumulating:
+            # this call's share of the window first (unless the caller ran it already, to put a reducer between the two): on the
+            # boundary call .grad then holds the window mean, which is what the norm and the update read
+            if self._pending is None:
+                self.accumulate()
+            lives, self._pending = self._pending, None
+        else:
+            lives = self._collect()
         if not lives:
             return loss
         stream = torch.cuda.current_stream().cuda_stream
+        updates = self.at_boundary                 # (host bookkeeping only: every call launches the same kernels)
         ctl = 0
         if self.clipping:
             # ONE norm over the gradients of every group (what torch's function gives for model.parameters()), then the coefficient
             grads = [g for _, _, live in lives for _, g, _ in live if g.numel() > 0]
             if grads:
                 ctl = self._norm_launches(L, grads, stream)
+        if accumulating and not ctl:
+            # no norm was asked for (or every gradient is empty): the control block still gates the updates, with a coefficient of
+            # exactly 1 — g * 1.0f keeps g's bits, so the clipped update on the boundary is the plain one
+            ctl = self._accum["ctrl"].data_ptr()
+            L.accum_clip_coef(0, 0, math.inf, 0, self._accum["block"].data_ptr(), ctl, stream)
         for gi, group, live in lives:
             lr_dev = self._lr_dev[gi]["dev"].data_ptr() if self.device_lr else 0
             self._launch(L, gi, group, live, lr_dev, ctl, stream)
             for p, _, st in live:
                 if "step" in st:
-                    st["step"] += 1
+                    if updates:
+                        st["step"] += 1
                     self._stepped.append(st["step"]); self._stepped_params.append(p)
         if self._ema is not None:
             self._ema.update(ctl)
+        self._advance_window()
         return loss
 
     def load_state_dict(self, state_dict) -> None:
         """torch's, then: ``step`` counters as the host scalars torch's own default keeps (whatever device the writer had them on), and
-        the bookkeeping of ``bump_steps`` pointed at the counters that replaced the old ones."""
+        the bookkeeping of ``bump_steps`` pointed at the counters that replaced the old ones.  An open accumulation window is
+        abandoned (``reset_accumulation``): buffers and position are not part of a state."""
+        if self._accum is not None and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{self._name()}: load_state_dict during a stream capture cannot reset the accumulation window")
         super().load_state_dict(state_dict)
+        self.reset_accumulation()
         for st in self.state.values():
             if "step" in st:
                 st["step"] = torch.tensor(float(st["step"]), dtype=torch.float32)
@@ -266,13 +399,13 @@ class _FusedOptimizer(torch.optim.Optimizer):
 
 class RMSprop(_FusedOptimizer):
     def __init__(self, params, lr: float = 1e-2, alpha: float = 0.99, eps: float = 1e-8, weight_decay: float = 0.0,
-                 momentum: float = 0.0, centered: bool = False, max_grad_norm=None, skip_nonfinite: bool = False):
+                 momentum: float = 0.0, centered: bool = False, max_grad_norm=None, skip_nonfinite: bool = False, accum_steps: int = 1):
         if momentum != 0.0 or centered:
             raise NotImplementedError("dcnet_amd.optim.RMSprop implements momentum=0, centered=False (the reference's setting)")
         if lr < 0 or eps < 0 or alpha < 0 or weight_decay < 0:
             raise ValueError("invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, alpha=alpha, eps=eps, weight_decay=weight_decay, momentum=0.0, centered=False),
-                         max_grad_norm, skip_nonfinite)
+                         max_grad_norm, skip_nonfinite, accum_steps)
 
     def _new_state(self, p):
         return {"step": torch.zeros((), dtype=torch.float32), "square_avg": torch.zeros_like(p, memory_format=torch.preserve_format)}
@@ -297,7 +430,7 @@ class Adam(_FusedOptimizer):
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
                  amsgrad: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False,
-                 decoupled_weight_decay: bool = False):
+                 decoupled_weight_decay: bool = False, accum_steps: int = 1):
         if amsgrad or maximize:
             raise NotImplementedError(f"dcnet_amd.optim.{type(self).__name__} implements amsgrad=False, maximize=False (the reference's setting)")
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
@@ -305,7 +438,7 @@ class Adam(_FusedOptimizer):
         # (the keys and values of torch.optim.Adam's groups: a state_dict loaded into torch's class brings its groups along)
         super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                                       capturable=False, differentiable=False, fused=None, decoupled_weight_decay=bool(decoupled_weight_decay)),
-                         max_grad_norm, skip_nonfinite)
+                         max_grad_norm, skip_nonfinite, accum_steps)
         self._tables = {}            # group index -> device step words and scalar slots of the group's parameters
 
     def _new_state(self, p):
@@ -380,9 +513,9 @@ class AdamW(Adam):
     Groups and ``state_dict`` are ``torch.optim.AdamW``'s, so states load both ways."""
 
     def __init__(self, params, lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 1e-2,
-                 amsgrad: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False):
+                 amsgrad: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False, accum_steps: int = 1):
         super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize,
-                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, decoupled_weight_decay=True)
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, decoupled_weight_decay=True, accum_steps=accum_steps)
 
 
 class SGD(_FusedOptimizer):
@@ -390,13 +523,13 @@ class SGD(_FusedOptimizer):
     keeps no ``step`` in its state, and neither does this one: ``bump_steps()`` has nothing to advance."""
 
     def __init__(self, params, lr: float = 1e-3, momentum: float = 0.0, dampening: float = 0.0, weight_decay: float = 0.0,
-                 nesterov: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False):
+                 nesterov: bool = False, maximize: bool = False, max_grad_norm=None, skip_nonfinite: bool = False, accum_steps: int = 1):
         if dampening != 0 or nesterov or maximize:
             raise NotImplementedError("dcnet_amd.optim.SGD implements dampening=0, nesterov=False, maximize=False (the reference's setting)")
         if lr < 0 or momentum < 0 or weight_decay < 0:
             raise ValueError("invalid hyper-parameter")
         super().__init__(params, dict(lr=lr, momentum=momentum, dampening=0, weight_decay=weight_decay, nesterov=False, maximize=False,
-                                      foreach=None, differentiable=False, fused=None), max_grad_norm, skip_nonfinite)
+                                      foreach=None, differentiable=False, fused=None), max_grad_norm, skip_nonfinite, accum_steps)
 
     def _new_state(self, p):
         return {"momentum_buffer": torch.zeros_like(p, memory_format=torch.preserve_format)}

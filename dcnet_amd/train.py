@@ -29,7 +29,7 @@ from . import losses, ops
 
 
 def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: bool = True, max_grad_norm: Optional[float] = None,
-                   skip_nonfinite: bool = False):
+                   skip_nonfinite: bool = False, accum_steps: int = 1):
     """The optimiser the reference builds for ``--optimizer`` (train_DCNet.py:519-534).  ``model`` may be DDP-wrapped.
 
     ``"RMSprop"`` (the default): two groups, everything except the backbone at ``lr``, the Darknet backbone at ``lr / 10``; weight
@@ -46,11 +46,20 @@ def make_optimizer(model, lr: float = 1e-4, optimizer: str = "RMSprop", fused: b
     ``max_grad_norm`` / ``skip_nonfinite``: the fused classes' global-norm gradient clipping and non-finite skip, computed on the
     device inside the step (``dcnet_amd.optim``; the reference has neither).  One norm over all groups.  In a data-parallel run the
     optimiser steps after the gradient all-reduce, so every rank clips by the same norm of the same averaged gradient.  torch's
-    classes have no such step: with ``fused=False`` call ``dcnet_amd.optim.clip_grad_norm_`` before ``step()`` yourself."""
+    classes have no such step: with ``fused=False`` call ``dcnet_amd.optim.clip_grad_norm_`` before ``step()`` yourself.
+
+    ``accum_steps = K``: the fused classes' gradient accumulation — every K-th ``step()`` updates, with the mean gradient of the K
+    calls (``dcnet_amd.optim``; 4 B per trained parameter).  It raises the effective batch of the update only: BatchNorm's statistics,
+    the sampling heads' draws and the contrastive losses' negatives stay per micro-batch.  Fused classes only."""
     from . import optim
     core = model.module if hasattr(model, "module") else model
     name = optimizer.lower()
-    clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite)
+    clip = dict(max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, accum_steps=accum_steps)
+    if isinstance(accum_steps, bool) or not isinstance(accum_steps, int) or accum_steps < 1:
+        raise ValueError(f"make_optimizer: accum_steps must be an integer >= 1, not {accum_steps!r}")
+    if not fused and accum_steps != 1:
+        raise ValueError("make_optimizer: accum_steps belongs to the fused optimisers (fused=False: scale the loss by 1 / K and step "
+                         "every K-th backward yourself)")
     if not fused and (max_grad_norm is not None or skip_nonfinite):
         raise ValueError("make_optimizer: max_grad_norm / skip_nonfinite belong to the fused optimisers; with fused=False call "
                          "dcnet_amd.optim.clip_grad_norm_(model.parameters(), max_norm) before optimizer.step()")
@@ -171,6 +180,8 @@ def arg_parser() -> argparse.ArgumentParser:
     ap.add_argument("--raw-frames", action="store_true", help="feed uint8 frames through dcnet_amd.prep every step")
     ap.add_argument("--clip-grad-norm", type=float, default=None, metavar="X", help="clip the global gradient norm to X inside the fused step")
     ap.add_argument("--skip-nonfinite", action="store_true", help="a step whose gradient norm is inf or NaN updates nothing")
+    ap.add_argument("--accum-steps", type=int, default=1, metavar="K",
+                    help="accumulate gradients over K steps inside the fused step: --steps counts micro-steps, every K-th one updates, the schedule advances per update")
     ap.add_argument("--ema-decay", type=float, default=None, metavar="D",
                     help="keep an exponential moving average of the weights inside the fused step (dcnet_amd.optim.WeightEMA) and evaluate it too")
     ap.add_argument("--ema-tau", type=float, default=None, metavar="T", help="warm-up constant of the average: decay * (1 - exp(-t / T)); 0: none (default 2000)")
@@ -207,7 +218,8 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     fz = freeze_bn_args(args)
     if fz is not None:
         model.freeze_batchnorm(**fz)
-    opt = make_optimizer(model, args.lr, args.optimizer, max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite)
+    opt = make_optimizer(model, args.lr, args.optimizer, max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite,
+                         accum_steps=args.accum_steps)
     ema = None
     if ema_args(args) is not None:
         from .optim import WeightEMA
@@ -226,7 +238,8 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
         phrases = [["the object on the left"] * args.frames for _ in range(args.clips)]
         prep_rng = random.Random(1)               # the pipeline's own draws: Python's global stream stays the model's
     for it in range(args.steps):
-        adjust_learning_rate(opt, it, args.lr, args.steps, 0.9)
+        # the schedule is in units of updates: micro-step `it` belongs to update it // K of ceil(steps / K)
+        adjust_learning_rate(opt, it // args.accum_steps, args.lr, -(-args.steps // args.accum_steps), 0.9)
         if args.raw_frames:
             res = prepare_clips(frames, src_boxes, phrases, args.size, True, rng=prep_rng, out=image)
             bbox.copy_(res.bbox)

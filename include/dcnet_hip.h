@@ -39,7 +39,7 @@ extern "C" {
 /* Bumped whenever an exported signature changes incompatibly (round 2 changed dcn_conv2d_*, dcn_scale_act, dcn_bn_act_bwd_apply,
  * dcn_l2norm_score_*, dcn_prof_collect; round 3 dcn_rmsprop_step).  dcn_version() returns the value the library was built with;
  * dcnet_amd/lib.py refuses a library whose version differs from the one its signature table was written for. */
-#define DCN_ABI_VERSION 317
+#define DCN_ABI_VERSION 318
 
 const char* dcn_last_error(void);
 int dcn_version(void);
@@ -797,6 +797,31 @@ int dcn_ema_prepare(int* step, float* w, double decay, double tau, const void* c
 int dcn_ema_update(float* const* shadow, const float* const* src, const int64_t* numel, int count, const float* w, const void* ctrl,
                    void* stream);
 int dcn_tensor_swap(float* const* a, float* const* b, const int64_t* numel, int count, void* stream);
+/* Gradient accumulation over K calls inside the fused step (ABI 318; dcnet_amd/optim.py: accum_steps of the fused optimisers).  Every K
+ * consecutive calls form a window; its gradient is G = (((g_1 + g_2) + g_3) ... + g_K) * (float)(1.0 / K), fp32 additions in call order
+ * and one final multiplication, each rounded once.  The window's position lives on the device — a replayed hipGraph walks through the
+ * window without the host — in the accumulation block `accum`, four 32-bit words (the caller zeroes them once, when it allocates them;
+ * zeroing word [0] puts the window back to its start):
+ *   [0] int32 pos      calls made in the open window; 0 once a window has closed
+ *   [1] int32 phase    of the current call: 0 first, 1 middle, 2 boundary (the K-th call), 3 a window of one call (k = 1)
+ *   [2] float inv_k    (float)(1.0 / k)
+ *   [3] int32 windows  closed so far
+ * dcn_accum_prepare: one thread, called once per call of the window in front of the other two: pos + 1 -> phase (boundary when it
+ * reaches k), inv_k, and on the boundary pos = 0, windows + 1.  k >= 1.
+ * dcn_grad_accumulate: one streaming pass over `count` (accumulation buffer, gradient) pairs — host arrays of device pointers and
+ * element counts, 32 tensors per launch — by the block's phase: first acc = g (acc is not read: a window starts clean without a
+ * zeroing pass, 8 B per value), middle acc += g (12 B), boundary g = (acc + g) * inv_k (12 B; acc is not written): the gradient
+ * tensor then holds G.  Phase 3 touches nothing (g is G).  count = 0 and tensors of 0 values (whose pointers may be NULL) are
+ * accepted; a 4-byte-aligned view gives the bits of an aligned tensor.
+ * dcn_accum_clip_coef: dcn_grad_clip_coef behind the window, for the dcn_*_step_clipped entry points and dcn_ema_*: off the boundary
+ * apply = 0 and the other three words of `ctrl` keep the last closed window's values; on the boundary exactly what dcn_grad_clip_coef
+ * writes from `partials` (dcn_grad_sumsq over the gradients, after dcn_grad_accumulate).  partials = NULL with slots = 0 — no norm was
+ * asked for — gives coef = 1 and apply = 1 on the boundary, 0 off it (max_norm and skip_nonfinite are not looked at).
+ * Nothing synchronises. */
+int dcn_accum_prepare(void* accum, int k, void* stream);
+int dcn_grad_accumulate(float* const* acc, float* const* grads, const int64_t* numel, int count, const void* accum, void* stream);
+int dcn_accum_clip_coef(const double* partials, int64_t slots, float max_norm, int skip_nonfinite, const void* accum, void* ctrl,
+                        void* stream);
 /* Keys: "precision" 4 (default): the wide tiles of the conv engine and of the weight-gradient GEMM run the f16 two-piece
  *         split (see dcn_absmax) wherever both operands carry their abs-max word, and as 1 otherwise;
  *         1: the bf16 matrix pipe with every fp32 operand cut into three bf16 pieces (exact) and the six cross terms

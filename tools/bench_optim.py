@@ -1,7 +1,7 @@
 """The fused Adam / SGD steps (csrc/optim.hip) against torch's foreach steps, on the trained parameter shapes of the real model
 (synthetic weights, random gradients), alternating in one process:
 
-    python tools/bench_optim.py [--iters 20] [--warmup 3] [--step] [--clip | --ema] [--json out.json]
+    python tools/bench_optim.py [--iters 20] [--warmup 3] [--step] [--clip | --ema | --accum K] [--json out.json]
 
 Per optimiser one JSON line: ms per step of ``torch.optim.{Adam,SGD}(foreach=True)`` and of ``dcnet_amd.optim.{Adam,SGD}`` (HIP events
 around ``step()`` on a warm, otherwise idle GPU; medians over --iters, the two sides measured in turns), the bytes a step has to move
@@ -25,6 +25,12 @@ process, in --rounds rounds of --iters; per side the median of the round medians
 and the spread of the round medians.  The EMA pass and RMSprop are both pure streaming passes over the same tensor list, so the
 figure to read is ``ema_frac_minus_rmsprop_frac`` against ``frac_round_spread``.  With ``--step`` as well: the replayed RMSprop
 training step at configs[1]'s geometry without and with an attached EMA, two graphs alive in one process, alternating blocks.
+
+``--accum K`` times the gradient-accumulation pass instead (dcn_grad_accumulate) on the model's trained tensors: the pass in its first
+(8 B per value), middle and boundary phase (12 B), ``torch._foreach_add_`` on the same tensors (12 B) and dcn_ema_update on the same
+tensors (the file's other 12 B pass), measured in turns in one process, --rounds rounds of --iters; ms, TB/s and the spread of the
+round medians per side.  With ``--step`` as well: the replayed RMSprop training step at configs[1]'s geometry with ``accum_steps=1``
+and with ``accum_steps=K`` (ms per micro-step), two graphs alive in one process, alternating blocks.
 """
 from __future__ import annotations
 
@@ -260,6 +266,96 @@ def bench_train_step_ema(dev, size, clips, iters, warmup, rounds=3):
             "blocks_ms": {k: [round(x, 3) for x in v] for k, v in blocks.items()}}
 
 
+def bench_accum(dev, size, k, iters, warmup, rounds=3):
+    """The accumulation pass by phase (the phase word of a block of its own is set by hand: no prepare launch moves it), against
+    torch._foreach_add_ and dcn_ema_update over the same tensors — HIP events around each, measured in turns."""
+    import ctypes
+    from dcnet_amd.lib import lib
+    L = lib()
+    model = build_model(size, dev)
+    shapes = [tuple(p.shape) for p in model.parameters() if p.requires_grad]
+    del model
+    torch.cuda.empty_cache()
+    g = torch.Generator(device=dev).manual_seed(0)
+    draw = lambda scale: [torch.randn(s, device=dev, generator=g) * scale for s in shapes]
+    grads, acc, acc_t, shadow, src = draw(1e-3), draw(1e-3), draw(1e-3), draw(0.05), draw(0.05)
+    n_t = len(shapes)
+    ptrs = lambda ts: (ctypes.c_void_p * n_t)(*[t.data_ptr() for t in ts])
+    numel = (ctypes.c_int64 * n_t)(*[t.numel() for t in grads])
+    p_acc, p_g, p_sh, p_src = ptrs(acc), ptrs(grads), ptrs(shadow), ptrs(src)
+    inv_k = torch.tensor([1.0 / k], dtype=torch.float32).view(torch.int32).item()
+    blocks = {ph: torch.tensor([0, code, inv_k, 0], dtype=torch.int32, device=dev) for ph, code in (("first", 0), ("middle", 1), ("boundary", 2))}
+    w = torch.full((1,), 1e-4, dtype=torch.float32, device=dev)
+    stream = lambda: torch.cuda.current_stream().cuda_stream
+    sides = {"accum_" + ph: (lambda b=b: L.grad_accumulate(p_acc, p_g, numel, n_t, b.data_ptr(), stream())) for ph, b in blocks.items()}
+    sides["foreach_add"] = lambda: torch._foreach_add_(acc_t, grads)
+    sides["ema"] = lambda: L.ema_update(p_sh, p_src, numel, n_t, w.data_ptr(), 0, stream())
+    bytes_per_value = {"accum_first": 8, "accum_middle": 12, "accum_boundary": 12, "foreach_add": 12, "ema": 12}
+    for _ in range(warmup):
+        for fn in sides.values():
+            fn()
+    torch.cuda.synchronize()
+    n = sum(t.numel() for t in grads)
+    meds = {s_: [] for s_ in sides}
+    lo, hi = {s_: math.inf for s_ in sides}, {s_: 0.0 for s_ in sides}
+    for _ in range(rounds):
+        ts = {s_: [] for s_ in sides}
+        for _ in range(iters):
+            for s_, fn in sides.items():
+                ts[s_].append(_timed(fn))
+        for s_, v in ts.items():
+            meds[s_].append(statistics.median(v)); lo[s_] = min(lo[s_], min(v)); hi[s_] = max(hi[s_], max(v))
+    ms = {s_: statistics.median(v) for s_, v in meds.items()}
+    out = {"accum": k, "tensors": n_t, "values_M": round(n / 1e6, 2), "rounds": rounds, "iters": iters}
+    for s_ in sides:
+        out[s_ + "_ms"] = round(ms[s_], 4)
+        out[s_ + "_TBps"] = round(n * bytes_per_value[s_] / ms[s_] / 1e9, 3)
+    out["ema_round_spread_ms"] = round(max(meds["ema"]) - min(meds["ema"]), 4)
+    out["middle_minus_ema_ms"] = round(ms["accum_middle"] - ms["ema"], 4)
+    out["boundary_minus_ema_ms"] = round(ms["accum_boundary"] - ms["ema"], 4)
+    out["round_medians_ms"] = {s_: [round(x, 4) for x in v] for s_, v in meds.items()}
+    out["spread_ms"] = {s_: [round(lo[s_], 4), round(hi[s_], 4)] for s_ in sides}
+    return out
+
+
+def bench_train_step_accum(dev, size, clips, iters, warmup, k, rounds=3):
+    """The replayed RMSprop training step with ``accum_steps=1`` and with ``accum_steps=k``: two models, two graphs, alternating blocks
+    of ``iters`` micro-steps (``iters`` rounded up to whole windows; wall clock per micro-step, host-synchronised at both ends of a
+    block); per side the median over the blocks."""
+    from dcnet_amd.graph import GraphedTrainStep
+    from dcnet_amd.train import make_optimizer
+    from dcnet_amd.utils.synth import synth_boxes, synth_inputs
+    n = clips * 8
+    iters = -(-iters // k) * k
+    image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, size, seed=100))
+    bbox = synth_boxes(n, size, seed=100).to(dev)
+    steps = {}
+    for key, kk in (("accum1", 1), (f"accum{k}", k)):
+        random.seed(13)
+        model = build_model(size, dev)
+        steps[key] = GraphedTrainStep(model, make_optimizer(model, 1e-4, "rmsprop", accum_steps=kk), image, word_id, word_mask, bbox, size,
+                                      warmup=max(1, warmup))
+        for _ in range(warmup):
+            steps[key]()
+    torch.cuda.synchronize()
+    blocks = {k_: [] for k_ in steps}
+    for _ in range(rounds):
+        for key, step in steps.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(iters):
+                step()
+            torch.cuda.synchronize()
+            blocks[key].append((time.perf_counter() - t0) / iters * 1e3)
+    med = {k_: statistics.median(v) for k_, v in blocks.items()}
+    return {"geometry": f"{clips} clips x T 8 at {size}x{size}", "micro_steps_per_block": iters, "blocks": rounds, "accum": k,
+            "replayed_rmsprop_ms": round(med["accum1"], 3), f"replayed_rmsprop_accum{k}_ms_per_micro_step": round(med[f"accum{k}"], 3),
+            "accum_minus_plain_ms": round(med[f"accum{k}"] - med["accum1"], 3),
+            "block_spread_ms": {k_: round(max(v) - min(v), 3) for k_, v in blocks.items()},
+            "window_position": steps[f"accum{k}"].window_position, "loss": float(steps["accum1"].loss),
+            "blocks_ms": {k_: [round(x, 3) for x in v] for k_, v in blocks.items()}}
+
+
 def bench_train_step(dev, size, clips, iters, warmup):
     from dcnet_amd.graph import GraphedTrainStep
     from dcnet_amd.train import make_optimizer, train_step
@@ -296,7 +392,7 @@ def bench_train_step(dev, size, clips, iters, warmup):
     return out
 
 
-def main(argv=None):
+def arg_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
@@ -306,12 +402,33 @@ def main(argv=None):
     ap.add_argument("--step-iters", type=int, default=10)
     ap.add_argument("--clip", action="store_true", help="time gradient clipping: fused / fused + clip / torch foreach / torch clip + foreach")
     ap.add_argument("--ema", action="store_true", help="time the weight EMA: update / torch._foreach_lerp_ / rmsprop_kernel / swap on the model's tensors")
-    ap.add_argument("--rounds", type=int, default=3, help="--ema: rounds of --iters (the spread of their medians is reported)")
+    ap.add_argument("--rounds", type=int, default=3, help="--ema, --accum: rounds of --iters (the spread of their medians is reported)")
+    ap.add_argument("--accum", type=int, default=0, metavar="K",
+                    help="time the gradient-accumulation pass (first / middle / boundary) against torch._foreach_add_ and dcn_ema_update; with --step "
+                         "the replayed step with accum_steps=1 and accum_steps=K")
     ap.add_argument("--json", default="")
+    return ap
+
+
+def main(argv=None):
+    ap = arg_parser()
     a = ap.parse_args(argv)
-    if a.ema and a.clip:
-        ap.error("--ema and --clip are separate measurements")
+    if (a.ema + a.clip + (a.accum != 0)) > 1:
+        ap.error("--ema, --clip and --accum are separate measurements")
+    if a.accum < 0 or a.accum == 1:
+        ap.error("--accum K: K >= 2")
     dev = torch.device("cuda:0")
+    if a.accum:
+        rows = [bench_accum(dev, a.size, a.accum, a.iters, a.warmup, a.rounds)]
+        print(json.dumps(rows[-1]), flush=True)
+        torch.cuda.empty_cache()
+        if a.step:
+            rows.append(bench_train_step_accum(dev, a.size, a.clips, a.step_iters, a.warmup, a.accum, a.rounds))
+            print(json.dumps(rows[-1]), flush=True)
+        if a.json:
+            with open(a.json, "w") as fh:
+                json.dump(rows, fh, indent=1)
+        return
     if a.ema:
         rows = [bench_ema(dev, a.size, a.iters, a.warmup, a.rounds)]
         print(json.dumps(rows[-1]), flush=True)
