@@ -123,7 +123,8 @@ def conv_dgrad(dy, in_shape, ksize, stride, w=None, bank=None, out=None, accumul
     return res if tap is not None else (res, None)
 
 
-def schedule_wgrad(x, dy, ksize, stride, wshape, dgrad, amax_x=None, amax_dy=None, after=None, may_hold=False, direct_into=None):
+def schedule_wgrad(x, dy, ksize, stride, wshape, dgrad, amax_x=None, amax_dy=None, after=None, may_hold=False, direct_into=None,
+                   want_w=True):
     """Launch a layer's two gradients in the order of the schedule: ``dgrad()`` launches the data gradient on the current stream, the
     weight gradient of (x, dy) goes to the side stream (ops.WGRAD_SIDE off: the current one).  Returns (dgrad(), dw): dw the OIHW
     gradient — the caller joins the side stream (ops.join_side) before it is read —, but
@@ -131,7 +132,13 @@ def schedule_wgrad(x, dy, ksize, stride, wshape, dgrad, amax_x=None, amax_dy=Non
         gradient is held, to be added to ``.grad`` on the side stream behind the next block's passes; dw is None;
       * after False (the blocks that never had another order): the weight gradient first, beside its own data gradient;
       * after None = ops.WGRAD_AFTER_DGRAD: queued behind the data gradient, beside the next layer's BatchNorm passes — with
-        may_hold (the backbone) and ops.WGRAD_HELD as an ops.HeldWgrad the caller issues behind the next layer's passes."""
+        may_hold (the backbone) and ops.WGRAD_HELD as an ops.HeldWgrad the caller issues behind the next layer's passes;
+      * want_w False (the weight is frozen): no weight gradient at all, dw is None and nothing is held or handed to the side stream —
+        what the block before held still goes out at the place it would have (ops.WGRAD_DIRECT)."""
+    if not want_w:
+        if ops.WGRAD_DIRECT:
+            ops.release_held_wgrads()
+        return dgrad(), None
     if direct_into is not None:
         ops.release_held_wgrads()
         dx = dgrad()

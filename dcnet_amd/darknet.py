@@ -18,7 +18,7 @@ Reference: model/darknet.py:99-116 (cfg parser), :162-237 (module factory), :391
 from __future__ import annotations
 
 import os
-from typing import Dict, List, Optional, Sequence
+from typing import Dict, List, NamedTuple, Optional, Sequence
 
 import numpy as np
 import torch
@@ -166,7 +166,7 @@ def create_modules(module_defs: List[dict]):
 # ----------------------------------------------------------------------------------------------------
 
 class _ConvOp:
-    __slots__ = ("slot", "src", "dst", "res", "cin", "cout", "k", "stride", "bn", "leaky", "need_dx")
+    __slots__ = ("slot", "src", "dst", "res", "cin", "cout", "k", "stride", "bn", "leaky")
 
 
 class _UpCatOp:
@@ -232,7 +232,6 @@ def build_plan(module_defs: List[dict], in_channels: int = 3):
             op.cin = in_channels if i == 0 else ch[i - 1]; op.cout = int(d["filters"])
             op.k = int(d["size"]); op.stride = int(d["stride"])
             op.bn = bool(int(d["batch_normalize"])); op.leaky = d["activation"] == "leaky"
-            op.need_dx = i > 0
             nxt = module_defs[i + 1] if i + 1 < n else None
             if (nxt is not None and nxt["type"] == "shortcut" and live[i + 1] and consumers[i] == [i + 1]
                     and i not in taps):
@@ -262,6 +261,56 @@ def build_plan(module_defs: List[dict], in_channels: int = 3):
             op = _AliasOp(); op.dst = i; op.src = ls[0] if ls[0] >= 0 else i + ls[0]
             plan.append(op)
     return plan, taps, ch
+
+
+# ----------------------------------------------------------------------------------------------------
+# what the backward has to compute (requires_grad decides the work)
+# ----------------------------------------------------------------------------------------------------
+
+class ConvNeeds(NamedTuple):
+    """One conv op's share of the backward.  want_w: its weight gradient; want_affine: the gradient of gamma / beta (or of the conv
+    bias); want_dx: its data gradient; want_res: its output gradient is also the shortcut source's; live: the layer has a backward
+    pass of its own and keeps a record for it (any trainable parameter, or a gradient that goes through it to a trainable one)."""
+    want_w: bool
+    want_affine: bool
+    want_dx: bool
+    want_res: bool
+    live: bool
+
+
+class BackwardNeeds(NamedTuple):
+    """conv: {slot: ConvNeeds}; tensor: {tensor slot: is its gradient computed}; live: the slots that keep a record."""
+    conv: Dict[int, ConvNeeds]
+    tensor: Dict[int, bool]
+    live: frozenset
+
+
+def all_trainable(plan) -> frozenset:
+    """Every (slot, key) of the plan's convolutions: key "w", and "gamma" / "beta" (BatchNorm) or "b" (biased convolution)."""
+    return frozenset((op.slot, k_) for op in plan if isinstance(op, _ConvOp) for k_ in (("w", "gamma", "beta") if op.bn else ("w", "b")))
+
+
+def backward_needs(plan, trainable) -> BackwardNeeds:
+    """Pure function of the plan and the set of trainable (slot, key) pairs (all_trainable: the keys).  The gradient of a tensor is
+    computed only if its producer, or a producer upstream of it, has a trainable parameter; the image (tensor -1) never has one.  With
+    everything trainable that is the schedule there always was: every layer live, every gradient wanted, no data gradient for the stem."""
+    trainable = frozenset(trainable)
+    tensor: Dict[int, bool] = {-1: False}
+    conv: Dict[int, ConvNeeds] = {}
+    for op in plan:          # (plan order is topological: inputs come first)
+        if isinstance(op, _ConvOp):
+            want_w = (op.slot, "w") in trainable
+            want_affine = any((op.slot, k_) in trainable for k_ in ("gamma", "beta", "b"))
+            want_dx = tensor[op.src]
+            want_res = op.res is not None and tensor[op.res]
+            live = want_w or want_affine or want_dx
+            conv[op.slot] = ConvNeeds(want_w, want_affine, want_dx, want_res, live)
+            tensor[op.dst] = live or want_res
+        elif isinstance(op, _UpCatOp):
+            tensor[op.dst] = tensor[op.up_src] or tensor[op.lat_src]
+        else:
+            tensor[op.dst] = tensor[op.src]
+    return BackwardNeeds(conv, tensor, frozenset(s_ for s_, c_ in conv.items() if c_.live))
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -306,9 +355,16 @@ def _b16_diag_layer(diag, op, p, x, res, w, bank, act, out, amx):
     return x, (None if res is None else ops.to_b16(res)), False
 
 
-def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], banks=None, taps_b16: bool = False):
+def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], banks=None, taps_b16: bool = False, live=None,
+                 backward: Optional[bool] = None):
     """P[slot] = dict(w=OIHW weight, b=conv bias|None, gamma, beta, rm, rv).  Returns tap tensors.
-    banks (ops.FilterBanks, refreshed by the caller): the filter banks of all slots in their GEMM forms."""
+    banks (ops.FilterBanks, refreshed by the caller): the filter banks of all slots in their GEMM forms.
+    Two things that used to be one: ``backward`` — the forward takes the kernels of a pass that a backward may follow (PreAct
+    hand-over, the activation kept apart from the shortcut add; default: ``save is not None``) — and ``live`` — the slots that keep a
+    record in ``save`` (backward_needs; default: all).  A layer outside ``live`` runs the same kernels and keeps nothing; a tensor is
+    dropped behind its last reader, so what no record holds is gone by then."""
+    if backward is None:
+        backward = save is not None
     out: Dict[int, torch.Tensor] = {-1: x_nhwc}
     # abs-max word of every activation (ops.amax_*): written by the kernel that produces the tensor, read by the GEMMs
     # that consume it (forward here, weight gradient in the backward) to pick their power-of-two operand scales
@@ -321,15 +377,17 @@ def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], ba
     # (ops.pre_supported): they are handed on as ops.PreAct — no scale_act pass, no activation tensor
     readers: Dict[int, list] = {}
     f8_left: Dict[int, int] = {}          # fp8 storage: e4m3 readers of a tensor still to come (its attached copy is dropped after the last)
-    for op in plan:
+    last_reader: Dict[int, int] = {}
+    for i_op, op in enumerate(plan):
         for s_ in _inputs(op):
             if s_ is not None:
                 readers.setdefault(s_, []).append(op)
+                last_reader[s_] = i_op
 
     def sole_pre_reader(op, x):
         """the only reader of op's output, when that is a train-mode conv + BatchNorm whose kernels take the raw tensor"""
         rd = readers.get(op.dst, [])
-        if not (am and ops.PRE_ACT and training and save is not None and len(rd) == 1 and op.dst not in taps and op.res is None):
+        if not (am and ops.PRE_ACT and training and backward and len(rd) == 1 and op.dst not in taps and op.res is None):
             return False
         nx = rd[0]
         ho, wo = ops.conv_out_hw(x.shape[1], x.shape[2], op.k, op.stride)
@@ -381,16 +439,17 @@ def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], ba
                                               for r_ in readers.get(op.dst, []))
                 mi, o, ao = convblock.train_bn_forward(y, stats, p["gamma"], p["beta"], 1e-5, p["momentum"], p["rm"], p["rv"], act, 0.1,
                                                        residual=res, amax_out=ao, amax_y=ay, out_b16=s16, quant=q_)    # (s16: the stem's fp32 raw output -> bf16)
-                if save is not None:
+                if save is not None and (live is None or op.slot in live):
                     save[op.slot] = convblock.SavedLayer(x, y, w, bank, ax, aw, mi=mi)
             else:
                 fold, shift = ((p["gamma"], p["beta"], p["rm"], p["rv"], 1e-5), None) if op.bn else (None, p["b"])
-                if save is None:      # inference: one kernel per layer, shortcut fused in the epilogue
+                if not backward:      # inference: one kernel per layer, shortcut fused in the epilogue
                     o, _ = conv(fold=fold, shift=shift, act=act, slope=0.1, residual=res, amax_out=ao)
                 else:                 # frozen-BN fine-tuning: keep the pre-shortcut activation for act'
                     a, ss = conv(fold=fold, shift=shift, act=act, slope=0.1, amax_out=ao if res is None else None)
                     o = a if res is None else ops.scale_act(a, None, None, ops.ACT_NONE, 0.0, residual=res, amax_out=ao)
-                    save[op.slot] = convblock.SavedLayer(x, a, w, bank, ax, aw, scale=None if ss is None else ss[0])
+                    if save is not None and (live is None or op.slot in live):
+                        save[op.slot] = convblock.SavedLayer(x, a, w, bank, ax, aw, scale=None if ss is None else ss[0])
             if s16:
                 o = ops.to_b16(o)          # (the stem in inference: its fused epilogue wrote fp32)
             out[op.dst] = o; amx[op.dst] = ao
@@ -407,14 +466,23 @@ def _run_forward(plan, taps, x_nhwc, P, training: bool, save: Optional[dict], ba
             amx[op.dst] = ops.absmax(lat, ops.absmax(up)) if am else None
         else:
             out[op.dst] = out[op.src]; amx[op.dst] = amx.get(op.src)
+        x = res = None
+        for s_ in _inputs(op):       # behind its last reader a tensor belongs to the records that kept it (the taps: to the caller)
+            if s_ is not None and s_ >= 0 and last_reader[s_] == i_op and s_ not in taps:
+                out.pop(s_, None)
     # (taps_b16: the caller's first kernels read bf16 — grounding_model's mapping convolutions — so the taps stay as they are)
     return [ops.to_f32(out[t]) if (s16 and not taps_b16) else out[t] for t in taps], [amx.get(t) for t in taps], early_event
 
 
-def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bucket_bytes: int = 0):
+def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bucket_bytes: int = 0, trainable=None):
     """Hand-scheduled reverse sweep.  Returns {slot: dict(w=, b=, gamma=, beta=)} parameter grads.
     sink (optional): called with [(slot, key, tensor), ...] every time ``bucket_bytes`` of parameter gradients are final —
-    the data-parallel reducer starts their all-reduce while the sweep continues (parallel.OverlappedGradReducer)."""
+    the data-parallel reducer starts their all-reduce while the sweep continues (parallel.OverlappedGradReducer).
+    trainable: the (slot, key) pairs that want a gradient (default: all).  backward_needs turns it into the launches that are made:
+    nothing is computed for a frozen parameter, no gradient is formed (added, copied, upsampled, quantised) for a tensor that has no
+    trainable parameter upstream, and the sink sees the trainable gradients only."""
+    trainable = all_trainable(plan) if trainable is None else frozenset(trainable)
+    needs = backward_needs(plan, trainable)
     pending: list = []
     pending_bytes = 0
     g: Dict[int, Optional[torch.Tensor]] = {}
@@ -432,7 +500,7 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
             ops.copy_slice(t, cur, accumulate=True)
 
     for t, gt in zip(taps, grads_taps):
-        if gt is not None:
+        if gt is not None and needs.tensor[t]:
             g0 = gt.clone(memory_format=torch.contiguous_format)      # never accumulate into autograd's tensor
             add(t, ops.to_b16(g0) if s16 else g0)
     pg: Dict[int, dict] = {}
@@ -458,13 +526,20 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
             if sink is not None:
                 pending.append((slot_, "w", d_["w"])); pending_bytes += d_["w"].numel() * 4
 
+    def keep(d_):
+        """a kernel that forms gamma's and beta's sums forms both: the frozen one of the two is dropped here"""
+        for k_ in d_:
+            if (op.slot, k_) not in trainable:
+                d_[k_] = None
+        return d_
+
     def finished(slot, d):
         """the gradients of a layer are final (a held weight gradient follows through release): to the reducer's sink, bucket by bucket"""
         nonlocal pending, pending_bytes
         pg[slot] = d
         if sink is not None:
             for k_, t_ in d.items():
-                if t_ is not None:
+                if t_ is not None and (slot, k_) in trainable:
                     pending.append((slot, k_, t_)); pending_bytes += t_.numel() * 4
             if pending_bytes >= bucket_bytes:
                 sink(pending); pending = []; pending_bytes = 0
@@ -474,24 +549,34 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
         if dout is None:
             continue
         if isinstance(op, _AliasOp):
-            add(op.src, dout)
+            if needs.tensor[op.src]:
+                add(op.src, dout)
         elif isinstance(op, _UpCatOp):
             n, h2, w2, _ = dout.shape
             cur = g.get(op.up_src)
-            if cur is None:
+            if not needs.tensor[op.up_src]:
+                pass
+            elif cur is None:
                 cur = torch.empty((n, h2 // 2, w2 // 2, op.c_up), dtype=dout.dtype, device=dout.device)
                 ops.upsample2_bwd(dout[..., :op.c_up], cur, False)
                 g[op.up_src] = cur
             else:
                 ops.upsample2_bwd(dout[..., :op.c_up], cur, True)
-            add(op.lat_src, dout[..., op.c_up:])
+            if needs.tensor[op.lat_src]:
+                add(op.lat_src, dout[..., op.c_up:])
         else:
+            nd = needs.conv[op.slot]
+            if not nd.live:            # (nothing trainable in or below this layer: its output gradient is the shortcut source's, no more)
+                if nd.want_res:
+                    add(op.res, dout)
+                continue
             p = P[op.slot]
             rec = save.pop(op.slot)
             x, y = rec.x, rec.y
             act = ops.ACT_LEAKY if op.leaky else ops.ACT_NONE
             # the stem: nothing but its weight gradient reads dy, so dy is formed inside that kernel and never written
-            stem_fused = (op.bn and training and not op.need_dx and ops.STEM_FUSED_BWD and torch.is_tensor(x) and x.shape[3] == 4 and op.cout == 32
+            # (a frozen stem weight: the generic BatchNorm backward forms gamma's and beta's gradients, no weight-gradient kernel runs)
+            stem_fused = (op.bn and training and not nd.want_dx and nd.want_w and ops.STEM_FUSED_BWD and torch.is_tensor(x) and x.shape[3] == 4 and op.cout == 32
                           and op.k == 3 and op.stride == 1 and op.res is None and torch.is_tensor(y) and y.is_contiguous() and x.shape[2] >= 32)
             if s16 and torch.is_tensor(x) and x.dtype == torch.float32 and dout.dtype == torch.bfloat16 and not stem_fused:
                 dout = ops.to_f32(dout)           # bf16 storage: the 3-channel stem's generic kernels stay fp32 (its fused backward reads bf16 itself)
@@ -502,29 +587,29 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
                 dw, d["gamma"], d["beta"] = ops.stem_bwd_weight_bn(x, y, dout, rec.mi[0], rec.mi[1], p["gamma"], p["beta"], act, 0.1,
                                                                    part=tapped.pop(op.slot, None))
                 d["w"] = ops.weight_grad_to_oihw(dw, shape)
-                finished(op.slot, d)
+                finished(op.slot, keep(d))
                 continue
             if op.bn and training:
                 dy, d["gamma"], d["beta"] = ops.bn_act_bwd(y, dout, rec.mi[0], rec.mi[1], p["gamma"], p["beta"], act, 0.1, amax_out=ady,
                                                            part=tapped.pop(op.slot, None),
-                                                           quant=bool(op.need_dx) and ops.f8_takes(op.cout, op.cin, op.k))      # ("fp8s": dy's e4m3 copy for the data gradient)
+                                                           quant=nd.want_dx and ops.f8_takes(op.cout, op.cin, op.k))      # ("fp8s": dy's e4m3 copy for the data gradient)
             else:
                 # frozen statistics: y holds act(scale*conv+shift) before the shortcut add
                 if rec.scale is not None:       # folded BN: z = scale*conv + shift
                     dy, dgamma, d["beta"] = convblock.frozen_bn_backward(y, dout, rec.scale, p["gamma"], p["beta"], act, 0.1,
-                                                                         want_sums=p["affine_grad"])
+                                                                         want_sums=nd.want_affine)
                     d["gamma"] = dgamma          # (behind beta: the order in which the reducer's sink sees them)
                 else:
                     dy = ops.act_bwd(y, dout, 0.1) if op.leaky else dout
-                    if p["b"] is not None:
+                    if p["b"] is not None and nd.want_affine:
                         d["b"] = dy.reshape(-1, op.cout).sum(0)
                 ady = None            # (frozen-BN path: the GEMMs below compute the abs-max of dy themselves)
-            if op.res is not None:
+            if nd.want_res:
                 add(op.res, dout)
             release()                  # (behind this layer's BatchNorm passes: the main chain stays the first dependent of the data gradient before)
 
             def dgrad():
-                if not op.need_dx:
+                if not nd.want_dx:
                     return
                 cur = g.get(op.src)
                 b16 = s16 and dy.dtype == torch.bfloat16
@@ -541,12 +626,13 @@ def _run_backward(plan, taps, grads_taps, P, save, training: bool, sink=None, bu
                 if cur is None:
                     g[op.src] = dx
 
-            _, dw = convblock.schedule_wgrad(x, dy, op.k, op.stride, shape, dgrad, amax_x=rec.ax, amax_dy=ady, may_hold=True)
+            # (a frozen weight: the data gradient alone, nothing is handed to the side stream or held)
+            _, dw = convblock.schedule_wgrad(x, dy, op.k, op.stride, shape, dgrad, amax_x=rec.ax, amax_dy=ady, may_hold=True, want_w=nd.want_w)
             if isinstance(dw, ops.HeldWgrad):      # launched behind the next layer's BatchNorm passes (release)
                 held = (d, op.slot, dw)
             else:
                 d["w"] = dw
-            finished(op.slot, d)
+            finished(op.slot, keep(d))
     release()
     if sink is not None and pending:
         sink(pending)
@@ -567,22 +653,31 @@ class _DarknetFn(torch.autograd.Function):
         # (needs_input_grad speaks about the parameters, not about the caller's grad mode: under torch.no_grad() — inference — nothing is
         #  saved and every layer is ONE kernel with BatchNorm, activation and shortcut in its epilogue; forward_nhwc notes the mode, since
         #  inside a Function's forward grad mode is always off)
-        need_grad = any(ctx.needs_input_grad[3:]) and bool(net.__dict__.get("_grad_on", True))
+        # requires_grad decides the work (backward_needs): the layers that keep a record are those with a trainable parameter in or
+        # below them.  With no trainable parameter at all autograd sees no node here, and nothing is kept.
+        trainable = frozenset((slot, k_) for slot, d_ in P.items() for k_, on_ in d_["train"].items() if on_)
+        live = backward_needs(plan, trainable).live
+        grad_on = bool(net.__dict__.get("_grad_on", True))
+        need_grad = bool(live) and grad_on
         ctx.no_backward_reason = None if need_grad else "nothing was saved: the forward ran with gradients off (or no parameter requires one)"
         if ops.storage_f8() and not training and need_grad:
             need_grad = False          # fp8 storage has no frozen-BatchNorm backward: inference only with running statistics (backward() says so)
             ctx.no_backward_reason = ("fp8 storage has no backward with BatchNorm on its running statistics (eval mode, freeze_batchnorm): "
                                       "fp32 and bf16 storage (\"bf16s\") have it")
         save = {} if need_grad else None
+        # the kernels of the forward do not depend on what is frozen: batch statistics take the training forward whenever the caller
+        # has gradients on; running statistics with no backward to come (nothing trainable, or fp8 storage) take the inference forward
         outs, tap_amax, net._early_event = _run_forward(plan, taps, x, P, training, save, net._filter_banks(P),
-                                                        taps_b16=bool(net.__dict__.get("_taps_b16")))
+                                                        taps_b16=bool(net.__dict__.get("_taps_b16")), live=live,
+                                                        backward=need_grad or (training and grad_on))
         net._tap_amax = tap_amax              # abs-max words of the three taps (read by the head's first convolutions)
+        net.__dict__["saved_slots"] = frozenset(save) if save is not None else frozenset()
         if save is not None:
             for rec in save.values():
                 rec.unlink_outputs(outs)          # (outputs go through save_for_backward)
             ctx.save_for_backward(*outs)
         ctx.net, ctx.training, ctx.save, ctx.nflat = net, training, save, len(flat)
-        ctx.P = P
+        ctx.P, ctx.trainable = P, trainable
         return tuple(outs)
 
     @staticmethod
@@ -602,7 +697,8 @@ class _DarknetFn(torch.autograd.Function):
         if red is not None:
             pmap = net._slot_params()
             sink = lambda items: red.push([(pmap[(slot, key)], t) for slot, key, t in items if (slot, key) in pmap])
-        pg = _run_backward(net._plan, net._taps, grads, ctx.P, save, ctx.training, sink, red.bucket_bytes if red is not None else 0)
+        pg = _run_backward(net._plan, net._taps, grads, ctx.P, save, ctx.training, sink, red.bucket_bytes if red is not None else 0,
+                           trainable=ctx.trainable)
         if red is not None:
             red.join_backward()                        # the averaged gradients are complete before autograd sees them
         flat_grads: List[Optional[torch.Tensor]] = []
@@ -637,6 +733,7 @@ class Darknet(nn.Module):
         self.header_info = np.array([0, 0, 0, self.seen, 0], dtype=np.int32)
         self._plan, self._taps, self._ch = build_plan(self.module_defs, int(self.hyperparams["channels"]))
         self._conv_ops = [op for op in self._plan if isinstance(op, _ConvOp)]
+        self.saved_slots = frozenset()       # the slots whose layers kept a record for the backward in the last forward
 
     # -- parameter plumbing -------------------------------------------------------------------
     def _flat_params(self) -> List[torch.Tensor]:
@@ -659,17 +756,27 @@ class Darknet(nn.Module):
         for op in self._conv_ops:
             seq = self.module_list[op.slot]
             d = dict(w=next(it).detach(), b=None, gamma=None, beta=None, rm=None, rv=None, momentum=0.1, affine_grad=True)
-            next(nd)
+            d["train"] = {"w": bool(next(nd))}          # which of the layer's parameters want a gradient (backward_needs)
             if op.bn:
                 bn = seq[1]
                 d["gamma"], d["beta"] = next(it).detach(), next(it).detach()
-                d["affine_grad"] = bool(next(nd)) | bool(next(nd))      # (frozen statistics: False = no partial sums in the backward)
+                d["train"]["gamma"], d["train"]["beta"] = bool(next(nd)), bool(next(nd))
+                d["affine_grad"] = d["train"]["gamma"] | d["train"]["beta"]      # (frozen statistics: False = no partial sums in the backward)
                 d["rm"], d["rv"], d["momentum"] = bn.running_mean, bn.running_var, bn.momentum
             else:
                 d["b"] = next(it).detach()
-                next(nd)
+                d["train"]["b"] = bool(next(nd))
             P[op.slot] = d
         return P
+
+    def trainable_keys(self) -> frozenset:
+        """The (slot, key) pairs of the live convolutions whose parameter has ``requires_grad`` now (the argument of backward_needs)."""
+        return frozenset(k_ for k_, p_ in self._slot_params().items() if p_.requires_grad)
+
+    def backward_needs(self) -> BackwardNeeds:
+        """What a backward through this module would launch with the parameters' ``requires_grad`` as it stands (darknet.backward_needs).
+        After a forward ``saved_slots`` holds the slots that kept a record for it: ``backward_needs().live`` with gradients on."""
+        return backward_needs(self._plan, self.trainable_keys())
 
     def _slot_params(self):
         """{(slot, "w" | "gamma" | "beta" | "b"): parameter} of the live convolutions."""

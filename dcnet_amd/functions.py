@@ -96,10 +96,13 @@ class ConvBNAct(torch.autograd.Function):
 
         # (ops.WGRAD_DIRECT: the block before's weight gradient goes out behind this block's passes, this one's is added to .grad on the
         #  side stream: no join here)
-        dx, dwt = convblock.schedule_wgrad(x, dy, ksize, 1, wshape, dgrad, amax_x=ax, amax_dy=ady, direct_into=ctx.wparam)
-        if ctx.wparam is None:
+        # requires_grad decides the work: a frozen weight launches no weight gradient (and joins no side stream for one)
+        want_w = ctx.needs_input_grad[1]
+        dx, dwt = convblock.schedule_wgrad(x, dy, ksize, 1, wshape, dgrad, amax_x=ax, amax_dy=ady, direct_into=ctx.wparam, want_w=want_w)
+        if ctx.wparam is None and want_w:
             ops.join_side(x.device)
-        return dx, dwt, dgamma, dbeta, None, None, None, None, None, None, None, None
+        return (dx, dwt, dgamma if ctx.needs_input_grad[2] else None, dbeta if ctx.needs_input_grad[3] else None,
+                None, None, None, None, None, None, None, None)
 
 
 class ConvBias(torch.autograd.Function):
@@ -136,7 +139,8 @@ class ConvBias(torch.autograd.Function):
         co, ci, k, _ = ctx.wshape
         ax, aw = ctx.amax
         dy = dy.contiguous()
-        rowsum = lambda: ops.colsum_rows(dy.view(-1, dy.shape[-1]))[:co]
+        want_w, want_b = ctx.needs_input_grad[1], ctx.needs_input_grad[2]      # (frozen: no weight gradient, no bias row sum)
+        rowsum = lambda: ops.colsum_rows(dy.view(-1, dy.shape[-1]))[:co] if want_b else None
         if ctx.b16:
             db = rowsum()                  # (of the fp32 gradient)
             dy, ady = ops.to_b16(dy), None
@@ -154,8 +158,9 @@ class ConvBias(torch.autograd.Function):
             return convblock.conv_dgrad(dy, x.shape, k, 1, w=w, bank=bank, out_f32=ctx.x_f32, amax_dy=ady, amax_w=aw)[0]
 
         # (ops.WGRAD_DIRECT: added to .grad on the side stream, no join here)
-        dx, dwt = convblock.schedule_wgrad(x, dy, k, 1, ctx.wshape, dgrad, amax_x=ax, amax_dy=ady, after=False, direct_into=ctx.wparam)
-        if ctx.wparam is None:
+        dx, dwt = convblock.schedule_wgrad(x, dy, k, 1, ctx.wshape, dgrad, amax_x=ax, amax_dy=ady, after=False, direct_into=ctx.wparam,
+                                           want_w=want_w)
+        if ctx.wparam is None and want_w:
             ops.join_side(x.device)
         return dx, dwt, db, None
 
@@ -324,15 +329,17 @@ class HeadTail(torch.autograd.Function):
         dM, gout, dmom = ops.locbn_bwd(M, mom, b_lt, g_lt, rmean_lt, saved, dMp, dbp, training, cnt)
         dM2 = dM.view(B * 8, -1)
         dX = ops.gemm_nn(dM2, wp)                                            # (B*8, Ppad)
-        dwp = ops.gemm_tn(dM2, X)                                            # (512, Ppad)
-        dw_lt = ops.pad_rows(dwp, P)
+        dw_lt = None
+        if ctx.needs_input_grad[12]:                                         # (loc_text_embedding's weight; frozen: no product)
+            dwp = ops.gemm_tn(dM2, X)                                        # (512, Ppad)
+            dw_lt = ops.pad_rows(dwp, P)
         dobj, dE_b = ops.head_fold(dX, e8, obj_map)
         dlogits, dsim = ops.head_dlogits(logits, sims, loc, only, d_out, d_only, obj_map, objn, dobj)
         g88 = ops.locemb_bwd(coord, w_le, g_le, be_le, xh, stat, dE_a, dE_b, dmom, training)
         shp = [t.shape for t in logits]
         dsim = [d.view(s_[0], s_[1], s_[2]) for d, s_ in zip(dsim, shp)]
         return (*dlogits, *dsim, dq_loc, None, g88[:64].view(8, 8), g88[64:72], g88[72:80], g88[80:88],
-                dw_lt.view(ctx.wshape), gout[2], gout[0], gout[1], None, None, None)
+                None if dw_lt is None else dw_lt.view(ctx.wshape), gout[2], gout[0], gout[1], None, None, None)
 
 
 class InterframeSample(torch.autograd.Function):
@@ -507,14 +514,21 @@ class FusionConvBNAct(torch.autograd.Function):
             bank = {"tb16": wk.t().contiguous().reshape(-1)} if ctx.b16 else None
             return convblock.conv_dgrad(dy, corr.shape, 1, 1, w=wk, bank=bank, out_f32=True, amax_dy=ady, amax_w=aw)[0]
 
-        dcorr, dw1 = convblock.schedule_wgrad(corr, dy, 1, 1, (co, e, 1, 1), dgrad, amax_x=ax, amax_dy=ady, after=False)
-        ops.join_side(corr.device)
+        want_w = ctx.needs_input_grad[3]
+        dcorr, dw1 = convblock.schedule_wgrad(corr, dy, 1, 1, (co, e, 1, 1), dgrad, amax_x=ax, amax_dy=ady, after=False, want_w=want_w)
+        if want_w:
+            ops.join_side(corr.device)
+        dgamma, dbeta = (dgamma if ctx.needs_input_grad[4] else None), (dbeta if ctx.needs_input_grad[5] else None)
+        if not (want_w or ctx.needs_input_grad[1]):
+            return dcorr, None, None, None, dgamma, dbeta, None, None, None
         # gradients of the per-image / per-position terms: one pass over dy (d_img, dW3), dW2 = d_img^T.flang, dflang = d_img.W2
+        # (a frozen weight with a trainable language branch: the pass still runs for d_img; its dW2 / dW3 go nowhere)
         dweight = torch.empty((co, wd.shape[1]), dtype=torch.float32, device=dy.device)
         d_img = ops.fusion_bwd(ops.to_f32(dy), ctx.coord2d, flang.detach().contiguous(), dweight, e)      # (the terms read fp32)
-        ops.copy_slice(dw1.view(co, e), dweight[:, :e])
+        if want_w:
+            ops.copy_slice(dw1.view(co, e), dweight[:, :e])
         dflang = ops.gemm_nn(d_img, wd[:, e:2 * e]) if ctx.needs_input_grad[1] else None
-        return dcorr, dflang, None, dweight.view_as(weight), dgamma, dbeta, None, None, None
+        return dcorr, dflang, None, dweight.view_as(weight) if want_w else None, dgamma, dbeta, None, None, None
 
 
 class CoAttentionPairs(torch.autograd.Function):
@@ -617,8 +631,8 @@ class LinearAct(torch.autograd.Function):
         if ctx.relu:
             dz = ops.act_bwd(out, dz, 0.0)
         dx = ops.gemm_nn(dz, weight.detach()) if ctx.needs_input_grad[0] else None
-        dw = ops.gemm_tn(dz, x)
-        db = ops.colsum(dz) if ctx.has_bias else None
+        dw = ops.gemm_tn(dz, x) if ctx.needs_input_grad[1] else None          # (requires_grad decides: a frozen weight / bias costs nothing)
+        db = ops.colsum(dz) if (ctx.has_bias and ctx.needs_input_grad[2]) else None
         return dx, dw, db, None
 
 
@@ -654,7 +668,7 @@ class BatchNormRowsAct(torch.autograd.Function):
         else:
             dx, dgamma, dbeta = convblock.frozen_bn_backward(a, dout, aux[0], gamma, beta, act, 0.0,
                                                              want_sums=ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
-        return dx, dgamma, dbeta, None, None, None
+        return dx, dgamma if ctx.needs_input_grad[1] else None, dbeta if ctx.needs_input_grad[2] else None, None, None, None
 
 
 class Embedding(torch.autograd.Function):
@@ -702,16 +716,19 @@ class BiLSTM(torch.autograd.Function):
         n, L, I, H = ctx.dims
         det = [p.detach().contiguous() for p in params]
         dxg = ops.bilstm_bwd(dout.contiguous(), det[1], det[5], acts, cprev, lens)
-        dx = torch.empty((n * L, I), dtype=torch.float32, device=x2d.device)
+        need = ctx.needs_input_grad          # (x, lengths, then the eight parameters: a product is launched only for what wants a gradient)
+        dx = torch.empty((n * L, I), dtype=torch.float32, device=x2d.device) if need[0] else None
         grads = []
         for d in range(2):
             g2 = dxg[d].view(n * L, 4 * H)
-            dw_ih = ops.gemm_tn(g2, x2d)
-            dw_hh = ops.gemm_tn(g2, hprev[d].view(n * L, H))                # sum over (row, time) of dgates^T . h_before
-            ops.gemm_nn(g2, det[4 * d], out=dx, accumulate=(d == 1))
-            db = ops.rows_sum(g2)
-            grads += [dw_ih, dw_hh, db, db]
-        return (dx.view(n, L, I), None) + tuple(grads)
+            w_ih, w_hh, b_ih, b_hh = need[2 + 4 * d:6 + 4 * d]
+            dw_ih = ops.gemm_tn(g2, x2d) if w_ih else None
+            dw_hh = ops.gemm_tn(g2, hprev[d].view(n * L, H)) if w_hh else None   # sum over (row, time) of dgates^T . h_before
+            if need[0]:
+                ops.gemm_nn(g2, det[4 * d], out=dx, accumulate=(d == 1))
+            db = ops.rows_sum(g2) if (b_ih or b_hh) else None
+            grads += [dw_ih, dw_hh, db if b_ih else None, db if b_hh else None]
+        return (None if dx is None else dx.view(n, L, I), None) + tuple(grads)
 
 
 class LocModule(torch.autograd.Function):

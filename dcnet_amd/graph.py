@@ -24,6 +24,9 @@ reducer **only on the call that closes a window** (``opt.at_boundary``: ``.grad`
 per window), ``opt.step()``.  Hook-based reducers and a DDP wrapper keep reducing every micro-step inside the backward — correct,
 because the mean is linear, but not optimised.
 
+``grounding_model.freeze_weights`` is respected the same way: the captured backward is the reduced one of the parameters that were trainable
+at the capture, and a call after the set changed raises.
+
 ``grounding_model.freeze_batchnorm`` is respected as it stands: the setting survives the ``model.train()`` below, frozen layers run
 their frozen forward and backward inside the capture, their running statistics are not written.
 
@@ -97,6 +100,8 @@ class GraphedTrainStep:
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
             self.loss, self.parts = self._body(eager=False)
         self.graph = g
+        # requires_grad decided which kernels were captured (grounding_model.freeze_weights, freeze_batchnorm(train_affine=False)): fixed from here
+        self._trainable = self._trainable_now()
         ops._amax_pools.pop(dev.index, None)                  # the capture's private abs-max pool stays with the graph
         self.replays = 0
         # the capture pass itself does not execute kernels: run it once so that state (parameters, running statistics) is that
@@ -117,6 +122,9 @@ class GraphedTrainStep:
         return getattr(self.opt, "window_position", 0)
 
     # ------------------------------------------------------------------------------------------------
+    def _trainable_now(self):
+        return tuple(p_.requires_grad for p_ in self.core.parameters())
+
     def _zero_grads(self):
         r = self.reducer
         if r is not None and getattr(r, "bound", False):
@@ -177,6 +185,10 @@ class GraphedTrainStep:
     def __call__(self):
         """One optimisation step.  Returns the (static) loss tensor of the step — reading it synchronises."""
         t0 = time.perf_counter()
+        if self._trainable_now() != self._trainable:
+            raise RuntimeError("GraphedTrainStep: the set of trainable parameters changed after the capture (freeze_weights, freeze_batchnorm(train_affine="
+                               "False) or requires_grad_): the captured step launches the backward of the set it was captured with; build a new "
+                               "GraphedTrainStep")
         if hasattr(self.opt, "sync_lr"):
             self.opt.sync_lr()
         t1 = time.perf_counter()

@@ -263,16 +263,79 @@ class grounding_model(nn.Module):
         ``.grad`` None, no partial sums in the backward); freeze_batchnorm(None) — or another call — gives them back.  Returns self."""
         if scope not in ("backbone", "all", None):
             raise ValueError(f"freeze_batchnorm: scope {scope!r}: expected 'backbone', 'all' or None")
-        for p_ in self.__dict__.pop("_bn_affine_off", []):
-            p_.requires_grad_(True)
+        given_back = self.__dict__.pop("_bn_affine_off", [])
         self.__dict__["_bn_scope"] = scope
         self.visumodel.freeze_batchnorm(scope is not None)
+        affine = []
         if scope is not None and not train_affine:
-            off = [p_ for m in self._frozen_bn_modules() for p_ in (m.weight, m.bias) if p_ is not None and p_.requires_grad]
-            for p_ in off:
-                p_.requires_grad_(False)
+            affine = [p_ for m in self._frozen_bn_modules() for p_ in (m.weight, m.bias) if p_ is not None]
+        self._hand_over(given_back, "_fw_scope", "_fw_off")        # (what freeze_weights holds too goes to its list, the rest trains again)
+        self.__dict__["_bn_affine_scope"] = {id(p_) for p_ in affine}
+        off = [p_ for p_ in affine if p_.requires_grad]
+        for p_ in off:
+            p_.requires_grad_(False)
+        # (a parameter freeze_weights switched off earlier is held by both from now on: an undo of either leaves it to the other)
+        if off:
             self.__dict__["_bn_affine_off"] = off
         return self.train(self.training)
+
+    def _hand_over(self, params, other_scope: str, other_off: str) -> None:
+        """Give back the parameters one of freeze_weights / freeze_batchnorm(train_affine=False) had switched off: those inside the
+        OTHER one's scope move to its list (they stay off, and its undo restores them), the rest get requires_grad back."""
+        scope = self.__dict__.get(other_scope, set())
+        for p_ in params:
+            if id(p_) in scope:
+                self.__dict__.setdefault(other_off, []).append(p_)
+            else:
+                p_.requires_grad_(True)
+
+    def freeze_weights(self, scope="backbone"):
+        """Partial fine-tuning: stop training the parameters in ``scope`` — convolution weights and biases, BatchNorm gamma and beta,
+        whatever else the scope holds (``requires_grad`` False, ``.grad`` None) — and with that the work for them: ``requires_grad``
+        decides which weight gradients, bias and BatchNorm sums and data gradients the backward launches and which layers keep anything
+        for it (darknet.backward_needs).  A frozen prefix of the backbone costs no backward and no storage.
+        scope: "backbone" (all of ``visumodel``); an int k (``visumodel.module_list[0..k]``: 74 is the Darknet-53 feature extractor, the
+        neck — modules 75-102 — keeps training); an iterable of parameter-name prefixes (``["visumodel", "textmodel"]``); None (undo).
+        This does NOT touch how BatchNorm normalises: a frozen layer on batch statistics still normalises with them and still updates
+        its running statistics, as torch does for a module whose parameters have requires_grad False.  The usual pairing is
+        ``freeze_batchnorm("backbone")`` (running statistics, left alone; with both, fp8 storage can train the rest of the model:
+        a backbone that is frozen whole has no backward).  Undo restores exactly what this call switched off — not what parallel.freeze_gradless,
+        freeze_batchnorm(train_affine=False) or the caller had switched off.  A second call replaces the first.  Returns self."""
+        named = list(self.named_parameters())
+        if scope is None:
+            chosen = []
+        elif isinstance(scope, str):
+            if scope != "backbone":
+                raise ValueError(f"freeze_weights: scope {scope!r}: expected 'backbone', an int, an iterable of parameter-name prefixes or None")
+            chosen = [p_ for n_, p_ in named if n_.startswith("visumodel.")]
+        elif isinstance(scope, bool):
+            raise ValueError(f"freeze_weights: scope {scope!r}: expected 'backbone', an int, an iterable of parameter-name prefixes or None")
+        elif isinstance(scope, int):
+            n_mod = len(self.visumodel.module_list)
+            if not 0 <= scope < n_mod:
+                raise ValueError(f"freeze_weights: scope {scope}: visumodel.module_list has modules 0..{n_mod - 1}")
+            chosen = [p_ for i_ in range(scope + 1) for p_ in self.visumodel.module_list[i_].parameters()]
+        else:
+            try:
+                prefixes = list(scope)
+            except TypeError:
+                prefixes = None
+            if not prefixes or not all(isinstance(x_, str) and x_ for x_ in prefixes):
+                raise ValueError(f"freeze_weights: scope {scope!r}: expected 'backbone', an int, an iterable of parameter-name prefixes or None")
+            hit = lambda n_, x_: n_ == x_ or n_.startswith(x_.rstrip(".") + ".")
+            for x_ in prefixes:
+                if not any(hit(n_, x_) for n_, _ in named):
+                    raise ValueError(f"freeze_weights: no parameter name starts with {x_!r}")
+            chosen = [p_ for n_, p_ in named if any(hit(n_, x_) for x_ in prefixes)]
+        given_back = self.__dict__.pop("_fw_off", [])
+        self._hand_over(given_back, "_bn_affine_scope", "_bn_affine_off")
+        self.__dict__["_fw_scope"] = {id(p_) for p_ in chosen}
+        off = [p_ for p_ in chosen if p_.requires_grad]
+        for p_ in off:
+            p_.requires_grad_(False)
+        if off:
+            self.__dict__["_fw_off"] = off
+        return self
 
     def _frozen_bn_modules(self):
         scope = self.__dict__.get("_bn_scope")

@@ -11,7 +11,8 @@ to drive ``grounding_model`` without the reference's data pipeline (SURVEY.md §
 ``--ema-decay D`` / ``--ema-tau T`` keep an exponential moving average of the weights inside the fused step (``dcnet_amd.optim.WeightEMA``);
 the closing evaluation then reports the raw and the averaged weights.
 
-``python -m dcnet_amd.train --steps 20`` (``--freeze-bn backbone|all``: BatchNorm on its running statistics) runs a short synthetic-data training loop on one GPU; with ``--raw-frames`` every step's
+``python -m dcnet_amd.train --steps 20`` (``--freeze-bn backbone|all``: BatchNorm on its running statistics; ``--freeze-weights backbone|K``:
+the backbone, or its modules 0..K, not trained and without a backward) runs a short synthetic-data training loop on one GPU; with ``--raw-frames`` every step's
 ``image`` / ``bbox`` come from synthetic uint8 frames of mixed sizes (1280x720 and 500x375) through the on-device clip
 preprocessing (``dcnet_amd.prep.prepare_clips``: flip, HSV, letterbox, affine, normalisation), as real decoded frames would.
 """
@@ -189,7 +190,25 @@ def arg_parser() -> argparse.ArgumentParser:
                     help="hold BatchNorm at its running statistics while training (grounding_model.freeze_batchnorm): the backbone's, or every one")
     ap.add_argument("--freeze-bn-stats-only", action="store_true",
                     help="with --freeze-bn: freeze the statistics only, gamma and beta keep training (train_affine=True; default: they are frozen too)")
+    ap.add_argument("--freeze-weights", type=freeze_weights_scope, default=None, metavar="{none,backbone,K}",
+                    help="stop training the backbone (grounding_model.freeze_weights): all of it, or its modules 0..K (74: the Darknet-53 feature "
+                         "extractor, the neck keeps training); frozen layers cost no backward and keep nothing for one.  Usually with --freeze-bn backbone")
     return ap
+
+
+def freeze_weights_scope(text: str):
+    """--freeze-weights: "none" -> None, "backbone", or an integer module index (the scope argument of grounding_model.freeze_weights)."""
+    if text == "none":
+        return None
+    if text == "backbone":
+        return text
+    try:
+        k = int(text)
+    except ValueError:
+        k = -1
+    if k < 0:
+        raise argparse.ArgumentTypeError(f"{text!r}: expected none, backbone or a module index >= 0")
+    return k
 
 
 def freeze_bn_args(args) -> Optional[dict]:
@@ -218,6 +237,8 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
     fz = freeze_bn_args(args)
     if fz is not None:
         model.freeze_batchnorm(**fz)
+    if args.freeze_weights is not None:
+        model.freeze_weights(args.freeze_weights)
     opt = make_optimizer(model, args.lr, args.optimizer, max_grad_norm=args.clip_grad_norm, skip_nonfinite=args.skip_nonfinite,
                          accum_steps=args.accum_steps)
     ema = None

@@ -153,6 +153,7 @@ def main():
     ap.add_argument("--out", required=True, help="directory of the trace files")
     args = ap.parse_args()
     os.makedirs(args.out, exist_ok=True)
+    import torch  # noqa: F401  (before the library loads: both must end up on the HIP runtime torch brings, as in every other entry point)
     tracer = Tracer()
     runs = [None] + [(kv.split("=")[0], ast.literal_eval(kv.split("=", 1)[1])) for kv in args.switches.split(";") if kv]
     for sw in runs:

@@ -32,7 +32,8 @@ ROOT = os.path.dirname(HERE)
 
 def _clock(torch):
     """MHz: the device's current shader clock where the runtime reports it, and its maximum"""
-    out = {"max_mhz": round(torch.cuda.get_device_properties(0).clock_rate / 1e3)}
+    khz = getattr(torch.cuda.get_device_properties(0), "clock_rate", None)          # (not every torch build exposes it)
+    out = {"max_mhz": None if khz is None else round(khz / 1e3)}
     try:
         out["now_mhz"] = int(torch.cuda.clock_rate())
     except Exception:
