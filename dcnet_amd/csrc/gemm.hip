@@ -80,7 +80,8 @@ extern "C" int dcn_gemm_nt(const float* A, int lda, const float* B, int ldb, flo
                            const float* bias, int act, const float* residual, int ldr, int accumulate, void* stream) {
   DCN_CHECK_ARG(A && B && C && M > 0 && N > 0 && K > 0 && K % 32 == 0, "gemm_nt: bad argument (K=%d must be a multiple of 32)", K);
   IgemmParams p; gemm_params(p, A, lda, B, ldb, C, ldc, M, N, K);
-  p.shift = bias; p.act = act; p.slope = 0.f; p.residual = residual; p.ldr = ldr > 0 ? ldr : ldc; p.accumulate = accumulate;
+  p.shift = bias; p.act = act; p.slope = 0.f; p.residual = residual; p.ldr = ldr > 0 ? ldr : ldc;
+  p.accumulate = accumulate; p.acc_post = 1;      // the old C is added to the finished value, after bias / activation / residual
   return igemm_launch(p, (hipStream_t)stream);
 }
 

@@ -42,6 +42,7 @@ struct IgemmParams {
   int cpt, kiters;        // filled by igemm_launch: K-steps per tap / in total for the chosen K-step size
   int act; float slope;
   int accumulate, dense_out, c4;
+  int acc_post;           // with accumulate: the old destination is added to the finished value (after act / residual), not to the raw accumulator
   int tap_dy[IGEMM_MAX_TAPS], tap_dx[IGEMM_MAX_TAPS], tap_w[IGEMM_MAX_TAPS];
   // ncls = 4: four sub-problems (the parity classes of a stride-2 data gradient) in one launch; class c has M / Hs / Ws / oy0 /
   // ox0 / ntaps below and its taps at tap_*[4c ...]; M, ntaps above then hold the largest class (tile and grid sizing)

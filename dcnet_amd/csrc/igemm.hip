@@ -510,8 +510,8 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgemmParams p) {
   // ---- epilogue ----------------------------------------------------------------------------
   // (0) accumulate: the destination's current content joins the RAW accumulator, i.e. before the
   //     statistics and before scale/shift/activation (dX += ..., or a pre-filled per-image/per-position
-  //     bias term of the fusion layer).
-  if (p.accumulate) {
+  //     bias term of the fusion layer).  With acc_post (dcn_gemm_nt) it is added to the finished value in (b) instead.
+  if (p.accumulate && !p.acc_post) {
     const int hsws0 = Hs_ * Ws_;
 #pragma unroll
     for (int mi = 0; mi < MI; ++mi) {
@@ -595,6 +595,7 @@ __global__ __launch_bounds__(256, OCC) void igemm_kernel(const IgemmParams p) {
         float v = acc[mi][ni][r] * rs * sc[ni] + sh[ni];
         if (p.act == DCN_ACT_LEAKY) v = v > 0.f ? v : v * p.slope;
         if (p.residual) v += p.residual[pix * p.ldr + co_[ni]];
+        if (p.accumulate && p.acc_post) v += gout[pix * p.ldo + co_[ni]];
         gout[pix * p.ldo + co_[ni]] = v;
         vmax = fmaxf(vmax, fabsf(v));
       }
