@@ -563,39 +563,47 @@ class CoAttentionPairs(torch.autograd.Function):
         return df.view(n, h, w, c), None
 
 
-class CoAttentionCenter(torch.autograd.Function):
-    """Centre-frame co-attention of the inference model (model/test_DCNet_model.py:247-282):
-    f1 = centre frame, f2 = another frame of the clip; only f1_attn is consumed.
-    clips (B,T,HW,C); returns [f1 | f1_attn] (B,HW,2C).
-    Backward (the reference's train branch of this model, test_DCNet_model.py:480-483, reachable though its scripts never take it): the
-    pair kernels of dcn_coattn_bwd with a zero gradient for the unused f2_attn; the result lands in frames ``ctr`` and ``idx`` of a
-    clips-shaped gradient (autograd sums the T - 1 of them)."""
+def coattn_center_cat(clips, ctr: int, idx: int, temperature: float):
+    """Centre-frame co-attention of the inference model (model/test_DCNet_model.py:247-282), forward only: f1 = centre frame,
+    f2 = frame ``idx`` of the clip; only f1_attn is consumed.  clips (B,T,HW,C); returns [f1 | f1_attn] (B,HW,2C).  No autograd node:
+    where a gradient is required the whole window goes through CoAttentionWindow."""
+    b, t, hw, c = clips.shape
+    cat = torch.empty((b, hw, 2 * c), dtype=torch.float32, device=clips.device)
+    cat[..., :c].copy_(clips[:, ctr])        # batch-strided source: plain torch copy
+    ops.coattn_fwd(clips[:, ctr], clips[:, idx], cat[..., c:], None, temperature)
+    return cat
+
+
+class CoAttentionWindow(torch.autograd.Function):
+    """Centre-versus-neighbours co-attention of a whole window (the train branch of the n_frame model, model/test_DCNet_model.py:259-274,
+    480-483) as ONE node per scale on csrc/coattn_center.hip: clips (B,T,HW,C), unit norm over C; returns cat (T-1,B,HW,2C) whose slice n
+    is [f_ctr | attn_n] for the n-th frame != ctr, contiguous per neighbour (take the slices with ``unbind(0)``: its backward is one
+    stack, where T-1 ``cat[n]`` would each return a zero-filled cat-sized gradient).
+    Backward: one (B,T,HW,C) gradient — the centre's rows are pre-filled with the sum of the pass-through halves and collect every
+    neighbour's dA . f_j inside the call, each neighbour's rows are written by that neighbour alone; nothing is zero-filled."""
 
     @staticmethod
-    def forward(ctx, clips, ctr: int, idx: int, temperature: float):
+    def forward(ctx, clips, ctr: int, temperature: float):
+        clips = clips.contiguous()
         b, t, hw, c = clips.shape
-        cat = torch.empty((b, hw, 2 * c), dtype=torch.float32, device=clips.device)
-        cat[..., :c].copy_(clips[:, ctr])        # batch-strided source: plain torch copy
-        ctx.meta = (ctr, idx, temperature)
+        cat = torch.empty((t - 1, b, hw, 2 * c), dtype=torch.float32, device=clips.device)
+        cat[..., :c].copy_(clips[:, ctr].unsqueeze(0).expand(t - 1, b, hw, c))       # batch-strided source: plain torch copy
+        E, rinv = ops.coattn_center_fwd(clips, ctr, cat[..., c:], temperature)
+        ctx.meta = (ctr, temperature)
         if ctx.needs_input_grad[0]:
-            o2 = torch.empty((b, hw, 2 * c), dtype=torch.float32, device=clips.device)[..., c:]      # f2_attn (strides of out1): only the backward's bookkeeping reads it
-            E, rc = ops.coattn_fwd(clips[:, ctr], clips[:, idx], cat[..., c:], o2, temperature)
-            ctx.save_for_backward(clips, cat, o2, E, rc)
-        else:
-            ops.coattn_fwd(clips[:, ctr], clips[:, idx], cat[..., c:], None, temperature)
+            ctx.save_for_backward(clips, cat, E, rinv)
         return cat
 
     @staticmethod
     def backward(ctx, g):
-        clips, cat, o2, E, rc = ctx.saved_tensors
-        ctr, idx, temperature = ctx.meta
-        b, t, hw, c = clips.shape
+        clips, cat, E, rinv = ctx.saved_tensors
+        ctr, temperature = ctx.meta
+        c = clips.shape[3]
         g = g.contiguous()
-        d = torch.zeros_like(clips)
-        d[:, ctr].copy_(g[..., :c])              # the pass-through half of the concat
-        z2 = torch.zeros((b, hw, 2 * c), dtype=torch.float32, device=g.device)[..., c:]        # d f2_attn = 0, in the strides of d f1_attn
-        ops.coattn_bwd(clips[:, ctr], clips[:, idx], g[..., c:], z2, cat[..., c:], o2, E, rc, d[:, ctr], d[:, idx], True, temperature)
-        return d, None, None, None
+        d = torch.empty_like(clips)
+        torch.sum(g[..., :c], dim=0, out=d[:, ctr])          # the pass-through halves of the T-1 concats
+        ops.coattn_center_bwd(clips, ctr, g[..., c:], cat[..., c:], E, rinv, d, True, temperature)
+        return d, None, None
 
 
 class ToNCHW(torch.autograd.Function):

@@ -30,6 +30,12 @@ at the capture, and a call after the set changed raises.
 ``grounding_model.freeze_batchnorm`` is respected as it stands: the setting survives the ``model.train()`` below, frozen layers run
 their frozen forward and backward inside the capture, their running statistics are not written.
 
+``n_frame = K`` captures the step of the WINDOW model instead (``model(image, word_id, word_mask, K)``, ``losses.window_loss``):
+``image`` is (B * K, 3, S, S), ``word_id`` (B, L), ``bbox`` (B, 4), the boxes of the centre frames.  That model has no sampling heads, so
+there are no sample buffers and nothing is drawn on the host.  The two step-level reorderings that belong to the pair forward — the
+deferred language backward and the head's direct weight gradients — stay off: a window step is exactly ``train.train_step(..., n_frame=K)``.
+Optimiser protocol, reducer order, accumulation window, frozen weights / BatchNorm and the trainable-set check are those of the pair step.
+
 Everything else is unchanged: the same kernels in the same order on the same streams, so a replayed step is bitwise equal to
 an eager one (tests/test_graph_gpu.py).
 """
@@ -44,16 +50,23 @@ from . import losses, ops
 
 
 class GraphedTrainStep:
-    """``step = GraphedTrainStep(model, optimizer, image, word_id, word_mask, bbox, size)`` then ``loss = step()`` per iteration.
+    """``step = GraphedTrainStep(model, optimizer, image, word_id, word_mask, bbox, size[, n_frame=K])`` then ``loss = step()`` per iteration.
 
     ``image``/``word_id``/``word_mask``/``bbox`` become the static inputs (``step.image.copy_(new)`` to feed new data of the same
     shape).  ``reducer``: a callable run after the replayed backward and before the optimiser step (data-parallel gradient
     averaging); with a reducer the optimiser step runs eagerly after it.  ``warmup`` eager steps are run first (they populate the
     library's caches: geometry tables, scratch buffers, function attributes) — they ARE training steps (parameters move)."""
 
-    def __init__(self, model, optimizer, image, word_id, word_mask, bbox, size: int, reducer=None, warmup: int = 2):
+    def __init__(self, model, optimizer, image, word_id, word_mask, bbox, size: int, reducer=None, warmup: int = 2,
+                 n_frame: Optional[int] = None):
+        if n_frame is not None:
+            if isinstance(n_frame, bool) or not isinstance(n_frame, int) or n_frame < 2:
+                raise ValueError(f"GraphedTrainStep: n_frame must be an integer >= 2 (a centre frame and its neighbours), not {n_frame!r}")
+            if image.shape[0] % n_frame:
+                raise ValueError(f"GraphedTrainStep: a batch of {image.shape[0]} images is not a multiple of n_frame = {n_frame}")
         if not image.is_cuda:
             raise RuntimeError("GraphedTrainStep: HIP only (no CPU path)")
+        self.n_frame = n_frame
         self.model, self.opt, self.size, self.reducer = model, optimizer, size, reducer
         self.core = model.module if hasattr(model, "module") else model
         self._hooked = (self.core is not model or getattr(reducer, "uses_parameter_hooks", False)
@@ -62,10 +75,11 @@ class GraphedTrainStep:
         self.image, self.word_id, self.bbox = image.clone(), word_id.clone(), bbox.clone()
         self.word_mask = None if word_mask is None else word_mask.clone()
         self.n = image.shape[0]
-        self.samples = self.core.sample_buffers(self.n, dev)
+        # (the window model has no sampling heads: no buffers, no draws)
+        self.samples = self.core.sample_buffers(self.n, dev) if n_frame is None else None
         # grounding_model.sampler == "device": the draws are kernels of the captured forward (csrc/sample.hip dcn_device_sample, step
         # counter on the device) — nothing of the sampling heads is left on the host, Python's `random` stream is not advanced
-        self.host_draws = getattr(self.core, "sampler", "mt") != "device"
+        self.host_draws = n_frame is None and getattr(self.core, "sampler", "mt") != "device"
         self.graph: Optional[torch.cuda.CUDAGraph] = None
         self.loss = None
         self.parts = None
@@ -136,18 +150,23 @@ class GraphedTrainStep:
         # the forward reads this step's draws from the static buffers (draw_samples filled them); only for this call — an eager
         # forward of the same model elsewhere keeps drawing for itself
         self.core.static_samples = self.samples
-        defer = ops.LANGUAGE_BWD_DEFERRED and hasattr(self.core, "finish_backward")
+        window = self.n_frame is not None
+        defer = ops.LANGUAGE_BWD_DEFERRED and hasattr(self.core, "finish_backward") and not window
         # direct = the head's conv blocks add their weight gradient to .grad themselves (autograd sees None): only where nobody listens
         # on the parameters — a DDP wrapper or a hook-based reducer would never see those gradients
-        direct = ops.HEAD_WGRAD_DIRECT and not self._hooked
+        direct = ops.HEAD_WGRAD_DIRECT and not self._hooked and not window
         was_direct = ops.WGRAD_DIRECT
         if defer:
             self.core.defer_language_backward = True
         ops.WGRAD_DIRECT = direct
         ops.reset_held_wgrads()
         try:
-            out = self.model(self.image, self.word_id, self.word_mask)
-            loss, parts = losses.total_loss(out, self.bbox, self.size)
+            if window:
+                out = self.model(self.image, self.word_id, self.word_mask, self.n_frame)
+                loss, parts = losses.window_loss(out, self.bbox, self.size)
+            else:
+                out = self.model(self.image, self.word_id, self.word_mask)
+                loss, parts = losses.total_loss(out, self.bbox, self.size)
             self._zero_grads()
             loss.backward()
             if defer:

@@ -68,6 +68,11 @@ SIGNATURES = {
     "dcn_coattn_fwd": (I, [P, P, I, L, P, P, I, L, P, P, P, P, I, I, I, F, P]),
     "dcn_coattn_bwd_ws": (L, [I, I, I]),
     "dcn_coattn_bwd": (I, [P, P, I, L, P, P, I, L, P, P, I, L, P, P, P, P, P, I, L, I, P, I, I, I, F, P]),
+    "dcn_coattn_center_saved_size": (L, [I, I, I, I]),
+    "dcn_coattn_center_fwd_ws": (L, [I, I, I, I]),
+    "dcn_coattn_center_fwd": (I, [P, P, I, L, L, P, P, P, I, I, I, I, I, F, P]),
+    "dcn_coattn_center_bwd_ws": (L, [I, I, I, I]),
+    "dcn_coattn_center_bwd": (I, [P, P, I, L, L, P, I, L, L, P, P, P, I, P, I, I, I, I, I, F, P]),
     "dcn_l2norm_score_fwd": (I, [P, I, P, I, P, P, P, P, L, I, I, F, I, P]),
     "dcn_l2norm_score_bwd": (I, [P, I, P, P, I, P, P, P, P, I, P, L, I, I, P]),
     "dcn_rowdot_fwd": (I, [P, I, P, I, P, L, I, I, P]),

@@ -139,6 +139,26 @@ def total_loss(outputs, bbox: torch.Tensor, size: int):
     return loss, parts
 
 
+def window_loss(outputs, bbox: torch.Tensor, size: int):
+    """The loss of the window model: the 5-tuple (outbox, sim, loc, corr_feat, flang_attn) of ``grounding_model.forward(..., n_frame)`` in
+    train mode (model/test_DCNet_model.py:480-483) against ``bbox`` (B,4), the boxes of the centre frames.  The dense terms of
+    train_DCNet.py:605-642 — yolo + 100 * rank + loc, the negative similarity from ``neg_sim_score`` — without the two contrastive
+    terms: this model has no sampling heads.  Returns (loss, dict of the three parts).  The shapes are checked before any device work."""
+    if not isinstance(outputs, (tuple, list)) or len(outputs) != 5:
+        n_out = len(outputs) if isinstance(outputs, (tuple, list)) else type(outputs).__name__
+        raise ValueError(f"window_loss: expected the 5-tuple (outbox, sim, loc, corr_feat, flang_attn) of the window model in train mode, "
+                         f"got {n_out} (the 11-tuple of the pair model goes to total_loss)")
+    pred, sim, loc, corr_feat, flang_attn = outputs
+    B = flang_attn.shape[0]
+    if bbox.dim() != 2 or tuple(bbox.shape) != (B, 4):
+        raise ValueError(f"window_loss: bbox must be (B, 4) = ({B}, 4), one box per clip (its centre frame), got {tuple(bbox.shape)}")
+    _need_gpu(pred[0], "window_loss")
+    neg_sim = neg_sim_score(corr_feat, flang_attn)
+    yolo, rank, locl = dense_losses(pred, sim, neg_sim, loc, bbox, size)
+    parts = dict(yolo=yolo, rank=rank, loc=locl)
+    return yolo + 100 * rank + locl, parts
+
+
 def decode_boxes(outbox: Sequence[torch.Tensor], size: int, anchor_imsize: int = 416) -> torch.Tensor:
     """Evaluation decode (train_DCNet.py:764-810): global arg-max of the modulated confidence over 3 scales x 3 anchors, then
     (sigmoid(tx)+gi, sigmoid(ty)+gj, exp(tw)*aw, exp(th)*ah)*stride and xywh -> xyxy.  outbox[s] (N,15,g,g) or (N,3,5,g,g)."""

@@ -32,8 +32,9 @@ import torch.nn.functional as F
 
 from . import convblock, ops
 from .darknet import Darknet
-from .functions import (BatchNormRowsAct, BiLSTM, CoAttentionCenter, CoAttentionPairs, ConvBias, ConvBNAct, CrossModalSample,
-                        Embedding, FusionConvBNAct, HeadTail, InterframeSample, L2Norm, LinearAct, NormAccumulate, NormScore, PhraseAttn, RowDot)
+from .functions import (BatchNormRowsAct, BiLSTM, CoAttentionPairs, CoAttentionWindow, ConvBias, ConvBNAct, CrossModalSample,
+                        Embedding, FusionConvBNAct, HeadTail, InterframeSample, L2Norm, LinearAct, NormAccumulate, NormScore, PhraseAttn, RowDot,
+                        coattn_center_cat)
 from .lib import lib
 
 
@@ -497,18 +498,19 @@ class grounding_model(nn.Module):
         _, h, w, e = fv.shape
         clips = fv.view(B, n_frame, h * w, e)
         ctr, acc = n_frame // 2, None                                            # :303
-        for idx in range(n_frame):                                               # :312-320
-            if idx == ctr:
-                continue
-            cat = CoAttentionCenter.apply(clips, ctr, idx, self.temperature).view(B, h, w, 2 * e)
-            z = self.corr_conv[s][0](cat, one)
-            if torch.is_grad_enabled() and z.requires_grad:
-                # the reference's train branch of this model (test_DCNet_model.py:480-483; its scripts never take it): differentiable
-                # mean of the normalised features — L2Norm has a backward, the in-place accumulate of the inference path has none
-                zn = L2Norm.apply(z)
+        others = [idx for idx in range(n_frame) if idx != ctr]                   # :312-320
+        if torch.is_grad_enabled() and (clips.requires_grad or any(p.requires_grad for p in self.corr_conv[s].parameters())):
+            # the reference's train branch of this model (test_DCNet_model.py:480-483): one co-attention node for the whole window, then
+            # corr_conv ONCE PER NEIGHBOUR as the reference calls it (train-mode BatchNorm statistics are per call) and the differentiable
+            # mean of the normalised features — L2Norm has a backward, the in-place accumulate of the inference path has none
+            cats = CoAttentionWindow.apply(clips, ctr, self.temperature).unbind(0)
+            for cat in cats:
+                zn = L2Norm.apply(self.corr_conv[s][0](cat.view(B, h, w, 2 * e), one))
                 acc = zn * (1.0 / (n_frame - 1)) if acc is None else acc + zn * (1.0 / (n_frame - 1))
-            else:
-                acc = NormAccumulate.apply(z, acc, 1.0 / (n_frame - 1))          # :277-280, mean :324-332
+        else:
+            for idx in others:
+                cat = coattn_center_cat(clips, ctr, idx, self.temperature).view(B, h, w, 2 * e)
+                acc = NormAccumulate.apply(self.corr_conv[s][0](cat, one), acc, 1.0 / (n_frame - 1))          # :277-280, mean :324-332
         corr = acc
         sim, logits = self._score_scale(s, corr, flang, flang_attn)
         return fv, corr, sim, None, logits

@@ -1139,6 +1139,47 @@ def coattn_bwd(f1, f2, d_out1, d_out2, out1, out2, E, rc, d_f1, d_f2, accumulate
                      b, hw, c, float(temperature), _s())
 
 
+def _window_slices(x, nn, b, hw, c, what):
+    """(nn, b, hw, c) view with a contiguous last dim (a channel slice of the per-neighbour concat) -> (ld, batch stride, neighbour stride)."""
+    if tuple(x.shape) != (nn, b, hw, c) or x.stride(3) != 1 or x.dtype != torch.float32:
+        raise ValueError(f"{what}: expected an fp32 (T-1, B, HW, C) = {(nn, b, hw, c)} view with a contiguous last dim, got "
+                         f"{tuple(x.shape)} strides {x.stride()}")
+    return x.stride(2), x.stride(1), x.stride(0)
+
+
+def coattn_center_fwd(clips, ctr, out, temperature):
+    """Centre-versus-neighbours co-attention of a window (csrc/coattn_center.hip).  clips (B,T,HW,C) contiguous fp32, unit norm over C;
+    out (T-1,B,HW,C) view (last dim contiguous): attn of neighbour n = the n-th frame != ctr.  Returns the saved (E, rinv)."""
+    _chk(clips, "coattn_center_fwd clips")
+    b, t, hw, c = clips.shape
+    nn = t - 1
+    ldo, bso, nso = _window_slices(out, nn, b, hw, c, "coattn_center_fwd out")
+    dev = clips.device
+    E = torch.empty(lib().coattn_center_saved_size(b, t, hw, c), dtype=torch.float32, device=dev)
+    rinv = torch.empty((nn, b, hw), dtype=torch.float32, device=dev)
+    ws = scratch(lib().coattn_center_fwd_ws(b, t, hw, c), dev, slot=0)
+    lib().coattn_center_fwd(clips.data_ptr(), out.data_ptr(), ldo, bso, nso, E.data_ptr(), rinv.data_ptr(), ws.data_ptr(),
+                            b, t, hw, c, int(ctr), float(temperature), _s())
+    return E, rinv
+
+
+def coattn_center_bwd(clips, ctr, d_out, out, E, rinv, d_clips, accumulate, temperature):
+    """d_clips (B,T,HW,C) contiguous: the centre's rows (+)= the sum over the neighbours (accumulate: onto what they hold), every
+    neighbour's rows are written.  d_out / out: (T-1,B,HW,C) views as in coattn_center_fwd."""
+    _chk(clips, "coattn_center_bwd clips")
+    _chk(d_clips, "coattn_center_bwd d_clips")
+    b, t, hw, c = clips.shape
+    nn = t - 1
+    if d_clips.shape != clips.shape:
+        raise ValueError(f"coattn_center_bwd: d_clips {tuple(d_clips.shape)} != clips {tuple(clips.shape)}")
+    lddo, bsdo, nsdo = _window_slices(d_out, nn, b, hw, c, "coattn_center_bwd d_out")
+    ldo, bso, nso = _window_slices(out, nn, b, hw, c, "coattn_center_bwd out")
+    ws = scratch(lib().coattn_center_bwd_ws(b, t, hw, c), clips.device, slot=0)
+    lib().coattn_center_bwd(clips.data_ptr(), d_out.data_ptr(), lddo, bsdo, nsdo, out.data_ptr(), ldo, bso, nso,
+                            E.data_ptr(), rinv.data_ptr(), d_clips.data_ptr(), int(bool(accumulate)), ws.data_ptr(),
+                            b, t, hw, c, int(ctr), float(temperature), _s())
+
+
 def gemm3_presplit(x, amax, out=None):
     """x (b, rows, c) fp32 view (last dim contiguous) -> its f16 two-piece split form (same shape / bytes; csrc/gemm3.hip), scaled by the
     power of two of the abs-max word ``amax``.  out=x splits in place."""

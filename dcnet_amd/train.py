@@ -11,6 +11,8 @@ to drive ``grounding_model`` without the reference's data pipeline (SURVEY.md §
 ``--ema-decay D`` / ``--ema-tau T`` keep an exponential moving average of the weights inside the fused step (``dcnet_amd.optim.WeightEMA``);
 the closing evaluation then reports the raw and the averaged weights.
 
+``--n-frame K`` trains the window model the inference path evaluates (``forward(image, word_id, word_mask, K)``, ``losses.window_loss``).
+
 ``python -m dcnet_amd.train --steps 20`` (``--freeze-bn backbone|all``: BatchNorm on its running statistics; ``--freeze-weights backbone|K``:
 the backbone, or its modules 0..K, not trained and without a backward) runs a short synthetic-data training loop on one GPU; with ``--raw-frames`` every step's
 ``image`` / ``bbox`` come from synthetic uint8 frames of mixed sizes (1280x720 and 500x375) through the on-device clip
@@ -92,12 +94,18 @@ def adjust_learning_rate(optimizer, i_iter: int, base_lr: float, nb_epoch: int, 
     return lr
 
 
-def train_step(model, optimizer, image, word_id, word_mask, bbox, size: int):
+def train_step(model, optimizer, image, word_id, word_mask, bbox, size: int, n_frame: Optional[int] = None):
     """One optimisation step (train_DCNet.py:580-646).  Returns (loss, dict of the five parts) as device
-    tensors — reading them is the caller's (only) synchronisation point."""
+    tensors — reading them is the caller's (only) synchronisation point.
+    ``n_frame = K``: a step of the window model — ``image`` (B * K, 3, S, S), ``word_id`` (B, L), ``bbox`` (B, 4) the boxes of the centre
+    frames — with ``losses.window_loss`` (three parts: no sampling heads, no contrastive terms)."""
     model.train()
-    out = model(image, word_id, word_mask)
-    loss, parts = losses.total_loss(out, bbox, size)
+    if n_frame is None:
+        out = model(image, word_id, word_mask)
+        loss, parts = losses.total_loss(out, bbox, size)
+    else:
+        out = model(image, word_id, word_mask, n_frame)
+        loss, parts = losses.window_loss(out, bbox, size)
     optimizer.zero_grad(set_to_none=True)
     loss.backward()
     optimizer.step()
@@ -174,8 +182,12 @@ def arg_parser() -> argparse.ArgumentParser:
     ap = argparse.ArgumentParser(description="short synthetic-data training run of the HIP-backed DCNet")
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--clips", type=int, default=2)
-    ap.add_argument("--frames", type=int, default=2)
+    ap.add_argument("--frames", type=int, default=None, help="frames per clip (default 2; with --n-frame K: K)")
     ap.add_argument("--size", type=int, default=256)
+    ap.add_argument("--n-frame", type=int, default=None, metavar="K",
+                    help="train the window model (forward(image, word_id, word_mask, K): the centre frame of every clip against its K - 1 "
+                         "neighbours, one query and one box per clip, losses.window_loss); every clip is ONE window: --frames is then exactly K "
+                         "(its default; any other value is an error)")
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--optimizer", choices=["rmsprop", "adam", "sgd", "adamw"], default="rmsprop", help="train_DCNet.py's --optimizer, and adamw")
     ap.add_argument("--raw-frames", action="store_true", help="feed uint8 frames through dcnet_amd.prep every step")
@@ -226,7 +238,13 @@ def ema_args(args) -> Optional[dict]:
 
 
 def main(argv: Optional[Iterable[str]] = None) -> None:
-    args = arg_parser().parse_args(argv)
+    ap = arg_parser()
+    args = ap.parse_args(argv)
+    K = args.n_frame
+    if args.frames is None:
+        args.frames = 2 if K is None else K
+    if K is not None and (K < 2 or args.frames != K):
+        ap.error(f"--n-frame {K}: needs K >= 2 and --frames {K} (every clip is one window of exactly K frames)")
     from .model import grounding_model
     from .parallel import freeze_gradless
     from .utils.synth import synth_boxes, synth_inputs
@@ -247,8 +265,9 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
         ema = WeightEMA(model, **ema_args(args))
         opt.attach_ema(ema)
     n = args.clips * args.frames
-    image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, args.size, seed=1))
-    bbox = synth_boxes(n, args.size, seed=1).to(dev)
+    # (the window model: one query and one box — the centre frame's — per clip)
+    image, word_id, word_mask = (t.to(dev) for t in synth_inputs(n, args.size, n_queries=None if K is None else args.clips, seed=1))
+    bbox = synth_boxes(n if K is None else args.clips, args.size, seed=1).to(dev)
     if args.raw_frames:
         import numpy as np
         from .prep import prepare_clips
@@ -263,18 +282,18 @@ def main(argv: Optional[Iterable[str]] = None) -> None:
         adjust_learning_rate(opt, it // args.accum_steps, args.lr, -(-args.steps // args.accum_steps), 0.9)
         if args.raw_frames:
             res = prepare_clips(frames, src_boxes, phrases, args.size, True, rng=prep_rng, out=image)
-            bbox.copy_(res.bbox)
-        loss, parts = train_step(model, opt, image, word_id, word_mask, bbox, args.size)
+            bbox.copy_(res.bbox if K is None else res.bbox.view(args.clips, K, 4)[:, K // 2])
+        loss, parts = train_step(model, opt, image, word_id, word_mask, bbox, args.size, n_frame=K)
         if it % 5 == 0 or it == args.steps - 1:
             print(f"step {it:3d} loss {float(loss):9.4f}  " + " ".join(f"{k} {float(v):.4f}" for k, v in parts.items()))
-    acc, miou, _ = evaluate(model, image, word_id, word_mask, bbox, args.size)
+    acc, miou, _ = evaluate(model, image, word_id, word_mask, bbox, args.size, n_frame=K)
     line = f"Acc@0.5 {float(acc):.3f}  mIoU {float(miou):.3f} (on the training clips)"
     if opt.grad_norm is not None:
         line += f"  last gradient norm {float(opt.grad_norm):.4g}  skipped steps {opt.skipped_steps()}"
     print(line)
     if ema is not None:
         with ema.applied():
-            acc, miou, _ = evaluate(model, image, word_id, word_mask, bbox, args.size)
+            acc, miou, _ = evaluate(model, image, word_id, word_mask, bbox, args.size, n_frame=K)
         print(f"Acc@0.5 {float(acc):.3f}  mIoU {float(miou):.3f} (averaged weights: decay {ema.decay:g}, tau {ema.tau:g}, {ema.updates()} updates)")
 
 

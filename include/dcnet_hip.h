@@ -315,7 +315,34 @@ int dcn_coattn_bwd(const float* f1, const float* f2, int ldf, int64_t bsf,
                    float* d_f1, float* d_f2, int lddf, int64_t bsdf, int accumulate, float* ws,
                    int b, int hw, int c, float temperature, void* stream);
 
-/* ---- cross-modal scoring (HBM-bound) --------------------------------------------------- */
+/* ---- centre-versus-neighbours co-attention of a window (coattn_center.hip) --------------- */
+/* clips [b][t][hw][c] fp32, dense, unit L2 norm over c, c % 32 == 0, t >= 2, 0 <= ctr < t.  The neighbours j are the frames != ctr in
+ * ascending order, numbered n = 0 .. t-2.  With A_j = f_ctr . f_j^T, E_j = exp(temp*A_j - temp), rinv_j = 1 / rowsum(E_j):
+ *   attn_j = diag(rinv_j) . E_j . f_j                      (only the centre attends: no f2_attn, no column sums)
+ * attn_j of clip i lands at attn + n*nso + i*bso, pixel stride ldo (a channel slice of the per-neighbour concat [f_ctr | attn_j]).
+ * E (dcn_coattn_center_saved_size floats) receives the b*(t-1) matrices E_j ([n][b][hw][ld_pad(hw)], dcn_coattn_e_size(b*(t-1), hw)) and,
+ * where the products run on gemm3.hip (dcn_coattn_fwd's rule for a (b, hw, c) problem), the split form of ALL of clips behind them, made
+ * once; rinv is [t-1][b][hw].  Both are kept for the backward and are opaque, as for dcn_coattn_fwd: precision mode and the "Gemm3" knob
+ * must not change between a forward and its backward.  ws: dcn_coattn_center_fwd_ws floats.
+ * Backward, given d_attn_j (at d_attn + n*nsdo + i*bsdo, pixel stride lddo) and the forward's attn_j:
+ *   del_j[i] = <d_attn_j[i], attn_j[i]>,  dP_j = d_attn_j . f_j^T,  dA_j = temp * E_j * rinv_j[i] * (dP_j - del_j[i])
+ *   d_clips[:, ctr] (+)= sum_j dA_j . f_j                  (accumulate != 0: onto what the centre's rows hold — the direct half of the concat)
+ *   d_clips[:, j]     = dA_j^T . f_ctr + E_j^T . (rinv_j * d_attn_j)      (written, never read: d_clips need not be initialised there)
+ * d_clips [b][t][hw][c] dense.  Four products per neighbour; ws (dcn_coattn_center_bwd_ws floats) holds ONE hw x ld_pad(hw) buffer per
+ * clip, reused by every neighbour.  Replaces, for the train branch of the n_frame model (model/test_DCNet_model.py:259-274,480-483), one
+ * dcn_coattn_fwd / dcn_coattn_bwd per neighbour with a zero gradient for the unused f2_attn.  Called through dcnet_amd/ops.py
+ * coattn_center_fwd / coattn_center_bwd by functions.CoAttentionWindow (model._scale_nframe when a gradient is required). */
+int64_t dcn_coattn_center_saved_size(int b, int t, int hw, int c);
+int64_t dcn_coattn_center_fwd_ws(int b, int t, int hw, int c);
+int dcn_coattn_center_fwd(const float* clips, float* attn, int ldo, int64_t bso, int64_t nso, float* E, float* rinv, float* ws,
+                          int b, int t, int hw, int c, int ctr, float temperature, void* stream);
+int64_t dcn_coattn_center_bwd_ws(int b, int t, int hw, int c);
+int dcn_coattn_center_bwd(const float* clips, const float* d_attn, int lddo, int64_t bsdo, int64_t nsdo,
+                          const float* attn, int ldo, int64_t bso, int64_t nso, const float* E, const float* rinv,
+                          float* d_clips, int accumulate, float* ws,
+                          int b, int t, int hw, int c, int ctr, float temperature, void* stream);
+
+/* ---- cross-modal scoring (HBM-bound)--------------------------------------------------- */
 /* One pass over x [rows][c] (pixel stride ldx): xn = x / max(||x||_2, 1e-12) over c
  * (F.normalize(dim=1), model/DCNet_model.py:359,469), out = (accumulate ? out : 0) + out_scale*xn, and, when q != NULL,
  * score[row] = <xn[row,:], q[img(row),:]> with img(row) = row / rows_per_image
