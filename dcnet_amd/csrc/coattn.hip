@@ -11,10 +11,16 @@
 // forward and 6 backward, at the price of ~6 streaming passes over E (<= 20 % of the GEMM time at
 // HW = 2704, less at the coarser scales).  Because |A| <= 1 the softmax needs no running max:
 // exp(t*A - t) is in [e^-2t, 1], so row sums and column sums of the same E give both directions.
-// All GEMMs run on the shared engines: NT and NN forms on igemm.hip, TN on wgrad.hip.
+// All GEMMs run on the shared engines: NT and NN forms on igemm.hip, TN on wgrad.hip — or all three on gemm3.hip, on pre-split operands.
+//
+// This file holds the ONE copy of the co-attention kernels and of the product path (coattn.h: CoOperand / CoProducts, which send a
+// product to either engine family by one decision per problem) for the three callers: the pair node below, the window of
+// coattn_center.hip (one softmax direction: the COLS = false forms of exp_sums_kernel and dA_kernel) and the feature banks of video.hip.
+// The split layout of four values, and the power-of-two scale of an abs-max word, are split4.h's.
 #include "igemm.h"
 #include "prof.h"
 #include "coattn.h"
+#include "split4.h"
 
 int tn_gemm_batched(const float* A, int lda, long long a_bs, const float* B, int ldb, long long b_bs,
                     float* C, int ldc, long long c_bs, const float* row_scale,
@@ -28,11 +34,9 @@ constexpr int EXP_ROWS = 32;
 // E = exp(t*A - t) in place (pad columns -> 0), row sums, per-row-block column partial sums.
 // grid (ceil(hw/32), b); each thread owns FOUR consecutive columns (16-B accesses: with one float per lane this pass ran at
 // 0.34 of the HBM rate) 4*tid, 4*tid + 1024, ... and walks the 32 rows, all 32 loads of a column group in flight together.
-// SPLIT: E is written in the f16 two-piece split form the products on gemm3.hip read ([8 h | 8 l] per 8 columns, scale 2^13 for values
-// <= 1): a thread's four columns are half of such a run — 8 bytes of the h piece, 8 of the l piece; the sums are those of the fp32 values.
-typedef _Float16 f16x4c_t __attribute__((ext_vector_type(4)));
-constexpr float E_SPLIT_SCALE = 8192.f;           // = pow2_scale(1.0): brings 1.0 below 2^14
-template <bool SPLIT>
+// SPLIT: E is written in the f16 two-piece split form the products on gemm3.hip read (split4.h, scale 2^13 for values <= 1); the sums
+// are those of the fp32 values.  COLS = false: no column partials (the window of coattn_center.hip attends along the rows only).
+template <bool SPLIT, bool COLS>
 __global__ __launch_bounds__(256) void exp_sums_kernel(float* __restrict__ E, int hw, int ldE, float t,
                                                        float* __restrict__ rsum, float* __restrict__ colpart) {
   __shared__ float red[4][EXP_ROWS];
@@ -55,21 +59,13 @@ __global__ __launch_bounds__(256) void exp_sums_kernel(float* __restrict__ E, in
         f32x4 o;
 #pragma unroll
         for (int k = 0; k < 4; ++k) o[k] = (j + k < hw) ? expf(t * v[r][k] - t) : 0.f;
-        if constexpr (SPLIT) {
-          const f32x4 ts = o * E_SPLIT_SCALE;
-          const f16x4c_t h = {(_Float16)ts[0], (_Float16)ts[1], (_Float16)ts[2], (_Float16)ts[3]};
-          const f16x4c_t l = {(_Float16)(ts[0] - (float)h[0]), (_Float16)(ts[1] - (float)h[1]), (_Float16)(ts[2] - (float)h[2]),
-                              (_Float16)(ts[3] - (float)h[3])};
-          unsigned char* run = reinterpret_cast<unsigned char*>(e + (size_t)r * ldE + (j & ~7)) + (j & 4) * 2;
-          *reinterpret_cast<f16x4c_t*>(run) = h;
-          *reinterpret_cast<f16x4c_t*>(run + 16) = l;
-        } else {
-          *reinterpret_cast<f32x4*>(e + (size_t)r * ldE + j) = o;
-        }
-        cs += o; racc[r] += (o[0] + o[1]) + (o[2] + o[3]);
+        if constexpr (SPLIT) split4_store(e + (size_t)r * ldE, j, o * SPLIT_SCALE_ONE);
+        else *reinterpret_cast<f32x4*>(e + (size_t)r * ldE + j) = o;
+        if constexpr (COLS) cs += o;
+        racc[r] += (o[0] + o[1]) + (o[2] + o[3]);
       }
     }
-    *reinterpret_cast<f32x4*>(colpart + ((size_t)rb * gridDim.y + b) * ldE + j) = cs;
+    if constexpr (COLS) *reinterpret_cast<f32x4*>(colpart + ((size_t)rb * gridDim.y + b) * ldE + j) = cs;
   }
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -95,9 +91,11 @@ __global__ __launch_bounds__(256) void colsum_inv_kernel(const float* __restrict
 // Abs-max words of the co-attention GEMM operands (DCN_AMAX_WORDS each, in the caller's workspace): slot 0 holds the
 // constant 1 — unit-norm features, E = exp(t*A - t) <= 1 — the others start at 0 and are raised by the kernels that write
 // or read the gradient operands.  With both words present a GEMM runs on the f16 two-piece split (igemm.hip).
+// (the slots of the pair entry points; the window of coattn_center.hip keeps one set of its own five per neighbour)
 enum { AM_ONE = 0, AM_DO1, AM_DO2, AM_DO1S, AM_DO2S, AM_DA, AM_DP1, AM_DP2, AM_SLOTS };
-__global__ __launch_bounds__(256) void amax_init_kernel(unsigned* __restrict__ w) {
-  for (int i = threadIdx.x; i < AM_SLOTS * DCN_AMAX_WORDS; i += 256) w[i] = i < DCN_AMAX_WORDS ? 0x3F800000u : 0u;
+__global__ __launch_bounds__(256) void amax_init_kernel(unsigned* __restrict__ w, int total, int words_per_set) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256)
+    w[i] = (i % words_per_set) < DCN_AMAX_WORDS ? 0x3F800000u : 0u;
 }
 
 // one wave per row: delta[row] = <d[row], o[row]>, ds[row] = d[row] * inv[row]; abs-max of d and ds
@@ -134,7 +132,9 @@ __global__ __launch_bounds__(256) void rowdot_scale_kernel(const float* __restri
 // dA = t * E * ((dP1 - d1[i]) * rinv[i] + (dP2 - d2[j]) * cinv[j]), written over dP1; pad columns -> 0
 // OSPLIT: dA is written in the split form as well, scaled by the word in amax_da, which then holds a BOUND (da_bound_kernel) instead
 // of receiving the maximum.
-template <bool ESPLIT, bool OSPLIT = false>
+// COLS = false, the one-sided form of the window: dA = t * E * rinv[i] * (dP1 - d1[i]), no dP2 / cinv / d2.  Only the arithmetic line
+// differs; its operation order is each form's own (the two round differently).
+template <bool ESPLIT, bool OSPLIT, bool COLS>
 __global__ __launch_bounds__(256) void dA_kernel(const float* __restrict__ E, float* __restrict__ dP1, const float* __restrict__ dP2,
                                                  const float* __restrict__ rinv, const float* __restrict__ cinv,
                                                  const float* __restrict__ d1, const float* __restrict__ d2,
@@ -143,43 +143,37 @@ __global__ __launch_bounds__(256) void dA_kernel(const float* __restrict__ E, fl
   float vmax = 0.f;
   const int l4 = ldE >> 2;
   float s_out = 1.f;
-  if constexpr (OSPLIT) {                         // (= igemm.hip pow2_scale of the bound)
-    const int be = (int)((amax_read(amax_da) >> 23) & 0xFF);
-    int ex = (be == 0 || be == 255) ? 0 : 14 - (be - 126);
-    ex = ex > 100 ? 100 : (ex < -100 ? -100 : ex);
-    s_out = __uint_as_float((unsigned)(ex + 127) << 23);
-  }
+  if constexpr (OSPLIT) s_out = split_pow2_scale(amax_read(amax_da));
   for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total4; idx += (int64_t)gridDim.x * 256) {
     const int64_t row = idx / l4;                 // = b*hw + i
     const int j = (int)(idx - row * l4) * 4;
-    const int64_t bb = row / hw;
     f32x4 e;
     if constexpr (ESPLIT) {                       // h + l of the split form: E to 22 bits
-      const unsigned char* run = reinterpret_cast<const unsigned char*>(E + row * ldE + (j & ~7)) + (j & 4) * 2;
-      const f16x4c_t h = *reinterpret_cast<const f16x4c_t*>(run), l = *reinterpret_cast<const f16x4c_t*>(run + 16);
+      const f32x4 hl = split4_load(E + row * ldE, j);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) e[k] = ((float)h[k] + (float)l[k]) * (1.f / E_SPLIT_SCALE);
+      for (int k = 0; k < 4; ++k) e[k] = hl[k] * (1.f / SPLIT_SCALE_ONE);
     } else {
       e = *reinterpret_cast<const f32x4*>(E + row * ldE + j);
     }
     const f32x4 p1 = *reinterpret_cast<const f32x4*>(dP1 + row * ldE + j);
-    const f32x4 p2 = *reinterpret_cast<const f32x4*>(dP2 + row * ldE + j);
     const float ri = rinv[row], di = d1[row];
     f32x4 o;
+    if constexpr (COLS) {
+      const int64_t bb = row / hw;
+      const f32x4 p2 = *reinterpret_cast<const f32x4*>(dP2 + row * ldE + j);
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      float v = 0.f;
-      if (j + k < hw) v = t * e[k] * ((p1[k] - di) * ri + (p2[k] - d2[bb * hw + j + k]) * cinv[bb * hw + j + k]);
-      o[k] = v;
+      for (int k = 0; k < 4; ++k) {
+        float v = 0.f;
+        if (j + k < hw) v = t * e[k] * ((p1[k] - di) * ri + (p2[k] - d2[bb * hw + j + k]) * cinv[bb * hw + j + k]);
+        o[k] = v;
+      }
+    } else {
+      const float tr = t * ri;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) o[k] = (j + k < hw) ? tr * e[k] * (p1[k] - di) : 0.f;
     }
     if constexpr (OSPLIT) {                       // (a lane pair shares a run of 8 columns: both have read their 16 bytes by now)
-      const f32x4 ts = o * s_out;
-      const f16x4c_t h = {(_Float16)ts[0], (_Float16)ts[1], (_Float16)ts[2], (_Float16)ts[3]};
-      const f16x4c_t l = {(_Float16)(ts[0] - (float)h[0]), (_Float16)(ts[1] - (float)h[1]), (_Float16)(ts[2] - (float)h[2]),
-                          (_Float16)(ts[3] - (float)h[3])};
-      unsigned char* run = reinterpret_cast<unsigned char*>(dP1 + row * ldE + (j & ~7)) + (j & 4) * 2;
-      *reinterpret_cast<f16x4c_t*>(run) = h;
-      *reinterpret_cast<f16x4c_t*>(run + 16) = l;
+      split4_store(dP1 + row * ldE, j, o * s_out);
     } else {
       *reinterpret_cast<f32x4*>(dP1 + row * ldE + j) = o;
       vmax = fmaxf(fmaxf(vmax, fmaxf(fabsf(o[0]), fabsf(o[1]))), fmaxf(fabsf(o[2]), fabsf(o[3])));
@@ -191,10 +185,10 @@ __global__ __launch_bounds__(256) void dA_kernel(const float* __restrict__ E, fl
 // |dA_ij| = t E_ij |(dP1_ij - d1_i) r_i + (dP2_ij - d2_j) c_j| <= 2 t (max|dP1| + max|dP2|): E_ij r_i <= 1 and E_ij c_j <= 1 (an entry is
 // one term of its row / column sum) and d1_i, d2_j are softmax-weighted means of dP1's row / dP2's column.  The f16 split needs a bound,
 // not the maximum (a loose one costs the smallest entries their lowest bits: absolute error <= 2^-39 of the bound), so dA_kernel can
-// write the split form directly instead of fp32 + a split pass over 0.94 GB.
+// write the split form directly instead of fp32 + a split pass over 0.94 GB.  a2 = null, the one-sided form: <= 2 t max|dP| (adding 0 is exact).
 __global__ __launch_bounds__(64) void da_bound_kernel(const unsigned* __restrict__ a1, const unsigned* __restrict__ a2, float t,
                                                       unsigned* __restrict__ out) {
-  const float b = 2.f * t * (__uint_as_float(amax_read(a1)) + __uint_as_float(amax_read(a2)));
+  const float b = 2.f * t * (__uint_as_float(amax_read(a1)) + (a2 ? __uint_as_float(amax_read(a2)) : 0.f));
   out[threadIdx.x & (DCN_AMAX_WORDS - 1)] = __float_as_uint(b);
 }
 
@@ -216,25 +210,104 @@ void gemm_params(IgemmParams& p, const float* A, int lda, long long a_bs, const 
 // "Gemm3" knob only: dcn_coattn_bwd must see what dcn_coattn_fwd saw (E is saved in the form the forward wrote).
 static bool on_gemm3(int b, int hw, int c) { return c % 32 == 0 && gemm3_applicable(hw, c, hw, b) && gemm3_applicable(hw, hw, c, b); }
 
-// ---- shared with video.hip (coattn.h): the same kernels on operands that live in a feature bank ---------------------------------
+// ---- shared with coattn_center.hip and video.hip (coattn.h): the same kernels on a window's frames / on a feature bank -------------
 int coattn_ld_pad(int hw) { return ld_pad(hw); }
 bool coattn_on_gemm3(int b, int hw, int c) { return on_gemm3(b, hw, c); }
 unsigned* coattn_ws_amax(float* ws, int b, int hw) { return reinterpret_cast<unsigned*>(ws + (int64_t)cdiv(hw, EXP_ROWS) * b * ld_pad(hw)); }
-int coattn_amax_init(unsigned* am, hipStream_t stream) {
-  hipLaunchKernelGGL(amax_init_kernel, dim3(1), dim3(256), 0, stream, am);
+int coattn_amax_init_sets(unsigned* am, int sets, int slots, hipStream_t stream) {
+  const int total = sets * slots * DCN_AMAX_WORDS;
+  hipLaunchKernelGGL(amax_init_kernel, dim3(cdiv(total, 256)), dim3(256), 0, stream, am, total, slots * DCN_AMAX_WORDS);
   DCN_CHECK_LAUNCH("coattn amax_init");
   return DCN_OK;
 }
-int coattn_exp_sums(float* E, int b, int hw, float temperature, float* rinv, float* cinv, float* ws, bool split, hipStream_t stream) {
+int coattn_amax_init(unsigned* am, hipStream_t stream) { return coattn_amax_init_sets(am, 1, AM_SLOTS, stream); }
+
+int coattn_exp_sums(float* E, int nb, int hw, float temperature, float* rinv, float* cinv, float* ws, bool split, hipStream_t stream) {
   const int ldE = ld_pad(hw), nrb = cdiv(hw, EXP_ROWS);
-  const int pid = prof_begin(12, (double)b * hw * ldE * 8.0, stream);
-  if (split) hipLaunchKernelGGL(exp_sums_kernel<true>, dim3(nrb, b), dim3(256), 0, stream, E, hw, ldE, temperature, rinv, ws);
-  else hipLaunchKernelGGL(exp_sums_kernel<false>, dim3(nrb, b), dim3(256), 0, stream, E, hw, ldE, temperature, rinv, ws);
+  const auto kernel = split ? (cinv ? exp_sums_kernel<true, true> : exp_sums_kernel<true, false>)
+                            : (cinv ? exp_sums_kernel<false, true> : exp_sums_kernel<false, false>);
+  const int pid = prof_begin(12, (double)nb * hw * ldE * 8.0, stream);
+  hipLaunchKernelGGL(kernel, dim3(nrb, nb), dim3(256), 0, stream, E, hw, ldE, temperature, rinv, ws);
   prof_end(pid, stream);
   DCN_CHECK_LAUNCH("exp_sums");
-  hipLaunchKernelGGL(colsum_inv_kernel, dim3(cdiv(hw, 256), b), dim3(256), 0, stream, ws, nrb, b, hw, ldE, cinv);
+  if (!cinv) return DCN_OK;
+  hipLaunchKernelGGL(colsum_inv_kernel, dim3(cdiv(hw, 256), nb), dim3(256), 0, stream, ws, nrb, nb, hw, ldE, cinv);
   DCN_CHECK_LAUNCH("colsum_inv");
   return DCN_OK;
+}
+
+int coattn_rowdot_scale(const float* d, int ldd, long long bsd, const float* o, int ldo, long long bso, const float* inv, int b, int hw,
+                        int c, float* delta, float* ds, unsigned* amax_d, unsigned* amax_ds, hipStream_t stream) {
+  const int64_t rows = (int64_t)b * hw;
+  hipLaunchKernelGGL(rowdot_scale_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, d, ldd, (int64_t)bsd, o, ldo, (int64_t)bso, hw, inv, rows, c,
+                     delta, ds, amax_d, amax_ds);
+  DCN_CHECK_LAUNCH("rowdot_scale");
+  return DCN_OK;
+}
+
+int coattn_da_bound(const unsigned* a1, const unsigned* a2, float temperature, unsigned* out, hipStream_t stream) {
+  hipLaunchKernelGGL(da_bound_kernel, dim3(1), dim3(64), 0, stream, a1, a2, temperature, out);
+  DCN_CHECK_LAUNCH("dA bound");
+  return DCN_OK;
+}
+
+int coattn_dA(const float* E, float* dP1, const float* dP2, const float* rinv, const float* cinv, const float* d1, const float* d2,
+              int b, int hw, float temperature, unsigned* amax_da, bool split, hipStream_t stream) {
+  const int ldE = ld_pad(hw);
+  const int64_t total4 = (int64_t)b * hw * (ldE / 4);
+  int64_t g = (total4 + 255) / 256;
+  if (g > 1024) g = 1024;      // (one abs-max atomic per workgroup)
+  const auto kernel = split ? (cinv ? dA_kernel<true, true, true> : dA_kernel<true, true, false>)
+                            : (cinv ? dA_kernel<false, false, true> : dA_kernel<false, false, false>);
+  const int pid = prof_begin(31, (double)total4 * 16.0 * (cinv ? 4.0 : 3.0), stream);      // HBM-priced: E, dP1 (, dP2) read, dA written
+  hipLaunchKernelGGL(kernel, dim3((int)g), dim3(256), 0, stream, E, dP1, dP2, rinv, cinv, d1, d2, hw, ldE, temperature, total4, amax_da);
+  prof_end(pid, stream);
+  DCN_CHECK_LAUNCH("dA");
+  return DCN_OK;
+}
+
+// ---- the product path ----------------------------------------------------------------------------------------------------------
+int CoProducts::nt(const CoOperand& A, const CoOperand& B, float* C, int ldc, long long c_bs, const float* row_scale, int accumulate,
+                   unsigned* amax_out) const {
+  if (g3) return gemm3_launch(A.s, A.lds, A.bss, 0, B.s, B.lds, B.bss, 0, C, ldc, c_bs, row_scale, row_scale ? hw : 0, hw, hw, c, b,
+                              accumulate, A.amax, B.amax, stream, amax_out);
+  IgemmParams p;
+  gemm_params(p, A.f, A.ld, A.bs, B.f, B.ld, B.bs, C, ldc, c_bs, hw, hw, c, b);
+  p.row_scale = row_scale; p.accumulate = accumulate; p.amax_a = A.amax; p.amax_b = B.amax;
+  return igemm_launch(p, stream);
+}
+int CoProducts::nn(const CoOperand& A, const CoOperand& B, float* C, int ldc, long long c_bs, const float* row_scale, int accumulate,
+                   unsigned* amax_out) const {
+  if (g3) return gemm3_launch(A.s, A.lds, A.bss, 0, B.s, B.lds, B.bss, 1, C, ldc, c_bs, row_scale, row_scale ? hw : 0, hw, c, hw, b,
+                              accumulate, A.amax, B.amax, stream, amax_out);
+  IgemmParams p;
+  gemm_params(p, A.f, A.ld, A.bs, B.f, B.ld, B.bs, C, ldc, c_bs, hw, c, A.ld, b);      // K = the padded row of A: zeros beyond kvalid
+  p.bmode = 1; p.kvalid = hw; p.row_scale = row_scale; p.accumulate = accumulate; p.amax_a = A.amax; p.amax_b = B.amax;
+  return igemm_launch(p, stream);
+}
+int CoProducts::tn(const CoOperand& A, const CoOperand& B, float* C, int ldc, long long c_bs, const float* row_scale, int accumulate,
+                   unsigned* amax_out) const {
+  if (g3) return gemm3_launch(A.s, A.lds, A.bss, 1, B.s, B.lds, B.bss, 1, C, ldc, c_bs, row_scale, row_scale ? hw : 0, hw, c, hw, b,
+                              accumulate, A.amax, B.amax, stream, amax_out);
+  return tn_gemm_batched(A.f, A.ld, A.bs, B.f, B.ld, B.bs, C, ldc, c_bs, row_scale, hw, A.ld, c, hw, b, accumulate, stream, A.amax, B.amax);
+}
+
+int coattn_fwd_operands(const CoOperand& F1, const CoOperand& F2, float* f1_attn, float* f2_attn, int ldo, long long bso, float* E,
+                        float* rinv, float* cinv, float* ws, int b, int hw, int c, float temperature, hipStream_t stream) {
+  const CoProducts P(b, hw, c, stream);
+  const int ldE = ld_pad(hw);
+  const long long bsE = (long long)hw * ldE;
+  const CoOperand Eo = co_buffer(E, ldE, bsE, F1.amax);       // (E <= 1: the constant word)
+  int rc;
+  // 1. A = f1 . f2^T -> E                                              (NT)
+  if ((rc = P.nt(F1, F2, E, ldE, bsE, nullptr, 0))) return rc;
+  // 2. E = exp(t*A - t) (gemm3.hip: in split form), rinv = 1/rowsum, cinv = 1/colsum
+  if ((rc = coattn_exp_sums(E, b, hw, temperature, rinv, cinv, ws, P.g3, stream))) return rc;
+  // 3. f1_attn = diag(rinv) E f2                                       (NN, K = keys j)
+  if ((rc = P.nn(Eo, F2, f1_attn, ldo, bso, rinv, 0))) return rc;
+  // 4. f2_attn = diag(cinv) E^T f1                                     (TN, K = queries i)
+  if (f2_attn) rc = P.tn(Eo, F1, f2_attn, ldo, bso, cinv, 0);
+  return rc;
 }
 
 extern "C" int64_t dcn_coattn_fwd_ws(int b, int hw, int c) {
@@ -260,59 +333,21 @@ extern "C" int dcn_coattn_fwd(const float* f1, const float* f2, int ldf, int64_t
   if (bsf <= 0) bsf = (int64_t)hw * ldf;
   if (bso <= 0) bso = (int64_t)hw * ldo;
   DCN_CHECK_ARG(bsf % 4 == 0 && bso % 4 == 0, "coattn_fwd: batch strides must be multiples of 4");
-  const int ldE = ld_pad(hw);
-  unsigned* am = reinterpret_cast<unsigned*>(ws + (int64_t)cdiv(hw, EXP_ROWS) * b * ldE);
-  hipLaunchKernelGGL(amax_init_kernel, dim3(1), dim3(256), 0, stream, am);
-  DCN_CHECK_LAUNCH("coattn amax_init");
+  unsigned* am = coattn_ws_amax(ws, b, hw);
+  int rc = coattn_amax_init(am, stream);
+  if (rc) return rc;
   const unsigned* one = am + AM_ONE * DCN_AMAX_WORDS;
-  const int nrb = cdiv(hw, EXP_ROWS);
-  const long long bsE = (long long)hw * ldE;
+  // gemm3.hip: f1, f2 split once (unit norm: the constant word) behind E, kept for the backward (dcn_coattn_saved_size; no such room,
+  // and no reader, on the other path)
+  float* f1s = E + dcn_coattn_e_size(b, hw);
+  float* f2s = f1s + (int64_t)b * hw * c;
+  const long long bss = (long long)hw * c;
   if (on_gemm3(b, hw, c)) {
-    // every product on gemm3.hip: f1, f2 split once (unit norm: the constant word), E written in split form by its own pass
-    float* f1s = E + dcn_coattn_e_size(b, hw);               // (kept for the backward: dcn_coattn_saved_size)
-    float* f2s = f1s + (int64_t)b * hw * c;
-    const long long bss = (long long)hw * c;
-    int rc = gemm3_presplit(f1, ldf, bsf, f1s, c, bss, b, hw, c, one, stream);
-    if (rc) return rc;
+    if ((rc = gemm3_presplit(f1, ldf, bsf, f1s, c, bss, b, hw, c, one, stream))) return rc;
     if ((rc = gemm3_presplit(f2, ldf, bsf, f2s, c, bss, b, hw, c, one, stream))) return rc;
-    // 1. A = f1 . f2^T -> E                                              (NT)
-    if ((rc = gemm3_launch(f1s, c, bss, 0, f2s, c, bss, 0, E, ldE, bsE, nullptr, 0, hw, hw, c, b, 0, one, one, stream))) return rc;
-    // 2. E = exp(t*A - t) in split form, rinv, cinv
-    const int pid = prof_begin(12, (double)b * hw * ldE * 8.0, stream);
-    hipLaunchKernelGGL(exp_sums_kernel<true>, dim3(nrb, b), dim3(256), 0, stream, E, hw, ldE, temperature, rinv, ws);
-    prof_end(pid, stream);
-    DCN_CHECK_LAUNCH("exp_sums");
-    hipLaunchKernelGGL(colsum_inv_kernel, dim3(cdiv(hw, 256), b), dim3(256), 0, stream, ws, nrb, b, hw, ldE, cinv);
-    DCN_CHECK_LAUNCH("colsum_inv");
-    // 3. f1_attn = diag(rinv) E f2                                       (NN, K = keys j)
-    if ((rc = gemm3_launch(E, ldE, bsE, 0, f2s, c, bss, 1, f1_attn, ldo, bso, rinv, hw, hw, c, hw, b, 0, one, one, stream))) return rc;
-    // 4. f2_attn = diag(cinv) E^T f1                                     (TN, K = queries i)
-    if (f2_attn) rc = gemm3_launch(E, ldE, bsE, 1, f1s, c, bss, 1, f2_attn, ldo, bso, cinv, hw, hw, c, hw, b, 0, one, one, stream);
-    return rc;
   }
-  IgemmParams p;
-  // 1. A = f1 . f2^T  -> E                                             (NT)
-  gemm_params(p, f1, ldf, bsf, f2, ldf, bsf, E, ldE, (long long)hw * ldE, hw, hw, c, b);
-  p.amax_a = one; p.amax_b = one;
-  int rc = igemm_launch(p, stream);
-  if (rc) return rc;
-  // 2. E = exp(t*A - t), rinv = 1/rowsum, cinv = 1/colsum
-  const int pid = prof_begin(12, (double)b * hw * ldE * 8.0, stream);
-  hipLaunchKernelGGL(exp_sums_kernel<false>, dim3(nrb, b), dim3(256), 0, stream, E, hw, ldE, temperature, rinv, ws);
-  prof_end(pid, stream);
-  DCN_CHECK_LAUNCH("exp_sums");
-  hipLaunchKernelGGL(colsum_inv_kernel, dim3(cdiv(hw, 256), b), dim3(256), 0, stream, ws, nrb, b, hw, ldE, cinv);
-  DCN_CHECK_LAUNCH("colsum_inv");
-  // 3. f1_attn = diag(rinv) E f2                                       (NN, K = keys j)
-  gemm_params(p, E, ldE, (long long)hw * ldE, f2, ldf, bsf, f1_attn, ldo, bso, hw, c, ldE, b);
-  p.bmode = 1; p.kvalid = hw; p.row_scale = rinv; p.amax_a = one; p.amax_b = one;
-  rc = igemm_launch(p, stream);
-  if (rc) return rc;
-  // 4. f2_attn = diag(cinv) E^T f1                                     (TN, K = queries i)
-  if (f2_attn)
-    rc = tn_gemm_batched(E, ldE, (long long)hw * ldE, f1, ldf, bsf, f2_attn, ldo, bso,
-                         cinv, hw, ldE, c, hw, b, 0, stream, one, one);
-  return rc;
+  return coattn_fwd_operands(CoOperand{f1, ldf, bsf, f1s, c, bss, one}, CoOperand{f2, ldf, bsf, f2s, c, bss, one}, f1_attn, f2_attn, ldo, bso,
+                             E, rinv, cinv, ws, b, hw, c, temperature, stream);
 }
 
 extern "C" int64_t dcn_coattn_bwd_ws(int b, int hw, int c) {
@@ -347,74 +382,39 @@ extern "C" int dcn_coattn_bwd(const float* f1, const float* f2, int ldf, int64_t
   float* del1 = dO2s + rows * c;
   float* del2 = del1 + rows;
   unsigned* am = reinterpret_cast<unsigned*>(del2 + rows);
-  hipLaunchKernelGGL(amax_init_kernel, dim3(1), dim3(256), 0, stream, am);
-  DCN_CHECK_LAUNCH("coattn amax_init");
+  int rc = coattn_amax_init(am, stream);
+  if (rc) return rc;
   auto slot = [&](int i) { return am + i * DCN_AMAX_WORDS; };
+  const CoProducts P(b, hw, c, stream);
+  const long long bsE = (long long)hw * ldE, bss = (long long)hw * c;
+  // gemm3.hip only: the split forms of the upstream gradients (workspace) and of f1, f2 (the forward's, behind E; unit norm: the constant word)
+  float* dO1p = reinterpret_cast<float*>(((uintptr_t)(am + AM_SLOTS * DCN_AMAX_WORDS) + 15) & ~(uintptr_t)15);      // (b * hw may be odd)
+  float* dO2p = dO1p + rows * c;
+  const float* f1s = E + dcn_coattn_e_size(b, hw);
+  const float* f2s = f1s + rows * c;
+  const CoOperand F1{f1, ldf, bsf, f1s, c, bss, slot(AM_ONE)}, F2{f2, ldf, bsf, f2s, c, bss, slot(AM_ONE)};
+  const CoOperand DO1{d_f1_attn, lddo, bsdo, dO1p, c, bss, slot(AM_DO1)}, DO2{d_f2_attn, lddo, bsdo, dO2p, c, bss, slot(AM_DO2)};
+  const CoOperand DO1S = co_buffer(dO1s, c, bss, slot(AM_DO1S)), DO2S = co_buffer(dO2s, c, bss, slot(AM_DO2S));
+  const CoOperand Eo = co_buffer(E, ldE, bsE, slot(AM_ONE)), DA = co_buffer(dP1, ldE, bsE, slot(AM_DA));
   // 1. delta and pre-scaled upstream gradients
-  hipLaunchKernelGGL(rowdot_scale_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, d_f1_attn, lddo, bsdo, f1_attn, ldo, bso, hw, rinv, rows, c, del1, dO1s,
-                     slot(AM_DO1), slot(AM_DO1S));
-  DCN_CHECK_LAUNCH("rowdot_scale");
-  hipLaunchKernelGGL(rowdot_scale_kernel, dim3(cdiv(rows, 4)), dim3(256), 0, stream, d_f2_attn, lddo, bsdo, f2_attn, ldo, bso, hw, cinv, rows, c, del2, dO2s,
-                     slot(AM_DO2), slot(AM_DO2S));
-  DCN_CHECK_LAUNCH("rowdot_scale");
-  const int64_t total4 = rows * (ldE / 4);
-  int64_t g = (total4 + 255) / 256; if (g > 8192) g = 8192;
-  if (g > 1024) g = 1024;      // (one abs-max atomic per workgroup)
-  const long long bsE = (long long)hw * ldE;
-  if (on_gemm3(b, hw, c)) {
-    // every product on gemm3.hip (E arrives in split form from dcn_coattn_fwd): the six narrow operands are split once each, dA in place
-    float* dO1p = reinterpret_cast<float*>(((uintptr_t)(am + AM_SLOTS * DCN_AMAX_WORDS) + 15) & ~(uintptr_t)15);      // (b * hw may be odd)
-    float* dO2p = dO1p + rows * c;
-    const float* f1s = E + dcn_coattn_e_size(b, hw);         // the forward's split forms of f1, f2 (unit norm: the constant abs-max word)
-    const float* f2s = f1s + rows * c;
-    const long long bss = (long long)hw * c;
-    int rc;
+  if ((rc = coattn_rowdot_scale(d_f1_attn, lddo, bsdo, f1_attn, ldo, bso, rinv, b, hw, c, del1, dO1s, slot(AM_DO1), slot(AM_DO1S), stream))) return rc;
+  if ((rc = coattn_rowdot_scale(d_f2_attn, lddo, bsdo, f2_attn, ldo, bso, cinv, b, hw, c, del2, dO2s, slot(AM_DO2), slot(AM_DO2S), stream))) return rc;
+  if (P.g3) {      // (E arrives in split form from dcn_coattn_fwd) the four narrow gradient operands are split once each, the scaled ones in place
     if ((rc = gemm3_presplit(d_f1_attn, lddo, bsdo, dO1p, c, bss, b, hw, c, slot(AM_DO1), stream))) return rc;
     if ((rc = gemm3_presplit(d_f2_attn, lddo, bsdo, dO2p, c, bss, b, hw, c, slot(AM_DO2), stream))) return rc;
     if ((rc = gemm3_presplit(dO1s, c, bss, dO1s, c, bss, b, hw, c, slot(AM_DO1S), stream))) return rc;
     if ((rc = gemm3_presplit(dO2s, c, bss, dO2s, c, bss, b, hw, c, slot(AM_DO2S), stream))) return rc;
-    // 2. dP1[i,j] = <dO1_i, f2_j>,  dP2[i,j] = <f1_i, dO2_j>                (NT x2)
-    if ((rc = gemm3_launch(dO1p, c, bss, 0, f2s, c, bss, 0, dP1, ldE, bsE, nullptr, 0, hw, hw, c, b, 0, slot(AM_DO1), slot(AM_ONE), stream, slot(AM_DP1)))) return rc;
-    if ((rc = gemm3_launch(f1s, c, bss, 0, dO2p, c, bss, 0, dP2, ldE, bsE, nullptr, 0, hw, hw, c, b, 0, slot(AM_ONE), slot(AM_DO2), stream, slot(AM_DP2)))) return rc;
-    // 3. dA (over dP1; pads -> 0) in split form straight away, scaled by a bound from the two maxima the products above left
-    hipLaunchKernelGGL(da_bound_kernel, dim3(1), dim3(64), 0, stream, slot(AM_DP1), slot(AM_DP2), temperature, slot(AM_DA));
-    DCN_CHECK_LAUNCH("dA bound");
-    const int pid_da = prof_begin(31, (double)total4 * 16.0 * 4.0, stream);
-    hipLaunchKernelGGL((dA_kernel<true, true>), dim3((int)g), dim3(256), 0, stream, E, dP1, dP2, rinv, cinv, del1, del2, hw, ldE, temperature, total4, slot(AM_DA));
-    prof_end(pid_da, stream);
-    DCN_CHECK_LAUNCH("dA");
-    // 4. d_f1 (+)= dA f2 + E (dO2 / colsum)                                 (NN x2)
-    if ((rc = gemm3_launch(dP1, ldE, bsE, 0, f2s, c, bss, 1, d_f1, lddf, bsdf, nullptr, 0, hw, c, hw, b, accumulate, slot(AM_DA), slot(AM_ONE), stream))) return rc;
-    if ((rc = gemm3_launch(E, ldE, bsE, 0, dO2s, c, bss, 1, d_f1, lddf, bsdf, nullptr, 0, hw, c, hw, b, 1, slot(AM_ONE), slot(AM_DO2S), stream))) return rc;
-    // 5. d_f2 (+)= dA^T f1 + E^T (dO1 / rowsum)                             (TN x2)
-    if ((rc = gemm3_launch(dP1, ldE, bsE, 1, f1s, c, bss, 1, d_f2, lddf, bsdf, nullptr, 0, hw, c, hw, b, accumulate, slot(AM_DA), slot(AM_ONE), stream))) return rc;
-    return gemm3_launch(E, ldE, bsE, 1, dO1s, c, bss, 1, d_f2, lddf, bsdf, nullptr, 0, hw, c, hw, b, 1, slot(AM_ONE), slot(AM_DO1S), stream);
   }
-  IgemmParams p;
-  int rc;
   // 2. dP1[i,j] = <dO1_i, f2_j>,  dP2[i,j] = <f1_i, dO2_j>                  (NT x2)
-  gemm_params(p, d_f1_attn, lddo, bsdo, f2, ldf, bsf, dP1, ldE, (long long)hw * ldE, hw, hw, c, b);
-  p.amax_a = slot(AM_DO1); p.amax_b = slot(AM_ONE);
-  if ((rc = igemm_launch(p, stream))) return rc;
-  gemm_params(p, f1, ldf, bsf, d_f2_attn, lddo, bsdo, dP2, ldE, (long long)hw * ldE, hw, hw, c, b);
-  p.amax_a = slot(AM_ONE); p.amax_b = slot(AM_DO2);
-  if ((rc = igemm_launch(p, stream))) return rc;
-  // 3. dA (over dP1)
-  const int pid_da = prof_begin(31, (double)total4 * 16.0 * 4.0, stream);             // HBM-priced: E, dP1, dP2 read, dA written
-  hipLaunchKernelGGL(dA_kernel<false>, dim3((int)g), dim3(256), 0, stream, E, dP1, dP2, rinv, cinv, del1, del2, hw, ldE, temperature, total4, slot(AM_DA));
-  prof_end(pid_da, stream);
-  DCN_CHECK_LAUNCH("dA");
+  if ((rc = P.nt(DO1, F2, dP1, ldE, bsE, nullptr, 0, slot(AM_DP1)))) return rc;
+  if ((rc = P.nt(F1, DO2, dP2, ldE, bsE, nullptr, 0, slot(AM_DP2)))) return rc;
+  // 3. dA (over dP1; pads -> 0).  gemm3.hip: in split form straight away, scaled by a bound from the two maxima the products above left
+  if (P.g3 && (rc = coattn_da_bound(slot(AM_DP1), slot(AM_DP2), temperature, slot(AM_DA), stream))) return rc;
+  if ((rc = coattn_dA(E, dP1, dP2, rinv, cinv, del1, del2, b, hw, temperature, slot(AM_DA), P.g3, stream))) return rc;
   // 4. d_f1 (+)= dA f2 + E (dO2 / colsum)                                   (NN x2)
-  gemm_params(p, dP1, ldE, (long long)hw * ldE, f2, ldf, bsf, d_f1, lddf, bsdf, hw, c, ldE, b);
-  p.bmode = 1; p.kvalid = hw; p.accumulate = accumulate; p.amax_a = slot(AM_DA); p.amax_b = slot(AM_ONE);
-  if ((rc = igemm_launch(p, stream))) return rc;
-  gemm_params(p, E, ldE, (long long)hw * ldE, dO2s, c, (long long)hw * c, d_f1, lddf, bsdf, hw, c, ldE, b);
-  p.bmode = 1; p.kvalid = hw; p.accumulate = 1; p.amax_a = slot(AM_ONE); p.amax_b = slot(AM_DO2S);
-  if ((rc = igemm_launch(p, stream))) return rc;
+  if ((rc = P.nn(DA, F2, d_f1, lddf, bsdf, nullptr, accumulate))) return rc;
+  if ((rc = P.nn(Eo, DO2S, d_f1, lddf, bsdf, nullptr, 1))) return rc;
   // 5. d_f2 (+)= dA^T f1 + E^T (dO1 / rowsum)                               (TN x2)
-  rc = tn_gemm_batched(dP1, ldE, (long long)hw * ldE, f1, ldf, bsf, d_f2, lddf, bsdf,
-                       nullptr, hw, ldE, c, hw, b, accumulate, stream, slot(AM_DA), slot(AM_ONE));
-  if (rc) return rc;
-  return tn_gemm_batched(E, ldE, (long long)hw * ldE, dO1s, c, (long long)hw * c, d_f2, lddf, bsdf,
-                         nullptr, hw, ldE, c, hw, b, 1, stream, slot(AM_ONE), slot(AM_DO1S));
+  if ((rc = P.tn(DA, F1, d_f2, lddf, bsdf, nullptr, accumulate))) return rc;
+  return P.tn(Eo, DO1S, d_f2, lddf, bsdf, nullptr, 1);
 }

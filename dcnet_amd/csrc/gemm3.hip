@@ -18,6 +18,7 @@
 // lanes (zeros).  Roofline: MFMA, 838.9 TFLOP/s (three f16 MFMAs per product: (l,h) + (h,l) + (h,h)).
 #include "igemm.h"
 #include "prof.h"
+#include "split4.h"
 
 namespace {
 
@@ -34,14 +35,6 @@ constexpr int G3_BM = 256, G3_BN = 256, G3_STAGES = 4;
 constexpr int G3_TILE = 256 * 64;                 // bytes of one operand tile of a K-slice (R: [256 rows][64 B]; T: [16 k][1024 B])
 constexpr int G3_STAGE = 2 * G3_TILE;
 constexpr int G3_LDS = G3_STAGES * G3_STAGE;      // 128 KB
-
-__device__ __forceinline__ float g3_pow2_scale(unsigned amax_bits) {      // = igemm.hip pow2_scale
-  const int be = (int)((amax_bits >> 23) & 0xFF);
-  if (be == 0 || be == 255) return 1.f;
-  int e = 14 - (be - 126);
-  e = e > 100 ? 100 : (e < -100 ? -100 : e);
-  return __uint_as_float((unsigned)(e + 127) << 23);
-}
 
 struct G3Params {
   const float* A; const float* B; float* C;       // A, B in split form
@@ -272,7 +265,7 @@ __global__ __launch_bounds__(512, 1) void gemm3_kernel(const G3Params p) {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 
   // ---- epilogue: 1 / (s_a s_b), row scale, accumulate, store --------------------------------------------------------------------
-  const float dq = 1.f / (g3_pow2_scale(amax_read(p.amax_a)) * g3_pow2_scale(amax_read(p.amax_b)));      // powers of two: exact
+  const float dq = 1.f / (split_pow2_scale(amax_read(p.amax_a)) * split_pow2_scale(amax_read(p.amax_b)));      // powers of two: exact
   float* __restrict__ cb = p.C + batch * p.c_bs;
   const float* rs = p.row_scale ? p.row_scale + batch * p.rs_bs : nullptr;
   float vmax = 0.f;
@@ -303,7 +296,7 @@ __global__ __launch_bounds__(512, 1) void gemm3_kernel(const G3Params p) {
 // x (fp32 [batch][rows][c], row stride ld) -> its split form, dense or in place: 8 elements per thread
 __global__ __launch_bounds__(256) void presplit_kernel(const float* __restrict__ src, int ld, long long bs, float* __restrict__ dst, int ldd,
                                                         long long bsd, int rows, int c, long long total8, const unsigned* __restrict__ amax) {
-  const float s = g3_pow2_scale(amax_read(amax));
+  const float s = split_pow2_scale(amax_read(amax));
   const int c8 = c >> 3;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total8; i += (long long)gridDim.x * 256) {
     const long long row_all = i / c8; const int o = (int)(i - row_all * c8);

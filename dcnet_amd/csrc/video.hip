@@ -6,8 +6,8 @@
 //                         split form (gemm3.hip) in one pass: the windowed form normalises once per window and splits both
 //                         operands of every co-attention call, 2 (K - 1) times per frame.
 //   dcn_coattn_bank_fwd   co-attention (test_DCNet_model.py:259-274) of a run of pairs with the operands taken from the split bank:
-//                         one affinity, then either or both attended features.  Same kernels and launch shapes as dcn_coattn_fwd
-//                         behind its pre-split (coattn.h); shapes gemm3.hip does not take go through dcn_coattn_fwd itself.
+//                         one affinity, then either or both attended features.  The sequence dcn_coattn_fwd runs behind its pre-split
+//                         (coattn.h: coattn_fwd_operands); shapes gemm3.hip does not take read the fp32 rows instead.
 //   dcn_bank_write_b16    bf16 storage ("bf16s"): the same pass with the row in bf16 as a third output, bank / split each on request;
 //   dcn_bank_concat_b16   corr_conv's bf16 input [f_centre | f_attn] from those rows and the fp32 attended features, one pass (instead of
 //                         a copy of the centre rows, a strided fp32 write of the attended half and a cast pass);
@@ -19,23 +19,17 @@
 #include "igemm.h"
 #include "prof.h"
 #include "coattn.h"
+#include "split4.h"
 #include "b16_pack.h"
-
-extern "C" int64_t dcn_coattn_e_size(int b, int hw);
-extern "C" int dcn_coattn_fwd(const float* f1, const float* f2, int ldf, int64_t bsf, float* f1_attn, float* f2_attn, int ldo,
-                              int64_t bso, float* E, float* rinv, float* cinv, float* ws, int b, int hw, int c, float temperature,
-                              void* stream);
 
 namespace {
 
-typedef _Float16 f16x4v_t __attribute__((ext_vector_type(4)));
-constexpr float BANK_SPLIT_SCALE = 8192.f;        // = gemm3.hip's power-of-two scale of the abs-max word 1.0 (unit-norm rows)
 constexpr int VF_MAXK = 64;                       // post.hip PK_MAXK
 constexpr int VF_MAXR = 32;                       // post.hip PF_MAXR
 
 // One wave per row, the arithmetic of score.hip's l2norm_score_fwd_kernel (same fma chain, same wave reduction: bitwise its result),
 // V4 16-byte loads per lane.  A lane's four channels are half of an 8-element run of the split form: 8 bytes of the high piece,
-// 8 bytes of the low piece (as exp_sums_kernel<true> writes E).
+// 8 bytes of the low piece (split4.h, as exp_sums_kernel writes E).
 template <int V4>
 __global__ __launch_bounds__(256) void bank_write_kernel(const float* __restrict__ x, int ldx, float* __restrict__ bank,
                                                          float* __restrict__ split, int64_t rows, int c) {
@@ -61,13 +55,7 @@ __global__ __launch_bounds__(256) void bank_write_kernel(const float* __restrict
     if (ch < c) {
       const f32x4 o = v[k] * inv;
       *reinterpret_cast<f32x4*>(bank + row * c + ch) = o;
-      const f32x4 ts = o * BANK_SPLIT_SCALE;
-      const f16x4v_t h = {(_Float16)ts[0], (_Float16)ts[1], (_Float16)ts[2], (_Float16)ts[3]};
-      const f16x4v_t l = {(_Float16)(ts[0] - (float)h[0]), (_Float16)(ts[1] - (float)h[1]), (_Float16)(ts[2] - (float)h[2]),
-                          (_Float16)(ts[3] - (float)h[3])};
-      unsigned char* run = reinterpret_cast<unsigned char*>(split + row * c + (ch & ~7)) + (ch & 4) * 2;
-      *reinterpret_cast<f16x4v_t*>(run) = h;
-      *reinterpret_cast<f16x4v_t*>(run + 16) = l;
+      split4_store(split + row * c, ch, o * SPLIT_SCALE_ONE);
     }
   }
 }
@@ -101,15 +89,7 @@ __global__ __launch_bounds__(256) void bank_write_b16_kernel(const float* __rest
       const f32x4 o = v[k] * inv;
       *reinterpret_cast<b16io::bf16x4_t*>(rows16 + row * c + ch) = b16io::pack4(o);
       if (bank) *reinterpret_cast<f32x4*>(bank + row * c + ch) = o;
-      if (split) {
-        const f32x4 ts = o * BANK_SPLIT_SCALE;
-        const f16x4v_t h = {(_Float16)ts[0], (_Float16)ts[1], (_Float16)ts[2], (_Float16)ts[3]};
-        const f16x4v_t l = {(_Float16)(ts[0] - (float)h[0]), (_Float16)(ts[1] - (float)h[1]), (_Float16)(ts[2] - (float)h[2]),
-                            (_Float16)(ts[3] - (float)h[3])};
-        unsigned char* run = reinterpret_cast<unsigned char*>(split + row * c + (ch & ~7)) + (ch & 4) * 2;
-        *reinterpret_cast<f16x4v_t*>(run) = h;
-        *reinterpret_cast<f16x4v_t*>(run + 16) = l;
-      }
+      if (split) split4_store(split + row * c, ch, o * SPLIT_SCALE_ONE);
     }
   }
 }
@@ -262,23 +242,12 @@ extern "C" int dcn_coattn_bank_fwd(const float* f1, const float* f2, const float
     t_ = f1s; f1s = f2s; f2s = t_;
     f1_attn = f2_attn; f2_attn = nullptr;
   }
-  if (!coattn_on_gemm3(b, hw, c))
-    return dcn_coattn_fwd(f1, f2, c, bsf, f1_attn, f2_attn, ldo, bso, E, rinv, cinv, ws, b, hw, c, temperature, stream_);
-  const int ldE = coattn_ld_pad(hw);
-  const long long bsE = (long long)hw * ldE;
-  unsigned* am = coattn_ws_amax(ws, b, hw);
-  int rc = coattn_amax_init(am, stream);
+  // dcn_coattn_fwd's sequence on operands that need no pre-split: the path that runs reads its own form of the bank
+  unsigned* one = coattn_ws_amax(ws, b, hw);       // word 0: the constant 1 (unit-norm rows, E <= 1)
+  const int rc = coattn_amax_init(one, stream);
   if (rc) return rc;
-  const unsigned* one = am;       // word 0: the constant 1 (unit-norm rows, E <= 1)
-  // 1. A = f1 . f2^T -> E                                                (NT), operands straight from the split bank
-  if ((rc = gemm3_launch(f1s, c, bsf, 0, f2s, c, bsf, 0, E, ldE, bsE, nullptr, 0, hw, hw, c, b, 0, one, one, stream))) return rc;
-  // 2. E = exp(t*A - t) in split form, rinv, cinv
-  if ((rc = coattn_exp_sums(E, b, hw, temperature, rinv, cinv, ws, true, stream))) return rc;
-  // 3. f1_attn = diag(rinv) E f2                                         (NN)
-  if ((rc = gemm3_launch(E, ldE, bsE, 0, f2s, c, bsf, 1, f1_attn, ldo, bso, rinv, hw, hw, c, hw, b, 0, one, one, stream))) return rc;
-  // 4. f2_attn = diag(cinv) E^T f1                                       (TN)
-  if (f2_attn) rc = gemm3_launch(E, ldE, bsE, 1, f1s, c, bsf, 1, f2_attn, ldo, bso, cinv, hw, hw, c, hw, b, 0, one, one, stream);
-  return rc;
+  return coattn_fwd_operands(CoOperand{f1, c, bsf, f1s, c, bsf, one}, CoOperand{f2, c, bsf, f2s, c, bsf, one}, f1_attn, f2_attn, ldo, bso,
+                             E, rinv, cinv, ws, b, hw, c, temperature, stream);
 }
 
 extern "C" int dcn_post_fusion_bank(const float* feats, const float* scores, int n, int k, int r, int e, float* fused, int64_t* best,

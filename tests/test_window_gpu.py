@@ -1,5 +1,6 @@
-"""GPU: window training — the centre-versus-neighbours co-attention of csrc/coattn_center.hip against fp64 torch and on the engines it
-must run on, the window model in train mode through functions.CoAttentionWindow and losses.window_loss against the oracle, and the
+"""GPU: window training — the centre-versus-neighbours co-attention of csrc/coattn_center.hip (host code: the kernels it launches are the
+pair node's, in csrc/coattn.hip, in their row-only forms) against fp64 torch, on the engines it must run on and bit for bit against the
+pair forward, the window model in train mode through functions.CoAttentionWindow and losses.window_loss against the oracle, and the
 captured window step (graph.GraphedTrainStep(..., n_frame=K)) against the eager one it was captured from."""
 import pytest
 import torch
@@ -71,6 +72,23 @@ def test_coattn_center_fwd_bwd(dev, b, t, g, c):
     # Engines.  Per neighbour the call runs 2 products forward (A = f_ctr . f_j^T, attn = E . f_j) and 4 backward (dP = d_attn . f_j^T,
     # dA . f_j, dA^T . f_ctr, E^T . d_attn / rowsum): 6 * (T - 1) launches on gemm3.hip where coattn_on_gemm3 holds (tag 40), none below.
     assert ran == (6 * (t - 1) if _on_gemm3(hw, c) else 0), ("which engine ran the products", ran)
+
+
+@pytest.mark.parametrize("b,g,c", [(2, 5, 96),       # tile engines; HW = 25, neither a multiple of 4 nor of 32
+                                   (2, 23, 256)])    # gemm3, an odd row count
+def test_window_of_two_is_the_pair_forward_bitwise(dev, b, g, c):
+    """A window of T = 2 (ctr = 1) attends from frame 1 to frame 0: the same A product, the same row sums and the same E . f product as
+    the first direction of the pair node on (f1, f2) = (frame 1, frame 0).  Both run ONE set of kernels and one product path, so the
+    two outputs (each in a 2C-wide slice) are equal bit for bit."""
+    from dcnet_amd import ops
+    hw, temp = g * g, 10.0
+    clips = F.normalize(_rand(b, 2, hw, c, seed=80), dim=3).to(dev)
+    win = torch.zeros(1, b, hw, 2 * c, device=dev)
+    pair = torch.zeros(b, hw, 2 * c, device=dev)
+    ops.coattn_center_fwd(clips, 1, win[..., c:], temp)
+    ops.coattn_fwd(clips[:, 1], clips[:, 0], pair[..., c:], None, temp)
+    assert float(pair[..., c:].abs().max()) > 0
+    assert torch.equal(win[0], pair), ("window and pair forward differ", maxdiff(win[0], pair))
 
 
 @pytest.mark.parametrize("b,t,g,c", KERNEL_SHAPES)
