@@ -197,6 +197,10 @@ SIGNATURES = {
     "dcn_bank_write_b16": (I, [P, I, P, P, P, L, I, P]),
     "dcn_bank_concat_b16": (I, [P, L, P, I, L, P, I, I, I, P]),
     "dcn_coattn_bank_form": (I, [I, I]),
+    "dcn_post_nms": (I, [P, I, I, F, P, P]),
+    "dcn_tube_transitions": (I, [P, P, I, I, I, I, I, I, F, F, P, P]),
+    "dcn_tube_forward": (I, [P, P, P, P, I, I, I, I, I, P, P, P]),
+    "dcn_tube_backtrack": (I, [P, P, I, I, I, P, P, P]),
 }
 _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap_rows", "dcn_conv2d_pre_supported",
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",

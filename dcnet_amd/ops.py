@@ -1801,6 +1801,108 @@ def post_fusion_bank(feats, scores, n_frame):
     return best, fused
 
 
+# ---- tube linking (csrc/tube.hip) ------------------------------------------------------------------------------------
+TUBE_MAXK = 64
+TUBE_WS_BYTES = 64 << 20             # budget of the transition scores W of one tube_link range (it walks the video in ranges)
+
+
+def tube_ranges(q, n, k, ws_bytes=None):
+    """The frame ranges [(t0, t1), ...] tube_link walks: max(1, ws_bytes // (q*k*k*4)) frames each, the last one shorter."""
+    ws = TUBE_WS_BYTES if ws_bytes is None else ws_bytes
+    if q < 1 or n < 1 or k < 1:
+        raise ValueError(f"tube_ranges: q, n, k must be >= 1 (q={q} n={n} k={k})")
+    per = max(1, int(ws) // (q * k * k * 4))
+    return [(t0, min(n, t0 + per)) for t0 in range(0, n, per)]
+
+
+def _chk_keep(keep, shape, name):
+    if not (keep.is_cuda and keep.dtype in (torch.uint8, torch.bool) and keep.is_contiguous() and tuple(keep.shape) == tuple(shape)):
+        raise ValueError(f"{name}: keep must be a contiguous uint8 / bool CUDA tensor {tuple(shape)}, got {keep.dtype} {keep.device} "
+                         f"{tuple(keep.shape)}")
+
+
+def post_nms(boxes, iou_thr, out=None):
+    """csrc/tube.hip: boxes (B,k,4) fp32 contiguous xyxy, k <= 64 -> keep (B,k) uint8: greedy NMS in index order per row (candidate i
+    is kept iff no kept j < i has IoU > iou_thr).  ``out``: a contiguous uint8 (B,k) tensor or view to write into."""
+    _chk(boxes, "post_nms boxes")
+    if boxes.dim() != 3 or boxes.shape[2] != 4 or boxes.shape[0] < 1 or not 1 <= boxes.shape[1] <= TUBE_MAXK:
+        raise ValueError(f"post_nms: boxes must be (B,k,4) with B >= 1 and 1 <= k <= {TUBE_MAXK}, got {tuple(boxes.shape)}")
+    B, k = boxes.shape[:2]
+    if out is None:
+        out = torch.empty((B, k), dtype=torch.uint8, device=boxes.device)
+    elif out.dtype != torch.uint8:
+        raise ValueError(f"post_nms: out must be uint8, got {out.dtype}")
+    _chk_keep(out, (B, k), "post_nms")
+    lib().post_nms(boxes.data_ptr(), B, k, float(iou_thr), out.data_ptr(), _s())
+    return out
+
+
+def tube_link(boxes, unary, feats=None, keep=None, w_iou=1.0, w_feat=1.0):
+    """csrc/tube.hip: boxes (Q,n,k,4), unary (Q,n,k), feats (Q,n,k,E) or None (then w_feat must be 0), keep (Q,n,k) uint8 / bool or
+    None — fp32 contiguous, k <= 64.  The path that maximises sum_t unary[t,p_t] + sum_{t>=1} W[t][p_{t-1}][p_t] over kept candidates,
+    W = w_iou * IoU + w_feat * <feat, feat>.  Returns (path (Q,n) int64, score (Q,)).  The transition scores live in a workspace of at
+    most TUBE_WS_BYTES (at least one frame): the video is walked in the ranges of ``tube_ranges``, delta carried between them.  A frame
+    with no kept candidate is a caller error that nothing detects."""
+    _chk(boxes, "tube_link boxes"); _chk(unary, "tube_link unary")
+    if boxes.dim() != 4 or boxes.shape[3] != 4 or min(boxes.shape[:3]) < 1 or boxes.shape[2] > TUBE_MAXK:
+        raise ValueError(f"tube_link: boxes must be (Q,n,k,4) with Q, n >= 1 and 1 <= k <= {TUBE_MAXK}, got {tuple(boxes.shape)}")
+    Q, n, k = boxes.shape[:3]
+    if tuple(unary.shape) != (Q, n, k):
+        raise ValueError(f"tube_link: unary must be {(Q, n, k)}, got {tuple(unary.shape)}")
+    w_iou, w_feat = float(w_iou), float(w_feat)
+    if not (w_iou >= 0.0 and w_feat >= 0.0):
+        raise ValueError(f"tube_link: weights must be >= 0 (w_iou={w_iou} w_feat={w_feat})")
+    E = 0
+    if feats is None:
+        if w_feat != 0.0:
+            raise ValueError(f"tube_link: feats is None but w_feat = {w_feat}: the appearance term needs the features (or w_feat = 0)")
+    else:
+        _chk(feats, "tube_link feats")
+        if feats.dim() != 4 or tuple(feats.shape[:3]) != (Q, n, k) or feats.shape[3] < 1:
+            raise ValueError(f"tube_link: feats must be {(Q, n, k)} + (E,), got {tuple(feats.shape)}")
+        E = feats.shape[3]
+    if keep is not None:
+        _chk_keep(keep, (Q, n, k), "tube_link")
+    dev = boxes.device
+    ranges = tube_ranges(Q, n, k)
+    W = torch.empty((Q, ranges[0][1] - ranges[0][0], k, k), dtype=torch.float32, device=dev)
+    delta = torch.empty((Q, k), dtype=torch.float32, device=dev)
+    backptr = torch.empty((Q, n, k), dtype=torch.uint8, device=dev)
+    for t0, t1 in ranges:
+        tube_transitions(boxes, feats, t0, t1, w_iou, w_feat, W)
+        tube_forward(W, unary, keep, delta, t0, t1, backptr)
+    return tube_backtrack(backptr, delta)
+
+
+def tube_transitions(boxes, feats, t0, t1, w_iou, w_feat, W=None):
+    """One entry of tube_link (its arguments, already checked): the transition scores of frames t0 <= t < t1 into W (Q, >= t1-t0, k, k)
+    contiguous, read as [Q][t1-t0][k][k]; the row of frame 0 is not written.  Returns W."""
+    Q, n, k = boxes.shape[:3]
+    if W is None:
+        W = torch.empty((Q, t1 - t0, k, k), dtype=torch.float32, device=boxes.device)
+    if W.numel() < Q * (t1 - t0) * k * k:
+        raise ValueError(f"tube_transitions: W holds {W.numel()} floats, frames {t0} .. {t1 - 1} need {Q * (t1 - t0) * k * k}")
+    lib().tube_transitions(boxes.data_ptr(), _p(feats), Q, n, k, 0 if feats is None else feats.shape[3], t0, t1, float(w_iou),
+                           float(w_feat), W.data_ptr(), _s())
+    return W
+
+
+def tube_forward(W, unary, keep, delta, t0, t1, backptr):
+    """One entry of tube_link: the Viterbi step over frames t0 <= t < t1; delta (Q,k) holds the delta of frame t0 - 1 (unread for
+    t0 == 0) and is overwritten with that of frame t1 - 1; rows t0 ... t1-1 of backptr (Q,n,k) uint8 are written."""
+    Q, n, k = unary.shape
+    lib().tube_forward(W.data_ptr(), unary.data_ptr(), _p(keep), delta.data_ptr() if t0 else 0, Q, n, k, t0, t1, delta.data_ptr(),
+                       backptr.data_ptr(), _s())
+
+
+def tube_backtrack(backptr, delta):
+    """One entry of tube_link: backptr (Q,n,k) uint8, delta (Q,k) of the last frame -> (path (Q,n) int64, score (Q,))."""
+    Q, n, k = backptr.shape
+    path = torch.empty((Q, n), dtype=torch.int64, device=delta.device); score = torch.empty(Q, dtype=torch.float32, device=delta.device)
+    lib().tube_backtrack(backptr.data_ptr(), delta.data_ptr(), Q, n, k, path.data_ptr(), score.data_ptr(), _s())
+    return path, score
+
+
 def box_iou(b1, b2):
     _chk(b1, "box_iou"); _chk(b2, "box_iou")
     iou = torch.empty(b1.shape[0], dtype=torch.float32, device=b1.device)

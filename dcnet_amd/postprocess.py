@@ -12,6 +12,9 @@ no vendor sort, no BLAS, and no CPU path (CPU tensors raise).  The same computat
                           un-letterbox + clamp, and the 512-d correspondence feature of each winning cell
   * ``temporal_fusion``   candidate-to-candidate similarity against every frame of the window, max over the
                           reference frame's candidates, softmax over frames, score fusion, arg-max
+  * ``nms_keep``          greedy NMS mask among a centre's candidates (``csrc/tube.hip``, ``dcn_post_nms``)
+  * ``link_tubes``        one temporally consistent track per query through the candidates of consecutive centres:
+                          IoU + feature transitions, Viterbi path (``dcn_tube_transitions / _forward / _backtrack``)
   * ``save_cache_entry`` / ``load_cache_entry`` / ``fuse_from_cache``   the reference's on-disk cache
                           format (``pred_bbox_topk`` (k,1,4), ``pred_score_topk`` list, ``visu_feat`` (k,1,E))
                           and its missing-neighbour rule (fall back to the centre entry, weight zeroed)
@@ -70,6 +73,37 @@ def temporal_fusion(center_feat: torch.Tensor, ref_feat: torch.Tensor, ref_score
         from . import ops
         return ops.post_fusion(center_feat.float().contiguous(), ref_feat.float().contiguous(), ref_score.float().contiguous(), valid)
     raise RuntimeError("dcnet_amd.postprocess.temporal_fusion: HIP kernels only — move the tensors to the GPU (no CPU path)")
+
+
+def nms_keep(boxes: torch.Tensor, iou_thr: float) -> torch.Tensor:
+    """Greedy non-maximum suppression in index order on ``csrc/tube.hip`` (``dcn_post_nms``).
+
+    boxes (B,k,4) xyxy, k <= 64, row by row in score order (what ``topk_candidates`` hands out).
+    Returns keep (B,k) bool: candidate i is kept iff no kept j < i has IoU(j, i) > iou_thr (strict, fp32; IoU of ``ops.box_iou``
+    with widths and heights clamped at 0).  A mask: nothing is compacted."""
+    if not (isinstance(boxes, torch.Tensor) and boxes.is_cuda):
+        raise RuntimeError("dcnet_amd.postprocess.nms_keep: HIP kernels only — move the tensors to the GPU (no CPU path)")
+    from . import ops
+    return ops.post_nms(boxes.float().contiguous(), iou_thr).view(torch.bool)
+
+
+def link_tubes(boxes: torch.Tensor, unary: torch.Tensor, feats: Optional[torch.Tensor] = None, keep: Optional[torch.Tensor] = None,
+               iou_weight: float = 1.0, feat_weight: float = 1.0):
+    """One temporally consistent track per query through the candidates of n consecutive centres, on ``csrc/tube.hip``.
+
+    boxes (Q,n,k,4) xyxy, unary (Q,n,k), feats (Q,n,k,E) or None (only with feat_weight = 0), keep (Q,n,k) bool / uint8 or None (all
+    kept); k <= 64; weights >= 0.  The path p maximises
+        sum_t unary[t, p_t]  +  sum_{t >= 1} iou_weight * IoU(box[t-1, p_{t-1}], box[t, p_t]) + feat_weight * <feat[t-1, p_{t-1}], feat[t, p_t]>
+    over kept candidates (Viterbi; equal values resolve to the lowest index at every step and at the end).  fp32 in every precision
+    mode.  Returns (path (Q,n) int64, score (Q,), tube_boxes (Q,n,4)).  Every frame needs a kept candidate: a frame without one is a
+    caller error that is not detected (detecting it would synchronise the host)."""
+    if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (boxes, unary) + tuple(t for t in (feats, keep) if t is not None)):
+        raise RuntimeError("dcnet_amd.postprocess.link_tubes: HIP kernels only — move the tensors to the GPU (no CPU path)")
+    from . import ops
+    boxes = boxes.float().contiguous()
+    path, score = ops.tube_link(boxes, unary.float().contiguous(), None if feats is None else feats.float().contiguous(),
+                                None if keep is None else keep.contiguous(), iou_weight, feat_weight)
+    return path, score, torch.gather(boxes, 2, path[:, :, None, None].expand(-1, -1, 1, 4))[:, :, 0]
 
 
 # ---- the reference's cache files ---------------------------------------------------------------------

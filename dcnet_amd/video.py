@@ -10,7 +10,9 @@ frames is computed once in each of their windows.  Here:
     (``dcn_coattn_bank_fwd`` reads bank rows through strides: the pairs of distance d are bank[a0:a0+n] against bank[a0+d:a0+d+n]);
   * the language branch runs once per query; nothing before ``sim_score`` and the fusion head depends on the sentence, so any
     number of queries share the visual work;
-  * the temporal re-scoring reads the candidates of the centres in place (``dcn_post_fusion_bank``).
+  * the temporal re-scoring reads the candidates of the centres in place (``dcn_post_fusion_bank``);
+  * optionally (``link=TubeLink()``) the candidates of ALL centres are joined into one track per query: an NMS mask per centre and a
+    Viterbi path over IoU + correspondence-feature transitions (``csrc/tube.hip``).
 
 The window rule is the reference's (``getChunk``):
 
@@ -186,7 +188,9 @@ class VideoResult:
     ``only_obj[q][s]``: the n_frame model's outputs of query q on scale s with the centres as the batch dimension; ``corr_feat[s]``
     (n,E,g,g) is shared by the queries.  ``boxes`` (Q,n,4): ``losses.decode_boxes`` (letterbox pixels), or source pixels when the
     letterbox meta was given.  With ``topk``: ``cand_boxes`` (Q,n,k,4), ``cand_scores`` (Q,n,k), ``cand_feats`` (Q,n,k,E) and the
-    temporally fused choice ``best`` (Q,n), ``fused`` (Q,n,k), ``fused_boxes`` (Q,n,4)."""
+    temporally fused choice ``best`` (Q,n), ``fused`` (Q,n,k), ``fused_boxes`` (Q,n,4).  With ``link``: ``cand_keep`` (Q,n,k) bool, the
+    candidates that survive the NMS, and the linked track ``tube`` (Q,n) int64 (candidate index per centre), ``tube_score`` (Q,),
+    ``tube_boxes`` (Q,n,4)."""
     centres: torch.Tensor
     outbox: List[List[torch.Tensor]]
     sim: List[List[torch.Tensor]]
@@ -200,6 +204,10 @@ class VideoResult:
     best: Optional[torch.Tensor] = None
     fused: Optional[torch.Tensor] = None
     fused_boxes: Optional[torch.Tensor] = None
+    cand_keep: Optional[torch.Tensor] = None
+    tube: Optional[torch.Tensor] = None
+    tube_score: Optional[torch.Tensor] = None
+    tube_boxes: Optional[torch.Tensor] = None
 
     def query(self, q: int = 0):
         """The n_frame model's return tuple (outbox, sim, loc, corr_feat, only_obj) of query q."""
@@ -218,7 +226,27 @@ class VideoResult:
         return VideoResult(centres=torch.cat([p.centres for p in parts]), outbox=per_q("outbox"), sim=per_q("sim"), loc=per_q("loc"),
                            corr_feat=[torch.cat([p.corr_feat[s] for p in parts]) for s in range(3)], only_obj=per_q("only_obj"),
                            boxes=torch.cat([p.boxes for p in parts], dim=1), cand_boxes=opt("cand_boxes"),
-                           cand_scores=opt("cand_scores"), cand_feats=opt("cand_feats"))
+                           cand_scores=opt("cand_scores"), cand_feats=opt("cand_feats"), cand_keep=opt("cand_keep"))
+
+
+@dataclass
+class TubeLink:
+    """How ``VideoGrounder.link`` joins the candidates of consecutive centres into one track per query (``postprocess.link_tubes``).
+    iou_weight, feat_weight  weights (>= 0) of the IoU and of the correspondence-feature dot product of two consecutive candidates
+    nms_iou   IoU threshold of the greedy NMS among a centre's candidates (``postprocess.nms_keep``); None: no NMS
+    unary     "score": the candidates' confidences; "fused": their temporally fused scores (``fuse``)"""
+    iou_weight: float = 1.0
+    feat_weight: float = 1.0
+    nms_iou: Optional[float] = 0.6
+    unary: str = "score"
+
+    def __post_init__(self):
+        if self.unary not in ("score", "fused"):
+            raise ValueError(f"TubeLink.unary = {self.unary!r}: expected \"score\" or \"fused\"")
+        if not (self.iou_weight >= 0 and self.feat_weight >= 0):
+            raise ValueError(f"TubeLink: weights must be >= 0 (iou_weight = {self.iou_weight!r}, feat_weight = {self.feat_weight!r})")
+        if self.nms_iou is not None and not 0 <= self.nms_iou <= 1:
+            raise ValueError(f"TubeLink.nms_iou = {self.nms_iou!r}: an IoU threshold in [0, 1], or None for no NMS")
 
 
 class VideoGrounder:
@@ -233,12 +261,15 @@ class VideoGrounder:
              co-attention sub-batches by ``ops.COATTN_BANK_WS_BYTES`` on its own)
     topk     k: also the k best candidates of every centre and their temporal fusion over windows of n_frame centres
              (n_frame <= 32, k <= 64)
+    link     a ``TubeLink``: also one temporally consistent track per query through the candidates of all centres (needs ``topk``);
+             None: nothing is linked and the tube fields of the result stay None
 
     ``push`` keeps the bank rows of the last n_frame // 2 frames (no pair reaches further back; per scale, both tensors of the mode) and the
     unfinished means of the last ceil(n_frame / 2) - 1 centres between calls, so chunked and streamed runs encode every frame once
     too.  Nothing here synchronises the host with the device."""
 
-    def __init__(self, model, n_frame: int = 5, border: str = "valid", chunk: int = 32, topk: Optional[int] = None):
+    def __init__(self, model, n_frame: int = 5, border: str = "valid", chunk: int = 32, topk: Optional[int] = None,
+                 link: Optional[TubeLink] = None):
         from .model import grounding_model
         self.n_frame, self.border = _check_window(n_frame), _check_border(border)
         if not isinstance(model, grounding_model):
@@ -249,7 +280,11 @@ class VideoGrounder:
             raise ValueError(f"chunk = {chunk!r}: frames per step, an int >= 1")
         if topk is not None and (not isinstance(topk, int) or not 1 <= topk <= 64 or n_frame > 32):
             raise ValueError(f"topk = {topk!r} with n_frame = {n_frame}: the temporal fusion takes topk in 1 ... 64 and n_frame <= 32")
-        self.model, self.chunk, self.topk = model, chunk, topk
+        if link is not None and not isinstance(link, TubeLink):
+            raise TypeError(f"link: expected a dcnet_amd.video.TubeLink or None, got {type(link).__name__}")
+        if link is not None and topk is None:
+            raise ValueError("link: tube linking joins the top-k candidates of the centres, give topk as well")
+        self.model, self.chunk, self.topk, self._link = model, chunk, topk, link
         self._lang = None
 
     # ---- state ----------------------------------------------------------------------------------------------------------------
@@ -403,6 +438,12 @@ class VideoGrounder:
                           boxes=torch.stack(boxes))
         if cands:
             res.cand_boxes, res.cand_scores, res.cand_feats = (torch.stack([c[k] for c in cands]) for k in range(3))
+            if self._link is not None:
+                Q, k = res.cand_scores.shape[0], res.cand_scores.shape[2]
+                if self._link.nms_iou is None:
+                    res.cand_keep = torch.ones((Q, nc, k), dtype=torch.bool, device=dev)
+                else:
+                    res.cand_keep = postprocess.nms_keep(res.cand_boxes.view(Q * nc, k, 4), self._link.nms_iou).view(Q, nc, k)
         self._acc_lo = hi
         return res
 
@@ -515,6 +556,24 @@ class VideoGrounder:
         res.fused_boxes = torch.gather(res.cand_boxes, 2, res.best[:, :, None, None].expand(-1, -1, 1, 4))[:, :, 0]
         return res
 
+    def link(self, res: VideoResult) -> VideoResult:
+        """The linked track of every query through the candidates of ``res`` (``link`` set): ``res`` covers consecutive centres — the
+        result of ``run``, or the ``VideoResult.cat`` of the parts of a stream.  Fills tube / tube_score / tube_boxes.  With
+        ``TubeLink.unary == "fused"`` the result must have been through ``fuse``."""
+        from . import postprocess
+        cfg = self._link
+        if cfg is None:
+            raise ValueError("link: the grounder was built without link")
+        if res.cand_keep is None:
+            raise ValueError("link: the result carries no candidates of a grounder with link (cand_keep is None)")
+        unary = res.cand_scores if cfg.unary == "score" else res.fused
+        if unary is None:
+            raise ValueError("link: TubeLink.unary is \"fused\" but the result has no fused scores, call fuse(res) first")
+        feats = res.cand_feats if cfg.feat_weight > 0 else None
+        res.tube, res.tube_score, res.tube_boxes = postprocess.link_tubes(res.cand_boxes, unary, feats, res.cand_keep, cfg.iou_weight,
+                                                                          cfg.feat_weight)
+        return res
+
     @torch.no_grad()
     def run(self, image: torch.Tensor, word_id: torch.Tensor, meta=None) -> VideoResult:
         """A whole video at once: image (F,3,S,S) CUDA, word_id (Q,L) or (L,), meta = (ratio, dw, dh) per frame or None."""
@@ -532,7 +591,9 @@ class VideoGrounder:
             parts.append(self.push(image[i0:i0 + self.chunk]))
         parts.append(self.flush())
         res = VideoResult.cat(parts)
-        return self.fuse(res) if self.topk is not None else res
+        if self.topk is not None:
+            res = self.fuse(res)
+        return self.link(res) if self._link is not None else res
 
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
@@ -565,6 +626,7 @@ def main(argv=None):
     ap.add_argument("--chunk", type=int, default=32)
     ap.add_argument("--queries", type=int, default=1)
     ap.add_argument("--topk", type=int, default=None)
+    ap.add_argument("--link", action="store_true", help="link the top-k candidates into one track per query (needs --topk); prints the tube boxes")
     ap.add_argument("--raw-frames", action="store_true", help="375x500 uint8 frames through prep.prepare_clips(augment=False); prints source-pixel boxes")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--precision", default="fp32", choices=sorted(BANK_BYTES_PER_VALUE), help="ops.set_precision mode of the run")
@@ -594,7 +656,9 @@ def _main_run(a):
         p = prep.prepare_clips(frames, [np.tile(np.array([[10, 10, 100, 100]]), (a.frames, 1))], [["a phrase"] * a.frames], a.size, False)
         image, meta = p.image, (p.ratio, p.dw, p.dh)
     image, word_id = image.to(dev), word_id.to(dev)
-    vg = VideoGrounder(m, n_frame=a.n_frame, border=a.border, chunk=a.chunk, topk=a.topk)
+    if a.link and a.topk is None:
+        raise SystemExit("--link needs --topk")
+    vg = VideoGrounder(m, n_frame=a.n_frame, border=a.border, chunk=a.chunk, topk=a.topk, link=TubeLink() if a.link else None)
     times = []
     for _ in range(a.repeat + 1):
         torch.cuda.synchronize()
@@ -606,10 +670,13 @@ def _main_run(a):
     print(f"{a.frames} frames {a.size}x{a.size}, n_frame {a.n_frame}, border {a.border}, {a.queries} quer{'y' if a.queries == 1 else 'ies'}, "
           f"{a.precision}: {res.centres.numel()} centres in {t * 1e3:.1f} ms = {a.frames / t:.1f} frames/s, peak memory "
           f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB, bank {vg.bank_bytes_per_frame(a.size) / 2 ** 20:.2f} MiB per frame")
-    if a.raw_frames:
-        b = (res.fused_boxes if a.topk is not None else res.boxes)[0].cpu()
+    if a.raw_frames or a.link:
+        b = (res.tube_boxes if a.link else res.fused_boxes if a.topk is not None else res.boxes)[0].cpu()
+        what = ("tube box" if a.link else "box") + (" (source pixels) " if a.raw_frames else " (letterbox pixels) ")
         for i, c in enumerate(res.centres.cpu().tolist()):
-            print(f"frame {c}: box (source pixels) " + " ".join(f"{v:.1f}" for v in b[i].tolist()))
+            print(f"frame {c}: {what}" + " ".join(f"{v:.1f}" for v in b[i].tolist()))
+        if a.link:
+            print(f"tube score {float(res.tube_score[0]):.4f}, candidates kept by the NMS: {float(res.cand_keep[0].float().sum(-1).mean()):.1f} of {a.topk} per centre")
 
 
 if __name__ == "__main__":

@@ -647,6 +647,32 @@ int dcn_bank_concat_b16(const void* rows16, int64_t bs16, const float* attn, int
  * 0 = it goes through dcn_coattn_fwd on the fp32 rows — under the current precision mode and knobs. */
 int dcn_coattn_bank_form(int hw, int c);
 
+/* ---- tube linking: one track per query through the candidates of consecutive centres (additive, ABI 318) --------------- */
+/* Shared definitions.  Boxes are xyxy.  iou(a, b) = inter / (area_a + area_b - inter + 1e-16f) with
+ * inter = max(min(ax2,bx2) - max(ax1,bx1), 0) * max(min(ay2,by2) - max(ay1,by1), 0) and areas of widths and heights clamped at 0
+ * (dcn_box_iou's formula with the clamp: a degenerate box has IoU 0 with everything).  All arithmetic is fp32 whatever the
+ * precision mode; results are bitwise repeatable; k <= 64; nothing synchronises the host.
+ *
+ * Greedy non-maximum suppression in index order for n centres: boxes [n][k][4], keep [n][k] bytes (1 / 0).  Candidate i is kept iff
+ * no kept j < i has iou(j, i) > iou_thr (strict); candidate 0 is always kept.  dcn_post_topk's order is score order.  A mask:
+ * nothing is compacted. */
+int dcn_post_nms(const float* boxes, int n, int k, float iou_thr, unsigned char* keep, void* stream);
+/* Transition scores of frames t0 <= t < t1 of q queries: boxes [q][n][k][4], feats [q][n][k][e] or NULL (only with w_feat == 0),
+ * W [q][t1-t0][k][k],  W[q][t-t0][i][j] = w_iou * iou(boxes[q][t-1][i], boxes[q][t][j]) + w_feat * <feats[q][t-1][i], feats[q][t][j]>
+ * (the dot product summed with e ascending).  The row of global frame 0 is not written.  w_iou, w_feat >= 0; q <= 65535. */
+int dcn_tube_transitions(const float* boxes, const float* feats, int q, int n, int k, int e, int t0, int t1, float w_iou, float w_feat,
+                         float* W, void* stream);
+/* Viterbi forward pass over frames t0 <= t < t1 with W as dcn_tube_transitions wrote it for the same range: unary [q][n][k],
+ * keep [q][n][k] bytes or NULL (all kept), delta_in [q][k] = the delta of frame t0 - 1 (NULL iff t0 == 0).
+ *   delta_0[j] = keep ? unary[0][j] : -inf;   delta_t[j] = keep ? unary[t][j] + max_i (delta_{t-1}[i] + W[t][i][j]) : -inf
+ * backptr [q][n][k] bytes: rows t0 ... t1-1 are written, the lowest i attaining the maximum; row 0 is written as 0.  delta_out
+ * [q][k] = delta_{t1-1} (may be delta_in).  A frame without any kept candidate is a caller error and is not detected. */
+int dcn_tube_forward(const float* W, const float* unary, const unsigned char* keep, const float* delta_in, int q, int n, int k, int t0,
+                     int t1, float* delta_out, unsigned char* backptr, void* stream);
+/* The best path: delta [q][k] = delta_{n-1}, score [q] = its maximum, path [q][n]: path[n-1] = its first arg-max,
+ * path[t-1] = backptr[t][path[t]]. */
+int dcn_tube_backtrack(const unsigned char* backptr, const float* delta, int q, int n, int k, int64_t* path, float* score, void* stream);
+
 /* ---- clip preprocessing: letterbox, flip, HSV and affine warp of decoded frames (ABI 309) ---------------------------- */
 /* One record per frame of the batch (host-built by dcnet_amd/prep.py; dataset/vid_loader.py:333-395 draws the parameters,
  * utils/transforms.py:123-137 letterbox, :139-185 random_affine, :236-275 wrap_points is box geometry and stays on the host).
