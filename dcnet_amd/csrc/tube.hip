@@ -5,9 +5,12 @@
 //   tube_transitions  W[t][i][j] = w_iou * iou(box[t-1,i], box[t,j]) + w_feat * <feat[t-1,i], feat[t,j]>
 //   tube_forward      delta_t[j] = unary[t,j] + max_i (delta_{t-1}[i] + W[t][i][j]) over kept candidates, lowest arg-max as back-pointer
 //   tube_backtrack    first arg-max of the last delta, then the back-pointers down to frame 0
+//   tube_stream_step  tube_forward on the centres of one push, frame t - lag committed after step t
+//   tube_stream_flush the last min(lag, n) frames of a stream and its score
 //
 // All arithmetic is fp32 on the vector ALU in every precision mode (like post_fusion_kernel; nothing goes through igemm_launch), every
 // sum has one fixed order (bitwise repeatable), nothing synchronises the host and there are no atomics.
+#include <limits.h>
 #include <math.h>
 #include "common.h"
 
@@ -17,6 +20,7 @@ constexpr int TB_MAXK = 64;       // candidates per centre = lanes of a wave
 constexpr int TB_EC = 64;         // feature columns per LDS chunk of tube_transitions
 constexpr int TB_LD = TB_EC + 1;  // its row pitch (floats): rows 16 apart land on banks 16 apart, column reads are conflict-free
 constexpr int TB_ROWS = 256;      // back-pointer rows per LDS tile of tube_backtrack
+constexpr int TB_MAXLAG = 64;     // frames a streamed track may trail the newest one: 16 registers of survivor bytes per lane
 
 // dcn_box_iou's formula with widths and heights clamped at 0: a degenerate or inverted box has IoU 0 with everything
 __device__ __forceinline__ float tb_iou(float ax1, float ay1, float ax2, float ay2, float bx1, float by1, float bx2, float by2) {
@@ -113,10 +117,35 @@ __global__ __launch_bounds__(256) void tube_transitions_kernel(const float* __re
   }
 }
 
-// One workgroup of 4 waves per query, lane = j.  Every wave holds delta_{t-1} in its registers (lane i = candidate i; the four
-// copies are bitwise equal) and takes the predecessors i of its quarter [wave * kq, (wave + 1) * kq), i ascending with a strict >;
-// the four partial (max, arg) meet in LDS and every wave combines them in wave order with a strict >: the lowest arg-max.  The
-// W rows, unary and keep of step t + 1 are loaded before step t is reduced, so a step waits for no memory.
+// One step of the recursion, shared by tube_forward_kernel and tube_stream_step_kernel.  Every wave holds delta_{t-1} in its registers
+// (lane i = candidate i; the four copies are bitwise equal) and takes the predecessors i of its quarter [i0, i0 + ni), i ascending with
+// a strict >; the four partial (max, arg) meet in LDS (pv, pa: this step's half) and every wave combines them in wave order with a
+// strict >: the lowest arg-max.  One barrier; the caller alternates the halves of pv / pa from step to step.
+__device__ __forceinline__ float tb_step(float delta, const float (&w_cur)[16], float u_cur, bool k_cur, int i0, int ni, int wave, int j,
+                                         float (*pv)[TB_MAXK], int (*pa)[TB_MAXK], int& arg_out) {
+  float best = -INFINITY;
+  int arg = i0;
+#pragma unroll
+  for (int ii = 0; ii < 16; ++ii) {
+    if (ii < ni) {
+      const float v = tb_readlane(delta, i0 + ii) + w_cur[ii];
+      if (v > best) { best = v; arg = i0 + ii; }
+    }
+  }
+  pv[wave][j] = best; pa[wave][j] = arg;
+  __syncthreads();
+  best = pv[0][j]; arg = pa[0][j];
+#pragma unroll
+  for (int w = 1; w < 4; ++w) {
+    const float v = pv[w][j];
+    if (v > best) { best = v; arg = pa[w][j]; }
+  }
+  arg_out = arg;
+  return k_cur ? u_cur + best : -INFINITY;
+}
+
+// One workgroup of 4 waves per query, lane = j (tb_step).  The W rows, unary and keep of step t + 1 are loaded before step t is
+// reduced, so a step waits for no memory.
 __global__ __launch_bounds__(256) void tube_forward_kernel(const float* __restrict__ W, const float* __restrict__ unary,
                                                            const unsigned char* __restrict__ keep, const float* __restrict__ delta_in,
                                                            int n, int k, int t0, int t1, float* __restrict__ delta_out,
@@ -162,25 +191,9 @@ __global__ __launch_bounds__(256) void tube_forward_kernel(const float* __restri
     const float u_cur = u_nxt;
     const bool k_cur = k_nxt;
     if (t + 1 < t1) fetch(t + 1);
-    float best = -INFINITY;
-    int arg = i0;
-#pragma unroll
-    for (int ii = 0; ii < 16; ++ii) {
-      if (ii < ni) {
-        const float v = tb_readlane(delta, i0 + ii) + w_cur[ii];
-        if (v > best) { best = v; arg = i0 + ii; }
-      }
-    }
-    const int p = t & 1;
-    pv[p][wave][j] = best; pa[p][wave][j] = arg;
-    __syncthreads();                 // (one barrier per step: the partials of step t + 1 go to the other half of pv / pa)
-    best = pv[p][0][j]; arg = pa[p][0][j];
-#pragma unroll
-    for (int w = 1; w < 4; ++w) {
-      const float v = pv[p][w][j];
-      if (v > best) { best = v; arg = pa[p][w][j]; }
-    }
-    delta = k_cur ? u_cur + best : -INFINITY;
+    const int p = t & 1;             // (one barrier per step: the partials of step t + 1 go to the other half of pv / pa)
+    int arg;
+    delta = tb_step(delta, w_cur, u_cur, k_cur, i0, ni, wave, j, pv[p], pa[p], arg);
     if (wave == 0 && live) bq[(size_t)t * k + j] = (unsigned char)arg;
   }
   if (wave == 0 && live) delta_out[(size_t)q * k + j] = delta;
@@ -215,6 +228,128 @@ __global__ __launch_bounds__(256) void tube_backtrack_kernel(const unsigned char
     __syncthreads();
     for (int r = tid; r < rows; r += 256) path[(size_t)q * n + lo + r] = pth[r];
   }
+}
+
+// Streaming forward pass with commitment: tube_forward_kernel's recursion (tb_step) over the m centres
+// t0 ... t0 + m - 1 of one push, plus the survivor memory that lets frame t - lag leave after step t.  Register exchange, as in a
+// hardware Viterbi decoder: lane j keeps the last lag choices of its survivor as bytes (byte b of hist = the candidate of frame
+// t - lag + b on the best path into candidate j of frame t) in NW = ceil(lag / 4) registers; the bytes from lag on stay 0.  A step
+// fetches the words of lane arg with ds_bpermute (all NW in flight at once: NW is a template parameter, nothing branches), shifts
+// them down a byte and puts arg in at byte lag - 1; byte 0 is the ancestor a[j] at frame t - lag.  If the live lanes (delta > -inf)
+// agree on it (two ballots) it is committed; else the ancestor of the first arg-max of delta_t is, the lanes that disagree are set to
+// -inf and the query's forced count grows by one.  All four waves keep the (bitwise equal) state, so the commitment needs no barrier
+// of its own; wave 0 writes.  surv [q][lag][k] bytes carries hist from launch to launch, delta [q][k] the scores.
+template <int NW>
+__global__ __launch_bounds__(256) void tube_stream_step_kernel(const float* __restrict__ W, const float* __restrict__ unary,
+                                                               const unsigned char* __restrict__ keep, int m, int k, int t0, int lag,
+                                                               float* __restrict__ delta_io, unsigned char* __restrict__ surv,
+                                                               int64_t* __restrict__ commit, int* __restrict__ forced) {
+  __shared__ float pv[2][4][TB_MAXK];
+  __shared__ int pa[2][4][TB_MAXK];
+  const int q = blockIdx.x, j = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int kq = (k + 3) >> 2, i0 = wave * kq, ni = max(0, min(kq, k - i0));
+  const int sh = ((lag - 1) & 3) * 8;                                  // bit of byte lag - 1 in hist[NW - 1] (NW == ceil(lag / 4))
+  const unsigned top_mask = 0xffffffffu >> (24 - sh);                   // the bytes of hist[NW - 1] below lag
+  const bool live = j < k, writer = wave == 0 && j == 0;
+  const float* Wq = W + (size_t)q * m * k * k;
+  const float* uq = unary + (size_t)q * m * k;
+  const unsigned char* kp = keep ? keep + (size_t)q * m * k : nullptr;
+  unsigned char* sq = surv + (size_t)q * lag * k;
+  int64_t* cq = commit + (size_t)q * m;
+  const int jc = min(j, k - 1);
+  unsigned hist[NW];
+#pragma unroll
+  for (int w = 0; w < NW; ++w) hist[w] = 0u;
+  float delta = -INFINITY;
+  int r = 0, nforced = 0;            // r: index within the push, t = t0 + r
+  if (t0 == 0) {
+    if (live) delta = (!kp || kp[j]) ? uq[j] : -INFINITY;
+    if (writer) cq[0] = -1;
+    r = 1;
+  } else {
+    if (live) delta = delta_io[(size_t)q * k + j];
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {   // unpredicated (one wait for all of them): a byte past lag - 1 re-reads the last one and is masked off
+#pragma unroll
+      for (int b = 0; b < 4; ++b) hist[w] |= (unsigned)sq[(size_t)min(4 * w + b, lag - 1) * k + jc] << (8 * b);
+    }
+    hist[NW - 1] &= top_mask;
+  }
+  float w_nxt[16], u_nxt = 0.f;
+  bool k_nxt = true;
+  unsigned off[16];
+#pragma unroll
+  for (int ii = 0; ii < 16; ++ii) off[ii] = (unsigned)(min(i0 + ii, k - 1) * k + jc);
+  auto fetch = [&](int rr) {
+    const float* wr = Wq + (size_t)rr * k * k;
+#pragma unroll
+    for (int ii = 0; ii < 16; ++ii) w_nxt[ii] = wr[off[ii]];
+    u_nxt = uq[(size_t)rr * k + jc];
+    k_nxt = live && (!kp || kp[(size_t)rr * k + jc]);
+  };
+  if (r < m) fetch(r);
+  for (; r < m; ++r) {
+    float w_cur[16];
+#pragma unroll
+    for (int ii = 0; ii < 16; ++ii) w_cur[ii] = w_nxt[ii];
+    const float u_cur = u_nxt;
+    const bool k_cur = k_nxt;
+    if (r + 1 < m) fetch(r + 1);
+    const int p = r & 1;
+    int arg;
+    delta = tb_step(delta, w_cur, u_cur, k_cur, i0, ni, wave, j, pv[p], pa[p], arg);
+    unsigned pw[NW];                 // the survivor of j = that of arg without its oldest frame, and arg
+#pragma unroll
+    for (int w = 0; w < NW; ++w) pw[w] = (unsigned)__builtin_amdgcn_ds_bpermute(arg << 2, (int)hist[w]);
+#pragma unroll
+    for (int w = 0; w < NW - 1; ++w) hist[w] = (pw[w] >> 8) | (pw[w + 1] << 24);
+    hist[NW - 1] = (pw[NW - 1] >> 8) | ((unsigned)arg << sh);
+    long long c_out = -1;
+    if (t0 + r >= lag) {
+      const int a = (int)(hist[0] & 0xffu);
+      const bool alive = delta > -INFINITY;
+      const unsigned long long lm = __ballot(alive);
+      int c = __builtin_amdgcn_readlane(a, lm ? __ffsll((long long)lm) - 1 : 0);
+      if (__ballot(alive && a != c)) {                                   // (wave-uniform: some live survivor has another ancestor)
+        float mx = delta;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+        const unsigned long long am = __ballot(delta == mx);           // (lm != 0: mx is finite, lanes >= k hold -inf)
+        c = __builtin_amdgcn_readlane(a, __ffsll((long long)am) - 1);  // the ancestor of the first arg-max
+        if (a != c) delta = -INFINITY;
+        ++nforced;
+      }
+      c_out = c;
+    }
+    if (writer) cq[r] = c_out;
+  }
+  if (wave == 0 && live) {
+    delta_io[(size_t)q * k + j] = delta;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+#pragma unroll
+      for (int b = 0; b < 4; ++b)
+        if (w < NW - 1 || 4 * w + b < lag) sq[(size_t)(4 * w + b) * k + j] = (unsigned char)(hist[w] >> (8 * b));
+    }
+  }
+  if (writer && nforced) forced[q] += nforced;                           // (the only writer of forced[q]: no atomic)
+}
+
+// End of a stream: the first arg-max of the last delta and its survivor, the frames that tube_stream_step_kernel has not committed.
+// One wave per query.
+__global__ __launch_bounds__(64) void tube_stream_flush_kernel(const float* __restrict__ delta, const unsigned char* __restrict__ surv,
+                                                               int k, int n, int lag, int64_t* __restrict__ tail,
+                                                               float* __restrict__ score) {
+  const int q = blockIdx.x, j = threadIdx.x;
+  const float d = j < k ? delta[(size_t)q * k + j] : -INFINITY;
+  float mx = d;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+  const int js = min(__ffsll((long long)__ballot(d == mx)) - 1, k - 1);  // first arg-max (lane 0 if every delta is -inf)
+  const int m = min(lag, n);
+  int64_t* tq = tail + (size_t)q * m;
+  if (j == 0) { score[q] = mx; tq[m - 1] = js; }
+  if (j < m - 1) tq[j] = surv[((size_t)q * lag + lag - m + 1 + j) * k + js];      // byte b of the survivor: frame n - 1 - lag + b
 }
 
 }  // namespace
@@ -255,5 +390,36 @@ extern "C" int dcn_tube_backtrack(const unsigned char* backptr, const float* del
                 "tube_backtrack: bad argument (q=%d n=%d k=%d)", q, n, k);
   hipLaunchKernelGGL(tube_backtrack_kernel, dim3(q), dim3(256), 0, (hipStream_t)stream, backptr, delta, n, k, path, score);
   DCN_CHECK_LAUNCH("tube_backtrack");
+  return DCN_OK;
+}
+
+extern "C" int dcn_tube_stream_step(const float* W, const float* unary, const unsigned char* keep, int q, int m, int k, int t0, int lag,
+                                    float* delta, unsigned char* surv, int64_t* commit, int* forced, void* stream) {
+  DCN_CHECK_ARG(W && unary && delta && surv && commit && forced && q >= 1 && m >= 1 && k >= 1 && k <= TB_MAXK && t0 >= 0 &&
+                    t0 <= INT_MAX - m,
+                "tube_stream_step: bad argument (q=%d m=%d k=%d t0=%d)", q, m, k, t0);
+  DCN_CHECK_ARG(lag >= 1 && lag <= TB_MAXLAG, "tube_stream_step: lag = %d outside 1 ... %d", lag, TB_MAXLAG);
+#define TB_STREAM_CASE(NW)                                                                                                          \
+  case NW:                                                                                                                          \
+    hipLaunchKernelGGL(tube_stream_step_kernel<NW>, dim3(q), dim3(256), 0, (hipStream_t)stream, W, unary, keep, m, k, t0, lag, delta, \
+                       surv, commit, forced);                                                                                       \
+    break;
+  switch ((lag + 3) >> 2) {          // registers of survivor bytes per lane
+    TB_STREAM_CASE(1) TB_STREAM_CASE(2) TB_STREAM_CASE(3) TB_STREAM_CASE(4) TB_STREAM_CASE(5) TB_STREAM_CASE(6) TB_STREAM_CASE(7)
+    TB_STREAM_CASE(8) TB_STREAM_CASE(9) TB_STREAM_CASE(10) TB_STREAM_CASE(11) TB_STREAM_CASE(12) TB_STREAM_CASE(13)
+    TB_STREAM_CASE(14) TB_STREAM_CASE(15) TB_STREAM_CASE(16)
+  }
+#undef TB_STREAM_CASE
+  DCN_CHECK_LAUNCH("tube_stream_step");
+  return DCN_OK;
+}
+
+extern "C" int dcn_tube_stream_flush(const float* delta, const unsigned char* surv, int q, int k, int n, int lag, int64_t* tail,
+                                     float* score, void* stream) {
+  DCN_CHECK_ARG(delta && surv && tail && score && q >= 1 && n >= 1 && k >= 1 && k <= TB_MAXK,
+                "tube_stream_flush: bad argument (q=%d n=%d k=%d)", q, n, k);
+  DCN_CHECK_ARG(lag >= 1 && lag <= TB_MAXLAG, "tube_stream_flush: lag = %d outside 1 ... %d", lag, TB_MAXLAG);
+  hipLaunchKernelGGL(tube_stream_flush_kernel, dim3(q), dim3(64), 0, (hipStream_t)stream, delta, surv, k, n, lag, tail, score);
+  DCN_CHECK_LAUNCH("tube_stream_flush");
   return DCN_OK;
 }

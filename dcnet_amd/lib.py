@@ -201,6 +201,8 @@ SIGNATURES = {
     "dcn_tube_transitions": (I, [P, P, I, I, I, I, I, I, F, F, P, P]),
     "dcn_tube_forward": (I, [P, P, P, P, I, I, I, I, I, P, P, P]),
     "dcn_tube_backtrack": (I, [P, P, I, I, I, P, P, P]),
+    "dcn_tube_stream_step": (I, [P, P, P, I, I, I, I, I, P, P, P, P, P]),
+    "dcn_tube_stream_flush": (I, [P, P, I, I, I, I, P, P, P]),
 }
 _VALUE_FUNCS = {"dcn_version", "dcn_conv2d_stats_rows", "dcn_conv2d_bwd_data_tap_rows", "dcn_conv2d_pre_supported",
                 "dcn_conv2d_bwd_weight_pre_supported", "dcn_gemm3_supported", "dcn_channel_stats_rows", "dcn_filter_job_bytes", "dcn_prof_records",

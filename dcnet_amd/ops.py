@@ -1903,6 +1903,66 @@ def tube_backtrack(backptr, delta):
     return path, score
 
 
+TUBE_MAXLAG = 64                     # frames a streamed track may trail the newest one (csrc/tube.hip TB_MAXLAG)
+
+
+def _chk_stream_state(name, lag, delta, surv, Q, k):
+    if not isinstance(lag, int) or isinstance(lag, bool) or not 1 <= lag <= TUBE_MAXLAG:
+        raise ValueError(f"{name}: lag = {lag!r}: an int in 1 ... {TUBE_MAXLAG}")
+    if not 1 <= k <= TUBE_MAXK:
+        raise ValueError(f"{name}: 1 <= k <= {TUBE_MAXK}, got k = {k}")
+    _chk(delta, f"{name} delta")
+    if tuple(delta.shape) != (Q, k):
+        raise ValueError(f"{name}: delta must be {(Q, k)}, got {tuple(delta.shape)}")
+    if not (surv.is_cuda and surv.dtype == torch.uint8 and surv.is_contiguous() and tuple(surv.shape) == (Q, lag, k)):
+        raise ValueError(f"{name}: surv must be a contiguous uint8 CUDA tensor {(Q, lag, k)}, got {surv.dtype} {surv.device} "
+                         f"{tuple(surv.shape)}")
+
+
+def tube_stream_step(W, unary, keep, t0, lag, delta, surv, forced, commit=None):
+    """csrc/tube.hip, streaming tube linking: the Viterbi step of tube_forward over the m centres t0 ... t0+m-1
+    of one push, and the commitment of the frames that are ``lag`` behind.  W (Q,m,k,k) fp32: row i = the transitions into frame t0+i
+    (tube_transitions; row 0 unread for t0 == 0), unary (Q,m,k) fp32, keep (Q,m,k) uint8 / bool or None.  State, in/out: delta (Q,k)
+    fp32 and surv (Q,lag,k) uint8 (both unread for t0 == 0), forced (Q,) int32 (accumulates; zero it before the first call).
+    Returns commit (Q,m) int64: entry i = the candidate committed for frame t0+i-lag, -1 where t0+i < lag."""
+    _chk(W, "tube_stream_step W"); _chk(unary, "tube_stream_step unary")
+    if unary.dim() != 3 or min(unary.shape) < 1:
+        raise ValueError(f"tube_stream_step: unary must be (Q,m,k) with Q, m, k >= 1, got {tuple(unary.shape)}")
+    Q, m, k = unary.shape
+    _chk_stream_state("tube_stream_step", lag, delta, surv, Q, k)
+    if tuple(W.shape) != (Q, m, k, k):
+        raise ValueError(f"tube_stream_step: W must be {(Q, m, k, k)}, got {tuple(W.shape)}")
+    if keep is not None:
+        _chk_keep(keep, (Q, m, k), "tube_stream_step")
+    if not isinstance(t0, int) or t0 < 0:
+        raise ValueError(f"tube_stream_step: t0 = {t0!r}: the index of the first centre of the push, an int >= 0")
+    if not (forced.is_cuda and forced.dtype == torch.int32 and forced.is_contiguous() and tuple(forced.shape) == (Q,)):
+        raise ValueError(f"tube_stream_step: forced must be a contiguous int32 CUDA tensor {(Q,)}, got {forced.dtype} {forced.device} "
+                         f"{tuple(forced.shape)}")
+    if commit is None:
+        commit = torch.empty((Q, m), dtype=torch.int64, device=unary.device)
+    elif not (commit.is_cuda and commit.dtype == torch.int64 and commit.is_contiguous() and tuple(commit.shape) == (Q, m)):
+        raise ValueError(f"tube_stream_step: commit must be a contiguous int64 CUDA tensor {(Q, m)}")
+    lib().tube_stream_step(W.data_ptr(), unary.data_ptr(), _p(keep), Q, m, k, t0, lag, delta.data_ptr(), surv.data_ptr(),
+                           commit.data_ptr(), forced.data_ptr(), _s())
+    return commit
+
+
+def tube_stream_flush(delta, surv, n, lag):
+    """csrc/tube.hip: the end of a stream of n frames, delta (Q,k) and surv (Q,lag,k) as the last tube_stream_step left them ->
+    (tail (Q, min(lag,n)) int64: the frames n - min(lag,n) ... n-1 of the walk back from the first arg-max of delta, score (Q,))."""
+    if delta.dim() != 2:
+        raise ValueError(f"tube_stream_flush: delta must be (Q,k), got {tuple(delta.shape)}")
+    Q, k = delta.shape
+    _chk_stream_state("tube_stream_flush", lag, delta, surv, Q, k)
+    if not isinstance(n, int) or n < 1:
+        raise ValueError(f"tube_stream_flush: n = {n!r}: the frames of the stream, an int >= 1")
+    tail = torch.empty((Q, min(lag, n)), dtype=torch.int64, device=delta.device)
+    score = torch.empty(Q, dtype=torch.float32, device=delta.device)
+    lib().tube_stream_flush(delta.data_ptr(), surv.data_ptr(), Q, k, n, lag, tail.data_ptr(), score.data_ptr(), _s())
+    return tail, score
+
+
 def box_iou(b1, b2):
     _chk(b1, "box_iou"); _chk(b2, "box_iou")
     iou = torch.empty(b1.shape[0], dtype=torch.float32, device=b1.device)

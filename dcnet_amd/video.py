@@ -12,7 +12,10 @@ frames is computed once in each of their windows.  Here:
     number of queries share the visual work;
   * the temporal re-scoring reads the candidates of the centres in place (``dcn_post_fusion_bank``);
   * optionally (``link=TubeLink()``) the candidates of ALL centres are joined into one track per query: an NMS mask per centre and a
-    Viterbi path over IoU + correspondence-feature transitions (``csrc/tube.hip``).
+    Viterbi path over IoU + correspondence-feature transitions (``csrc/tube.hip``, DESIGN.md section 13);
+  * for streams, ``FuseStream`` / ``TubeStream`` (``vg.tube_stream(lag)``) do the last two while the frames arrive: they take the parts
+    of ``push`` one by one, keep a constant amount of state and hand a centre's fused choice and tube entry out a fixed number of
+    centres later.
 
 The window rule is the reference's (``getChunk``):
 
@@ -595,6 +598,253 @@ class VideoGrounder:
             res = self.fuse(res)
         return self.link(res) if self._link is not None else res
 
+    def tube_stream(self, lag: int = 16) -> "TubeStream":
+        """A ``TubeStream`` with this grounder's ``link``, ``n_frame`` and ``topk``: feed it the parts that ``push`` / ``flush`` return
+        and drop them; fused choices and tube boxes come back while the frames arrive."""
+        if self._link is None:
+            raise ValueError("tube_stream: the grounder was built without link")
+        return TubeStream(self._link, self.n_frame, lag)
+
+
+# ---- streaming fusion and tube linking (DESIGN.md section 14) -------------------------------------------------------------------
+@dataclass
+class FuseChunk:
+    """The temporally fused choice of m centres that became final: ``centres`` (m,), ``best`` (Q,m) int64, ``fused`` (Q,m,k),
+    ``fused_boxes`` (Q,m,4) — the values of ``VideoGrounder.fuse`` on the whole run, bit for bit."""
+    centres: torch.Tensor
+    best: torch.Tensor
+    fused: torch.Tensor
+    fused_boxes: torch.Tensor
+
+
+@dataclass
+class TubeChunk:
+    """The part of the track that a call released: ``centres`` (m,), ``tube`` (Q,m) int64 (candidate index per centre), ``tube_boxes``
+    (Q,m,4); m may be 0.  ``fused``: the ``FuseChunk`` of the same call (other centres: fusion and linking trail the arrivals by
+    different amounts), or None.  ``tube_score`` (Q,): set by ``flush`` only."""
+    centres: torch.Tensor
+    tube: torch.Tensor
+    tube_boxes: torch.Tensor
+    fused: Optional[FuseChunk] = None
+    tube_score: Optional[torch.Tensor] = None
+
+
+def fuse_delay(n_frame: int) -> int:
+    """Centres that the fusion trails the arrivals by: centre b is final once centre b + n_frame - 1 - n_frame // 2 has arrived."""
+    K = _check_window(n_frame)
+    return K - 1 - K // 2
+
+
+def stream_counts(arrived: int, n_frame: int, lag: int, fused_unary: bool, flushed: bool = False) -> Tuple[int, int, int]:
+    """(fused, linked, released) after ``arrived`` centres: how many centres have their final fused scores, how many the Viterbi
+    recursion has taken, how many tube entries are out.  Counts alone decide what a call hands out: nothing asks the device."""
+    d = 0 if flushed else fuse_delay(n_frame)
+    n_fused = max(0, arrived - d)
+    linked = n_fused if fused_unary else arrived
+    return n_fused, linked, linked if flushed else max(0, linked - lag)
+
+
+def _check_lag(lag) -> int:
+    if not isinstance(lag, int) or isinstance(lag, bool) or not 1 <= lag <= 64:
+        raise ValueError(f"lag = {lag!r}: frames a streamed track trails the newest one, an int in 1 ... 64")
+    return lag
+
+
+def _check_stream_part(part, qk: Optional[Tuple[int, int]], where: str, need_keep: bool) -> Tuple[int, int, int]:
+    """(Q, m, k) of a part of a stream; ValueError if it has no candidates, differs from the (Q, k) of the first part, or is not on
+    the GPU."""
+    if part.cand_feats is None or part.cand_scores is None or part.cand_boxes is None:
+        raise ValueError(f"{where}: the part carries no candidates (the grounder was built without topk)")
+    if need_keep and part.cand_keep is None:
+        raise ValueError(f"{where}: the part carries no candidates of a grounder with link (cand_keep is None)")
+    Q, m, k = part.cand_scores.shape
+    if qk is not None and (Q, k) != tuple(qk):
+        raise ValueError(f"{where}: the part has Q = {Q} queries of k = {k} candidates, the stream began with Q = {qk[0]}, k = {qk[1]}")
+    if tuple(part.cand_boxes.shape) != (Q, m, k, 4) or tuple(part.cand_feats.shape[:3]) != (Q, m, k) or part.centres.numel() != m:
+        raise ValueError(f"{where}: cand_boxes / cand_feats / centres do not match cand_scores {(Q, m, k)}")
+    if not all(t.is_cuda for t in (part.cand_feats, part.cand_scores, part.cand_boxes, part.centres)):
+        raise ValueError(f"{where}: expected CUDA tensors (HIP kernels only, no CPU path)")
+    return Q, m, k
+
+
+def _own(t: torch.Tensor) -> torch.Tensor:
+    """A slice kept between calls owns its memory (a view would hold the whole staging tensor)."""
+    return t.clone(memory_format=torch.contiguous_format)
+
+
+def _nbytes(ts) -> int:
+    return sum(t.numel() * t.element_size() for t in ts if t is not None)
+
+
+class FuseStream:
+    """``VideoGrounder.fuse`` while the centres arrive.  ``push(part)`` takes the next part of a stream (any number of centres, or
+    None) and returns the centres that became final; ``flush()`` returns the last ``fuse_delay(n_frame)`` ones.  Between calls it
+    keeps the candidates of the last n_frame - 1 centres.  Each call runs ``ops.post_fusion_bank`` on [kept | new] and takes the
+    centres whose whole window lies inside (the start of the video and, at ``flush``, its end are the true borders): the same kernel
+    on the same window contents as a run over the whole video."""
+
+    def __init__(self, n_frame: int):
+        self.n_frame = _check_window(n_frame)
+        if n_frame > 32:
+            raise ValueError(f"n_frame = {n_frame}: the temporal fusion takes n_frame <= 32")
+        self._kept = None                  # (centres (s,), feats (Q,s,k,E), scores (Q,s,k), boxes (Q,s,k,4)) of the last s <= K - 1 centres
+        self._qk = None
+        self._n = self._done = 0           # centres arrived / handed out
+
+    def state_bytes(self) -> int:
+        return _nbytes(self._kept or ())
+
+    def _emit(self, stage, hi: int) -> Optional[FuseChunk]:
+        from . import ops
+        cen, feats, scores, boxes = stage
+        s0, lo = self._n - cen.numel(), self._done
+        if hi <= lo:
+            return None
+        best, fused = zip(*[ops.post_fusion_bank(feats[q], scores[q], self.n_frame) for q in range(feats.shape[0])])
+        best, fused = torch.stack(best)[:, lo - s0:hi - s0], torch.stack(fused)[:, lo - s0:hi - s0]
+        fb = torch.gather(boxes[:, lo - s0:hi - s0], 2, best[:, :, None, None].expand(-1, -1, 1, 4))[:, :, 0]
+        self._done = hi
+        return FuseChunk(centres=cen[lo - s0:hi - s0], best=best, fused=fused, fused_boxes=fb)
+
+    @torch.no_grad()
+    def push(self, part: Optional[VideoResult]) -> Optional[FuseChunk]:
+        if part is None:
+            return None
+        Q, m, k = _check_stream_part(part, self._qk, "FuseStream.push", False)
+        self._qk = (Q, k)
+        new = (part.centres, part.cand_feats.float(), part.cand_scores.float(), part.cand_boxes.float())
+        dims = (0, 1, 1, 1)
+        stage = tuple(t.contiguous() for t in new) if self._kept is None else \
+            tuple(torch.cat([a, b], dim=d) for a, b, d in zip(self._kept, new, dims))
+        self._n += m
+        out = self._emit(stage, self._n - fuse_delay(self.n_frame))
+        s = min(self.n_frame - 1, stage[0].numel())
+        self._kept = tuple(_own(t.narrow(d, t.shape[d] - s, s)) for t, d in zip(stage, dims))
+        return out
+
+    @torch.no_grad()
+    def flush(self) -> Optional[FuseChunk]:
+        out = None if self._kept is None else self._emit(self._kept, self._n)
+        self._kept, self._qk, self._n, self._done = None, None, 0, 0
+        return out
+
+
+class TubeStream:
+    """``VideoGrounder.fuse`` and ``VideoGrounder.link`` while the centres arrive, with constant state.
+
+        ts = vg.tube_stream(lag=16)                    # or TubeStream(TubeLink(), n_frame, lag)
+        for frames in video: chunk = ts.push(vg.push(frames)); ...        # the part can be dropped at once
+        ts.push(vg.flush()); last = ts.flush()
+
+    ``push`` hands a centre's tube entry out once the Viterbi recursion is ``lag`` centres past it (for ``unary == "fused"`` the
+    recursion itself trails the arrivals by ``fuse_delay(n_frame)``); ``flush`` hands out the rest and ``tube_score``.  How many
+    centres a call releases follows from counts alone (``stream_counts``): nothing here synchronises the host with the device.
+    ``forced`` (Q,) int32, a device tensor: how often a frame had to be committed although the live survivors disagreed on it.  While
+    it is 0 the track is bit for bit that of ``link`` on the whole video."""
+
+    def __init__(self, link: TubeLink, n_frame: int, lag: int = 16):
+        if not isinstance(link, TubeLink):
+            raise TypeError(f"link: expected a dcnet_amd.video.TubeLink, got {type(link).__name__}")
+        self.link, self.n_frame, self.lag = link, _check_window(n_frame), _check_lag(lag)
+        self._fs = FuseStream(n_frame)
+        self._reset()
+
+    def _reset(self):
+        self._qk = None
+        self._t = 0                        # centres the recursion has taken
+        self._pend = None                  # (centres, boxes, feats, keep, scores) of the centres that wait for their fused scores
+        self._last = None                  # (boxes (Q,1,k,4), feats (Q,1,k,E)) of centre _t - 1
+        self._ring = None                  # (centres, boxes) of the centres [max(0, _t - lag), _t): not released yet
+        self._delta = self._surv = None
+        self.forced = None
+
+    def state_bytes(self) -> int:
+        """Bytes of the device tensors held between calls."""
+        held = [self._delta, self._surv, self.forced]
+        for group in (self._pend, self._last, self._ring):
+            held.extend(group or ())
+        return _nbytes(held) + self._fs.state_bytes()
+
+    def _advance(self, r: int, unary: torch.Tensor):
+        """The recursion over the first r waiting centres; returns (centres, tube, tube_boxes) of the frames it committed."""
+        from . import ops
+        cfg, lag, T = self.link, self.lag, self._t
+        cen, boxes, feats, keep, _ = (t[:r] if i == 0 else t[:, :r] for i, t in enumerate(self._pend))
+        use_feats = cfg.feat_weight > 0
+        if T:
+            sb = torch.cat([self._last[0], boxes], dim=1)
+            sf = torch.cat([self._last[1], feats], dim=1) if use_feats else None
+            W = ops.tube_transitions(sb, sf, 1, 1 + r, cfg.iou_weight, cfg.feat_weight)
+        else:
+            W = ops.tube_transitions(boxes.contiguous(), feats.contiguous() if use_feats else None, 0, r, cfg.iou_weight, cfg.feat_weight)
+        commit = ops.tube_stream_step(W, unary.contiguous(), keep.contiguous(), T, lag, self._delta, self._surv, self.forced)
+        rc, rb = (cen, boxes) if self._ring is None else (torch.cat([self._ring[0], cen]), torch.cat([self._ring[1], boxes], dim=1))
+        lo, hi = max(0, T - lag), max(0, T + r - lag)                      # the ring begins at centre lo; [lo, hi) leave
+        tube = commit[:, r - (hi - lo):]
+        tb = torch.gather(rb[:, :hi - lo], 2, tube[:, :, None, None].expand(-1, -1, 1, 4))[:, :, 0]
+        out = (rc[:hi - lo], tube, tb)
+        self._ring = (_own(rc[hi - lo:]), _own(rb[:, hi - lo:]))
+        self._last = (_own(boxes[:, r - 1:r]), _own(feats[:, r - 1:r]) if use_feats else None)
+        rest = self._pend[0].numel() - r
+        self._pend = tuple(_own(t[r:] if i == 0 else t[:, r:]) for i, t in enumerate(self._pend)) if rest else None
+        self._t = T + r
+        return out
+
+    def _take(self, part: VideoResult, Q: int, k: int):
+        dev = part.cand_scores.device
+        if self._delta is None:
+            self._delta = torch.empty((Q, k), dtype=torch.float32, device=dev)
+            self._surv = torch.zeros((Q, self.lag, k), dtype=torch.uint8, device=dev)
+            self.forced = torch.zeros(Q, dtype=torch.int32, device=dev)
+        keep = part.cand_keep
+        keep = keep.view(torch.uint8) if keep.dtype == torch.bool else keep
+        new = (part.centres, part.cand_boxes.float(), part.cand_feats.float(), keep, part.cand_scores.float())
+        self._pend = new if self._pend is None else tuple(torch.cat([a, b], dim=0 if i == 0 else 1)
+                                                          for i, (a, b) in enumerate(zip(self._pend, new)))
+
+    @torch.no_grad()
+    def push(self, part: Optional[VideoResult]) -> Optional[TubeChunk]:
+        """The next part of the stream (what ``VideoGrounder.push`` / ``flush`` returned; None: nothing).  Returns the fused choices
+        and tube entries that this part completed, or None."""
+        if part is None:
+            return None
+        Q, m, k = _check_stream_part(part, self._qk, "TubeStream.push", True)
+        self._qk = (Q, k)
+        fchunk = self._fs.push(part)
+        self._take(part, Q, k)
+        if self.link.unary == "fused":
+            r, unary = (0, None) if fchunk is None else (fchunk.fused.shape[1], fchunk.fused)
+        else:
+            r, unary = m, self._pend[4]
+        out = self._advance(r, unary) if r else None
+        if out is None and fchunk is None:
+            return None
+        if out is None:
+            dev = part.cand_scores.device
+            out = (part.centres[:0], torch.empty((Q, 0), dtype=torch.int64, device=dev), torch.empty((Q, 0, 4), device=dev))
+        return TubeChunk(centres=out[0], tube=out[1], tube_boxes=out[2], fused=fchunk)
+
+    @torch.no_grad()
+    def flush(self) -> Optional[TubeChunk]:
+        """End of the stream: the centres not released yet and ``tube_score``; None if no centre ever arrived.  The stream is empty
+        afterwards; ``forced`` keeps the count of the finished stream until the next ``push``."""
+        from . import ops
+        fchunk = self._fs.flush()
+        outs = []
+        if self._pend is not None:                                         # (unary "fused": the centres that waited for the end)
+            outs.append(self._advance(self._pend[0].numel(), fchunk.fused))
+        if not self._t:
+            self._reset()
+            return None
+        tail, score = ops.tube_stream_flush(self._delta, self._surv, self._t, self.lag)
+        rc, rb = self._ring
+        outs.append((rc, tail, torch.gather(rb, 2, tail[:, :, None, None].expand(-1, -1, 1, 4))[:, :, 0]))
+        cen, tube, tb = (torch.cat([o[i] for o in outs], dim=0 if i == 0 else 1) for i in range(3))
+        forced = self.forced
+        self._reset()
+        self.forced = forced
+        return TubeChunk(centres=cen, tube=tube, tube_boxes=tb, fused=fchunk, tube_score=score)
+
 
 # ---- command line -------------------------------------------------------------------------------------------------------------
 def synthetic_model(size: int, device):
@@ -627,6 +877,8 @@ def main(argv=None):
     ap.add_argument("--queries", type=int, default=1)
     ap.add_argument("--topk", type=int, default=None)
     ap.add_argument("--link", action="store_true", help="link the top-k candidates into one track per query (needs --topk); prints the tube boxes")
+    ap.add_argument("--stream-tubes", action="store_true", help="with --link: push the video chunk by chunk through a TubeStream, keep no part; prints the tube boxes as they are released")
+    ap.add_argument("--lag", type=int, default=16, help="--stream-tubes: centres a tube entry trails the newest one (1 ... 64)")
     ap.add_argument("--raw-frames", action="store_true", help="375x500 uint8 frames through prep.prepare_clips(augment=False); prints source-pixel boxes")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--precision", default="fp32", choices=sorted(BANK_BYTES_PER_VALUE), help="ops.set_precision mode of the run")
@@ -658,7 +910,11 @@ def _main_run(a):
     image, word_id = image.to(dev), word_id.to(dev)
     if a.link and a.topk is None:
         raise SystemExit("--link needs --topk")
+    if a.stream_tubes and not a.link:
+        raise SystemExit("--stream-tubes needs --link")
     vg = VideoGrounder(m, n_frame=a.n_frame, border=a.border, chunk=a.chunk, topk=a.topk, link=TubeLink() if a.link else None)
+    if a.stream_tubes:
+        return _main_stream(a, vg, image, word_id, meta)
     times = []
     for _ in range(a.repeat + 1):
         torch.cuda.synchronize()
@@ -677,6 +933,53 @@ def _main_run(a):
             print(f"frame {c}: {what}" + " ".join(f"{v:.1f}" for v in b[i].tolist()))
         if a.link:
             print(f"tube score {float(res.tube_score[0]):.4f}, candidates kept by the NMS: {float(res.cand_keep[0].float().sum(-1).mean()):.1f} of {a.topk} per centre")
+
+
+def _main_stream(a, vg, image, word_id, meta):
+    """--stream-tubes: every part goes to the TubeStream and is dropped.  The first pass (untimed) prints the tube boxes as they are
+    released; the timed passes keep only the released chunks."""
+    import time
+    import numpy as np
+    what = "tube box" + (" (source pixels) " if a.raw_frames else " (letterbox pixels) ")
+
+    def one_pass(show: bool):
+        vg.reset(word_id, total=a.frames)
+        ts = vg.tube_stream(a.lag)
+        n_out, peak_state, last = 0, 0, None
+        parts = list(range(0, a.frames, a.chunk)) + [None]
+        for i0 in parts:
+            if i0 is None:
+                part = vg.flush()
+            else:
+                part = vg.push(image[i0:i0 + a.chunk], None if meta is None else tuple(x[i0:i0 + a.chunk] for x in meta))
+            chunks = [ts.push(part)]
+            del part
+            peak_state = max(peak_state, ts.state_bytes())
+            if i0 is None:
+                chunks.append(ts.flush())
+            for ch in chunks:
+                if ch is None:
+                    continue
+                last = ch
+                n_out += ch.centres.numel()
+                if show:
+                    for c, b in zip(ch.centres.cpu().tolist(), ch.tube_boxes[0].cpu().tolist()):
+                        print(f"frame {c}: {what}" + " ".join(f"{v:.1f}" for v in b))
+        return n_out, peak_state, last, ts.forced
+
+    times = []
+    for r in range(a.repeat + 1):
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        t0 = time.perf_counter()
+        n_out, state, last, forced = one_pass(show=r == 0)
+        torch.cuda.synchronize()
+        times.append(time.perf_counter() - t0)
+    t = float(np.median(times[1:])) if len(times) > 1 else times[0]
+    print(f"{a.frames} frames {a.size}x{a.size}, n_frame {a.n_frame}, border {a.border}, {a.queries} quer{'y' if a.queries == 1 else 'ies'}, "
+          f"{a.precision}, streamed tubes (lag {a.lag}): {n_out} centres in {t * 1e3:.1f} ms = {a.frames / t:.1f} frames/s, peak memory "
+          f"{torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB, stream state {state / 2 ** 20:.2f} MiB")
+    print(f"tube score {float(last.tube_score[0]):.4f}, forced {forced.cpu().tolist()}")
 
 
 if __name__ == "__main__":

@@ -672,6 +672,19 @@ int dcn_tube_forward(const float* W, const float* unary, const unsigned char* ke
 /* The best path: delta [q][k] = delta_{n-1}, score [q] = its maximum, path [q][n]: path[n-1] = its first arg-max,
  * path[t-1] = backptr[t][path[t]]. */
 int dcn_tube_backtrack(const unsigned char* backptr, const float* delta, int q, int n, int k, int64_t* path, float* score, void* stream);
+/* Streaming forward pass with commitment (additive, ABI 318): dcn_tube_forward's recursion over the m centres
+ * t0 ... t0+m-1 of one push, 1 <= lag <= 64.  W [q][m][k][k]: row i = the transitions into frame t0+i, as dcn_tube_transitions wrote
+ * them (row 0 unread when t0 == 0); unary [q][m][k]; keep [q][m][k] bytes or NULL; delta [q][k] in/out (unread when t0 == 0);
+ * surv [q][lag][k] bytes in/out (unread when t0 == 0): surv[q][b][j] = the candidate of frame t-lag+b on the best path into candidate
+ * j of the newest frame t.  After step t >= lag frame t - lag is committed: a[j] = surv[q][0][j]; c = a[first arg-max of delta_t];
+ * if a live j (delta_t[j] > -inf) has a[j] != c, forced[q] += 1 and delta_t[j] = -inf for every j with a[j] != c.
+ * commit [q][m]: entry i = c of frame t0+i-lag, or -1 where t0+i < lag.  forced [q] int32 accumulates (zero it before the first call). */
+int dcn_tube_stream_step(const float* W, const float* unary, const unsigned char* keep, int q, int m, int k, int t0, int lag,
+                         float* delta, unsigned char* surv, int64_t* commit, int* forced, void* stream);
+/* End of a stream of n frames: delta, surv as the last dcn_tube_stream_step left them.  score [q] = max delta_{n-1};
+ * tail [q][min(lag,n)] = frames n - min(lag,n) ... n-1 of the walk back from the first arg-max of delta_{n-1}. */
+int dcn_tube_stream_flush(const float* delta, const unsigned char* surv, int q, int k, int n, int lag, int64_t* tail, float* score,
+                          void* stream);
 
 /* ---- clip preprocessing: letterbox, flip, HSV and affine warp of decoded frames (ABI 309) ---------------------------- */
 /* One record per frame of the batch (host-built by dcnet_amd/prep.py; dataset/vid_loader.py:333-395 draws the parameters,
