@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from dcnet_amd import postprocess as PP
+import post_ref as PR
 import post_torch as PT
 from dcnet_amd.utils.synth import synth_head_outputs
 from oracle import post_oracle as PO
@@ -135,6 +136,10 @@ def test_post_kernels_against_the_torch_forms():
         assert c1[:, :3].tolist() == [[[0, 2, 0, 5], [1, 0, 2, 3], [1, 1, 1, 1]]] * B             # ties: flat-index order
         assert torch.equal(c1[:, 3:], c2[:, 3:]) and torch.equal(f1[:, 3:], f2[:, 3:])              # (torch.topk orders ties its own way)
         assert (b1[:, 3:] - b2[:, 3:]).abs().max() < 1e-3
+        n_ = lambda t: t.cpu().numpy()
+        ref = PR.topk_ref([n_(o) for o in outbox], [n_(c) for c in corr], size, k, n_(ratio), n_(dw), n_(dh), n_(hw))
+        assert np.array_equal(n_(c1), ref.cells) and np.array_equal(n_(f1), ref.feats)              # every slot, the tied ones included
+        assert np.abs(n_(b1) - ref.boxes).max() < 1e-3
         again = PP.topk_candidates(outbox, corr, size, k, ratio, dw, dh, hw)
         assert all(torch.equal(x, y) for x, y in zip((b1, s1, f1, c1), again))
         R = 5
