@@ -581,14 +581,16 @@ __global__ __launch_bounds__(256) void pad_rows_kernel(const float* __restrict__
     dst[(size_t)r * ldd + c] = c < cols ? src[(size_t)r * lds_ + c] : 0.f;
 }
 
+// Fills every field of g whatever it returns: callers print g.P in their error text, and a field left unset on the failing path made
+// that path undefined behaviour, which the optimiser used to drop the hw / ld check of dcn_head_obj altogether.
 int fill_geom(Geom3& g, const int* hw, const int* ld, int pad32) {
-  int off = 0;
+  int off = 0, bad = 0;
   for (int s = 0; s < 3; ++s) {
-    if (hw[s] <= 0 || ld[s] < 15) return -1;
-    g.hw[s] = hw[s]; g.off[s] = off; g.ld[s] = ld[s]; off += hw[s];
+    if (hw[s] <= 0 || ld[s] < 15) bad = 1;
+    g.hw[s] = hw[s]; g.off[s] = off; g.ld[s] = ld[s]; off += hw[s] > 0 ? hw[s] : 0;
   }
   g.P = off; g.Ppad = pad32 ? (off + 31) / 32 * 32 : off;
-  return 0;
+  return bad ? -1 : 0;
 }
 
 }  // namespace
