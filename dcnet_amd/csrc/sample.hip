@@ -18,8 +18,9 @@ namespace {
 constexpr int SK_MAXK = 64;       // top-k entries per pair (the reference uses 30)
 constexpr int SK_T = 1024;
 
-__device__ __forceinline__ unsigned ord_key(float v) {          // order-preserving float -> uint
-  const unsigned b = __float_as_uint(v);
+__device__ __forceinline__ unsigned ord_key(float v) {          // order-preserving float -> uint; -0.0 gets the key of +0.0
+  unsigned b = __float_as_uint(v);
+  if (b == 0x80000000u) b = 0u;
   return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
 }
 
@@ -29,7 +30,8 @@ __device__ __forceinline__ void wave_copy_row(const float* __restrict__ src, flo
 }
 
 // One workgroup per frame pair: radix-select the top_k largest of cmap[pair][HW*HW] (ties: lowest flat index first),
-// sort them (value descending, index ascending), then gather q / k / negatives.
+// sort them (value descending, index ascending), then gather q / k / negatives.  Ties are by numeric value: +0.0 and -0.0 are equal
+// (ord_key), as they are to torch.topk; inputs are finite.
 __global__ __launch_bounds__(SK_T) void k9_fwd_kernel(const float* __restrict__ cmap, const float* __restrict__ fv, const int64_t* __restrict__ raw_neg,
                                                       int HW, int E, int top_k, int neg_n,
                                                       int64_t* __restrict__ index, int64_t* __restrict__ neg_idx,
@@ -430,7 +432,8 @@ extern "C" int dcn_k9_fwd(const float* cmap, const float* fv, const int64_t* raw
 extern "C" int dcn_k9_bwd(const int64_t* index, const int64_t* neg_idx, const float* d_frame, const float* d_corr, const float* d_neg,
                           int pairs, int hw, int e, int top_k, int neg_n, float* dfv, void* stream) {
   DCN_CHECK_ARG(index && neg_idx && d_frame && d_corr && d_neg && dfv && pairs > 0 && hw > 0 && e > 0, "k9_bwd: bad argument");
-  const size_t lds = (size_t)((top_k + top_k * neg_n) * (K9B_GP + 1) + K9B_GP) * sizeof(int);
+  DCN_CHECK_ARG(top_k > 0 && neg_n >= 0, "k9_bwd: bad list sizes (top_k=%d, neg_n=%d)", top_k, neg_n);
+  const size_t lds = ((size_t)top_k * ((size_t)neg_n + 1) * (K9B_GP + 1) + K9B_GP) * sizeof(int);
   DCN_CHECK_ARG(lds <= 64 * 1024, "k9_bwd: %zu bytes of LDS (top_k=%d, neg_n=%d)", lds, top_k, neg_n);
   hipLaunchKernelGGL(k9_bwd_kernel, dim3(cdiv(hw, K9B_GP), 2, pairs), dim3(256), lds, (hipStream_t)stream, index, neg_idx, d_frame, d_corr,
                      d_neg, hw, e, top_k, neg_n, dfv);
@@ -489,7 +492,9 @@ extern "C" int dcn_k14_negscatter(const float* d_neg, const int* csr_off, const 
 extern "C" int dcn_k14_dlag(const float* lag, const float* lnorm, const int64_t* cols, const float* d_k, int n, int l, int hw, int e,
                             float* dcontext, void* stream) {
   DCN_CHECK_ARG(lag && lnorm && cols && d_k && dcontext && n > 0 && l > 0 && l <= CM_MAXL && hw > 0 && e > 0, "k14_dlag: bad argument");
-  hipLaunchKernelGGL(k14_dlag_kernel, dim3(n, cdiv(e, DL_C)), dim3(DL_C), (size_t)(2 * hw + CM_MAXL + 1) * sizeof(int), (hipStream_t)stream,
+  const size_t lds = (2 * (size_t)hw + CM_MAXL + 1) * sizeof(int);
+  DCN_CHECK_ARG(lds <= 64 * 1024, "k14_dlag: %zu bytes of LDS needed (HW=%d)", lds, hw);
+  hipLaunchKernelGGL(k14_dlag_kernel, dim3(n, cdiv(e, DL_C)), dim3(DL_C), lds, (hipStream_t)stream,
                      lag, lnorm, cols, d_k, l, hw, e, dcontext);
   DCN_CHECK_LAUNCH("k14_dlag");
   return DCN_OK;
