@@ -322,6 +322,10 @@ __global__ __launch_bounds__(256) void contrastive_bwd_kernel(const float* __res
 }
 
 // ---- evaluation decode ---------------------------------------------------------------------------------------------
+// Order of the arg-max (torch.max): NaN ranks above every number, NaNs tie with each other; ties go to the lower index.
+__device__ __forceinline__ bool conf_gt(float a, float b) { return a > b || (a != a && b == b); }
+__device__ __forceinline__ bool conf_eq(float a, float b) { return a == b || (a != a && b != b); }
+
 __global__ __launch_bounds__(256) void decode_kernel(const CP3 outbox, const float* __restrict__ anchors, int size, int N,
                                                      float* __restrict__ boxes, int* __restrict__ cellinfo) {
   __shared__ float sv[4]; __shared__ int si[4];
@@ -330,17 +334,18 @@ __global__ __launch_bounds__(256) void decode_kernel(const CP3 outbox, const flo
   float best = -INFINITY; int arg = 0x7fffffff;
   for (int j = tid; j < 3 * G.P; j += 256) {
     const float v = *conf_ptr(outbox, G, n, j);
-    if (v > best) { best = v; arg = j; }                        // (ascending j per thread: first maximum)
+    if (conf_gt(v, best)) { best = v; arg = j; }                // (ascending j per thread: first maximum)
   }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ov = __shfl_xor(best, o); const int oi = __shfl_xor(arg, o);
-    if (ov > best || (ov == best && oi < arg)) { best = ov; arg = oi; }
+    if (conf_gt(ov, best) || (conf_eq(ov, best) && oi < arg)) { best = ov; arg = oi; }
   }
   if ((tid & 63) == 0) { sv[tid >> 6] = best; si[tid >> 6] = arg; }
   __syncthreads();
   if (tid == 0) {
-    for (int w = 1; w < 4; ++w) if (sv[w] > best || (sv[w] == best && si[w] < arg)) { best = sv[w]; arg = si[w]; }
+    for (int w = 1; w < 4; ++w) if (conf_gt(sv[w], best) || (conf_eq(sv[w], best) && si[w] < arg)) { best = sv[w]; arg = si[w]; }
+    if (arg == 0x7fffffff) arg = 0;                                                // every confidence -inf: index 0, as torch.max
     const int s = arg < G.off3[1] ? 0 : (arg < G.off3[2] ? 1 : 2);                 // :779-787
     const int g = G.g[s], gg = g * g, r = arg - G.off3[s], a = r / gg, cell = r - a * gg, gj = cell / g, gi = cell - gj * g;
     const float* t = outbox.p[s] + ((size_t)n * 15 + a * 5) * gg + cell;
@@ -376,7 +381,8 @@ extern "C" int dcn_build_target(const float* bbox, const float* anchors, int siz
 extern "C" int dcn_target_dense(const int* target_i, const float* target_f, int size, int n, float* const* bbox_list,
                                 float* const* center_list, void* stream) {
   P3 b, c;
-  DCN_CHECK_ARG(target_i && target_f && n > 0 && set3(b, bbox_list) == 0 && set3(c, center_list) == 0, "target_dense: bad argument");
+  DCN_CHECK_ARG(target_i && target_f && n > 0 && size >= 32 && size % 32 == 0 && set3(b, bbox_list) == 0 && set3(c, center_list) == 0,
+                "target_dense: bad argument");
   hipLaunchKernelGGL(target_dense_kernel, dim3(cdiv(n, 64)), dim3(64), 0, (hipStream_t)stream, target_i, target_f, size, n, b, c);
   DCN_CHECK_LAUNCH("target_dense");
   return DCN_OK;
@@ -401,7 +407,7 @@ extern "C" int dcn_dense_loss_bwd(const float* const* outbox, const float* const
   CP3 ob, sm, ns, lc; P3 dob, dsm, dns, dlc;
   DCN_CHECK_ARG(set3(ob, outbox) == 0 && set3(sm, sim) == 0 && set3(ns, negsim) == 0 && set3(lc, loc) == 0, "dense_loss_bwd: null map");
   DCN_CHECK_ARG(set3(dob, d_outbox) == 0 && set3(dsm, d_sim) == 0 && set3(dns, d_negsim) == 0 && set3(dlc, d_loc) == 0, "dense_loss_bwd: null output");
-  DCN_CHECK_ARG(target_i && target_f && lse && grad_out && n > 0, "dense_loss_bwd: bad argument");
+  DCN_CHECK_ARG(target_i && target_f && lse && grad_out && n > 0 && size >= 32 && size % 32 == 0, "dense_loss_bwd: bad argument");
   hipLaunchKernelGGL(dense_loss_bwd_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, ob, sm, ns, lc, target_i, target_f, lse, grad_out,
                      size, n, dob, dsm, dns, dlc);
   DCN_CHECK_LAUNCH("dense_loss_bwd");

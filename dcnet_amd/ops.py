@@ -1565,74 +1565,151 @@ def k14_dlag(lag, ln, cols, d_k):
 
 
 # ---- losses, targets, decode --------------------------------------------------------------------------------------
+# Shapes and dtypes are checked on the host before any launch (tuple comparisons only: no synchronisation); the kernels index the
+# maps by `size` and `n` alone.
+def _loss_size(size, name):
+    if isinstance(size, (bool, torch.Tensor)) or not hasattr(size, "__index__") or size < 32 or size % 32 != 0:
+        raise ValueError(f"{name}: size must be an integer multiple of 32, at least 32, got {size!r}")
+    size = int(size)
+    return [size // 32, size // 16, size // 8]
+
+
+def _chk_as(t, shape, dtype, name):
+    if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape) == tuple(shape)):
+        got = (t.dtype, str(t.device), tuple(t.shape), t.is_contiguous()) if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{name}: expected a contiguous {dtype} CUDA tensor of shape {tuple(shape)}, got {got}")
+
+
+def _chk_maps(maps, n, lead, grids, name):
+    if not (isinstance(maps, (list, tuple)) and len(maps) == 3):
+        raise ValueError(f"{name}: expected a list of 3 maps, one per scale")
+    for s, g in enumerate(grids):
+        _chk_as(maps[s], (n, *lead, g, g), torch.float32, f"{name}[{s}]")
+
+
+def _chk_target(ti, tf, name):
+    if not (isinstance(ti, torch.Tensor) and ti.dim() == 2 and ti.shape[0] > 0):
+        raise ValueError(f"{name}: target_i must be (N, 4) with N > 0")
+    n = ti.shape[0]
+    _chk_as(ti, (n, 4), torch.int32, f"{name} target_i"); _chk_as(tf, (n, 4), torch.float32, f"{name} target_f")
+    return n
+
+
 def build_target(bbox, anchors, size):
+    _loss_size(size, "build_target")
+    if not (isinstance(bbox, torch.Tensor) and bbox.dim() == 2 and bbox.shape[0] > 0):
+        raise ValueError("build_target: bbox must be (N, 4) with N > 0")
     n = bbox.shape[0]
+    _chk_as(bbox, (n, 4), torch.float32, "build_target bbox"); _chk_as(anchors, (3, 3, 2), torch.float32, "build_target anchors")
     ti = torch.empty((n, 4), dtype=torch.int32, device=bbox.device); tf = torch.empty((n, 4), dtype=torch.float32, device=bbox.device)
-    _chk(bbox, "build_target bbox")
     lib().build_target(bbox.data_ptr(), anchors.data_ptr(), size, n, ti.data_ptr(), tf.data_ptr(), _s())
     return ti, tf
 
 
-def target_dense(ti, tf, size):
-    n = ti.shape[0]
-    grids = [size // 32, size // 16, size // 8]
-    box = [torch.zeros((n, 3, 5, g, g), dtype=torch.float32, device=ti.device) for g in grids]
-    ctr = [torch.zeros((n, 5, g, g), dtype=torch.float32, device=ti.device) for g in grids]
+def target_dense(ti, tf, size, out=None):
+    """out = (box[3], ctr[3]): caller-supplied, pre-zeroed (N,3,5,g,g) / (N,5,g,g) tensors (the kernel writes the positive cells only)."""
+    grids = _loss_size(size, "target_dense")
+    n = _chk_target(ti, tf, "target_dense")
+    if out is None:
+        box = [torch.zeros((n, 3, 5, g, g), dtype=torch.float32, device=ti.device) for g in grids]
+        ctr = [torch.zeros((n, 5, g, g), dtype=torch.float32, device=ti.device) for g in grids]
+    else:
+        box, ctr = out
+        _chk_maps(box, n, (3, 5), grids, "target_dense out box"); _chk_maps(ctr, n, (5,), grids, "target_dense out center")
     lib().target_dense(ti.data_ptr(), tf.data_ptr(), size, n, _ptrs(box), _ptrs(ctr), _s())
     return box, ctr
 
 
-def dense_loss_fwd(outbox, sim, negsim, loc, ti, tf, size):
-    n = ti.shape[0]
+def _chk_dense(outbox, sim, negsim, loc, ti, tf, size, name):
+    grids = _loss_size(size, name)
+    n = _chk_target(ti, tf, name)
+    _chk_maps(outbox, n, (15,), grids, f"{name} outbox")
+    for maps, what in ((sim, "sim"), (negsim, "negsim"), (loc, "loc")):
+        _chk_maps(maps, n, (), grids, f"{name} {what}")
+    return n, grids
+
+
+def dense_loss_fwd(outbox, sim, negsim, loc, ti, tf, size, want_vals=False):
+    """Returns (out (3,) = yolo, rank, loc; lse (N,2)), and with want_vals the per-sample terms vals (N,8) as a third."""
+    n, _ = _chk_dense(outbox, sim, negsim, loc, ti, tf, size, "dense_loss_fwd")
     dev = ti.device
     vals = torch.empty((n, 8), dtype=torch.float32, device=dev); lse = torch.empty((n, 2), dtype=torch.float32, device=dev)
     out = torch.empty(3, dtype=torch.float32, device=dev)
-    for t in list(outbox) + list(sim) + list(negsim) + list(loc):
-        _chk(t, "dense_loss map")
     lib().dense_loss_fwd(_ptrs(outbox), _ptrs(sim), _ptrs(negsim), _ptrs(loc), ti.data_ptr(), tf.data_ptr(), size, n, vals.data_ptr(),
                          lse.data_ptr(), out.data_ptr(), _s())
-    return out, lse
+    return (out, lse, vals) if want_vals else (out, lse)
 
 
-def dense_loss_bwd(outbox, sim, negsim, loc, ti, tf, lse, gout, size):
-    n = ti.shape[0]
-    d_ob = [torch.empty_like(t) for t in outbox]; d_sim = [torch.empty_like(t) for t in sim]
-    d_ns = [torch.empty_like(t) for t in negsim]; d_loc = [torch.empty_like(t) for t in loc]
-    _chk(gout, "dense_loss gout")
+def dense_loss_bwd(outbox, sim, negsim, loc, ti, tf, lse, gout, size, out=None):
+    """out = (d_outbox[3], d_sim[3], d_negsim[3], d_loc[3]): caller-supplied tensors of the inputs' shapes (every element is written)."""
+    n, grids = _chk_dense(outbox, sim, negsim, loc, ti, tf, size, "dense_loss_bwd")
+    _chk_as(lse, (n, 2), torch.float32, "dense_loss_bwd lse"); _chk_as(gout, (3,), torch.float32, "dense_loss_bwd gout")
+    if out is None:
+        d_ob = [torch.empty_like(t) for t in outbox]; d_sim = [torch.empty_like(t) for t in sim]
+        d_ns = [torch.empty_like(t) for t in negsim]; d_loc = [torch.empty_like(t) for t in loc]
+    else:
+        d_ob, d_sim, d_ns, d_loc = out
+        _chk_maps(d_ob, n, (15,), grids, "dense_loss_bwd out d_outbox")
+        for maps, what in ((d_sim, "d_sim"), (d_ns, "d_negsim"), (d_loc, "d_loc")):
+            _chk_maps(maps, n, (), grids, f"dense_loss_bwd out {what}")
     lib().dense_loss_bwd(_ptrs(outbox), _ptrs(sim), _ptrs(negsim), _ptrs(loc), ti.data_ptr(), tf.data_ptr(), lse.data_ptr(), gout.data_ptr(),
                          size, n, _ptrs(d_ob), _ptrs(d_sim), _ptrs(d_ns), _ptrs(d_loc), _s())
     return d_ob, d_sim, d_ns, d_loc
 
 
+def _chk_contrastive(q, pos, neg, name):
+    """q, pos (..., e), neg (..., m, e) with the same leading shape -> rows, e, m."""
+    if not (isinstance(q, torch.Tensor) and q.dim() >= 1 and q.numel() > 0):
+        raise ValueError(f"{name}: q must be a non-empty (..., e) tensor")
+    _chk_as(q, q.shape, torch.float32, f"{name} q"); _chk_as(pos, q.shape, torch.float32, f"{name} pos")
+    e = q.shape[-1]
+    if not (isinstance(neg, torch.Tensor) and neg.dim() == q.dim() + 1 and neg.shape[-2] > 0):
+        raise ValueError(f"{name}: neg must be {tuple(q.shape[:-1])} + (m, {e}) with m > 0")
+    m = neg.shape[-2]
+    _chk_as(neg, (*q.shape[:-1], m, e), torch.float32, f"{name} neg")
+    return q.numel() // e, e, m
+
+
 def contrastive_fwd(q, pos, neg, temperature):
     """q, pos [rows][e], neg [rows][m][e] contiguous.  Returns the mean InfoNCE loss (0-dim tensor)."""
-    e = q.shape[-1]
-    rows = q.numel() // e
-    m = neg.numel() // (rows * e)
-    for t in (q, pos, neg):
-        _chk(t, "contrastive")
+    rows, e, m = _chk_contrastive(q, pos, neg, "contrastive_fwd")
     rl = scratch(rows, q.device, slot=4)
     loss = torch.empty((), dtype=torch.float32, device=q.device)
     lib().contrastive_fwd(q.data_ptr(), pos.data_ptr(), neg.data_ptr(), rows, e, m, float(temperature), rl.data_ptr(), loss.data_ptr(), _s())
     return loss
 
 
-def contrastive_bwd(q, pos, neg, temperature, gout):
-    e = q.shape[-1]
-    rows = q.numel() // e
-    m = neg.numel() // (rows * e)
-    dq = torch.empty_like(q); dpos = torch.empty_like(pos); dneg = torch.empty_like(neg)
+def contrastive_bwd(q, pos, neg, temperature, gout, out=None):
+    """out = (dq, dpos, dneg): caller-supplied tensors of the inputs' shapes (every element is written)."""
+    rows, e, m = _chk_contrastive(q, pos, neg, "contrastive_bwd")
+    _chk_as(gout, (1,), torch.float32, "contrastive_bwd gout")
+    if out is None:
+        dq = torch.empty_like(q); dpos = torch.empty_like(pos); dneg = torch.empty_like(neg)
+    else:
+        dq, dpos, dneg = out
+        _chk_as(dq, q.shape, torch.float32, "contrastive_bwd out dq"); _chk_as(dpos, q.shape, torch.float32, "contrastive_bwd out dpos")
+        _chk_as(dneg, neg.shape, torch.float32, "contrastive_bwd out dneg")
     lib().contrastive_bwd(q.data_ptr(), pos.data_ptr(), neg.data_ptr(), rows, e, m, float(temperature), gout.data_ptr(),
                           dq.data_ptr(), dpos.data_ptr(), dneg.data_ptr(), _s())
     return dq, dpos, dneg
 
 
-def decode_boxes(outbox, anchors, size, want_cells=False):
+def decode_boxes(outbox, anchors, size, want_cells=False, out=None):
+    """out = (boxes (N,4) fp32, cells (N,3) int32 or None): caller-supplied outputs."""
+    grids = _loss_size(size, "decode_boxes")
+    if not (isinstance(outbox, (list, tuple)) and len(outbox) == 3 and isinstance(outbox[0], torch.Tensor) and outbox[0].dim() == 4
+            and outbox[0].shape[0] > 0):
+        raise ValueError("decode_boxes: outbox must be 3 maps (N,15,g,g) with N > 0")
     n = outbox[0].shape[0]
-    for t in outbox:
-        _chk(t, "decode outbox")
-    boxes = torch.empty((n, 4), dtype=torch.float32, device=outbox[0].device)
-    cells = torch.empty((n, 3), dtype=torch.int32, device=outbox[0].device) if want_cells else None
+    _chk_maps(outbox, n, (15,), grids, "decode_boxes outbox"); _chk_as(anchors, (3, 3, 2), torch.float32, "decode_boxes anchors")
+    if out is None:
+        boxes = torch.empty((n, 4), dtype=torch.float32, device=outbox[0].device)
+        cells = torch.empty((n, 3), dtype=torch.int32, device=outbox[0].device) if want_cells else None
+    else:
+        boxes, cells = out
+        _chk_as(boxes, (n, 4), torch.float32, "decode_boxes out boxes")
+        if cells is not None:
+            _chk_as(cells, (n, 3), torch.int32, "decode_boxes out cells")
     lib().decode_boxes(_ptrs(outbox), anchors.data_ptr(), size, n, boxes.data_ptr(), _p(cells), _s())
     return (boxes, cells) if want_cells else boxes
 
@@ -1964,7 +2041,9 @@ def tube_stream_flush(delta, surv, n, lag):
 
 
 def box_iou(b1, b2):
-    _chk(b1, "box_iou"); _chk(b2, "box_iou")
+    if not (isinstance(b1, torch.Tensor) and b1.dim() == 2 and b1.shape[0] > 0):
+        raise ValueError("box_iou: boxes must be (N, 4) with N > 0")
+    _chk_as(b1, (b1.shape[0], 4), torch.float32, "box_iou box1"); _chk_as(b2, b1.shape, torch.float32, "box_iou box2")
     iou = torch.empty(b1.shape[0], dtype=torch.float32, device=b1.device)
     lib().box_iou(b1.data_ptr(), b2.data_ptr(), b1.shape[0], iou.data_ptr(), _s())
     return iou

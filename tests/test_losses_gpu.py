@@ -1,7 +1,9 @@
 """The caller-side pieces of the hot path on the device (dcnet_amd.losses: target assignment, the five losses, box
-decode, IoU) against the oracle's line-by-line restatement of train_DCNet.py:45-220,265-332,764-816 — the same three
-comparisons as tests/test_losses_cpu.py, on device tensors (this is the path a training step runs), plus the gradients
-of the total loss with respect to every model output."""
+decode, IoU) against the oracle's line-by-line restatement of train_DCNet.py:45-220,265-332,764-816, on device tensors
+(this is the path a training step runs), plus the gradients of the total loss with respect to every model output.  These
+are whole-path comparisons on random inputs; each kernel of csrc/loss.hip is pinned per element, at its edges, by
+tests/test_loss_edges_gpu.py over tests/loss_cases.py against tests/loss_ref.py (checked on the CPU by
+tests/test_loss_ref_host.py)."""
 import pytest
 import torch
 
