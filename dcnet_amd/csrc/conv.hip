@@ -66,13 +66,6 @@ void base_params(IgemmParams& p) {
   p.osy = p.osx = 1; p.isy = p.isx = 1; p.dense_out = 1;
 }
 
-// "same" padding, taps and output size of a k x k convolution over an h x wd map
-struct ConvShape {
-  int pad, T, ho, wo;
-  ConvShape(int h, int wd, int ksize, int stride)
-      : pad((ksize - 1) / 2), T(ksize * ksize), ho((h + 2 * pad - ksize) / stride + 1), wo((wd + 2 * pad - ksize) / stride + 1) {}
-};
-
 // forward: y[i,j] = sum_{r,s} x[i*stride + r - pad, j*stride + s - pad] . w[:,r,s,:]
 void fwd_geometry(IgemmParams& p, int n, int h, int wd, int cin, int cout, int ksize, int stride, int ldy, int ldr) {
   const ConvShape g(h, wd, ksize, stride);

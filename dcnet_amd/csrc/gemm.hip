@@ -2,12 +2,7 @@
 // LSTM cell kernels.  They carry the language branch of DCNet (model/DCNet_model.py:124-188 RNNEncoder,
 // :268-276 mapping_lang, :190-219 PhraseAttention): Linear layers and the BiLSTM's input / recurrent
 // projections are GEMMs with M = batch rows, the gate non-linearities are an elementwise kernel.
-#include "igemm.h"
-
-int tn_gemm_batched(const float* A, int lda, long long a_bs, const float* B, int ldb, long long b_bs,
-                    float* C, int ldc, long long c_bs, const float* row_scale,
-                    int M, int m_ld, int N, int K, int batch, int accumulate, hipStream_t stream,
-                    const unsigned* amax_a = nullptr, const unsigned* amax_b = nullptr);
+#include "wgrad.h"
 
 namespace {
 

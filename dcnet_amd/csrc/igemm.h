@@ -11,6 +11,12 @@
 
 #define IGEMM_MAX_TAPS 16
 
+// "same" padding, taps and output size of a k x k convolution over an h x wd map
+struct ConvShape {
+  int pad, T, ho, wo;
+  ConvShape(int h, int wd, int ksize, int stride)
+      : pad((ksize - 1) / 2), T(ksize * ksize), ho((h + 2 * pad - ksize) / stride + 1), wo((wd + 2 * pad - ksize) / stride + 1) {}
+};
 
 struct IgemmParams {
   const float* in;        // gathered tensor, NHWC, pixel stride ldi

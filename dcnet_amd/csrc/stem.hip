@@ -10,7 +10,7 @@
 //   * the block's [256 pixels][32 filters] go through LDS once: BatchNorm partial sums per 256 pixels (the layout of the igemm
 //     epilogue: [row][2][Co]), then scale / shift / LeakyReLU and fully coalesced stores, abs-max of what is stored.
 // Roofline: HBM (write of N*H*W*32 floats + read of N*H*W*4).
-#include "igemm.h"
+#include "wgrad.h"
 #include "prof.h"
 
 namespace {
@@ -160,7 +160,6 @@ int stem_launch(const IgemmParams& p, float* scratch, hipStream_t stream) {
 // in LDS (double buffered), wave w contracts positions 8w .. 8w+7 (four MFMAs), the four partial tiles meet in LDS at the end.
 // One [32][64] slab per workgroup in the c4 layout of the stem's filter bank (k = tap*4 + channel), summed in a fixed order by
 // reduce_slabs_kernel.  Roofline: HBM (y + dOut + X once: 3.0 GB).
-int wgrad_reduce_slabs(const float* ws, float* dw, int64_t n4, int splits, hipStream_t stream);
 
 namespace {
 

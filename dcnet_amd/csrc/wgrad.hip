@@ -10,9 +10,8 @@
 // partial slabs go to a workspace and are summed in a fixed order by reduce_slabs_kernel, so
 // the result is bitwise reproducible (no float atomics).
 // Roofline: MFMA (same 157.3 TFLOP/s fp32 peak as the forward).
-#include "igemm.h"
+#include "wgrad.h"
 #include "prof.h"
-#include "slabsum.h"
 #include <type_traits>
 
 #ifndef WG_OCC
@@ -675,39 +674,38 @@ DCN_KNOB(g_wg_target_b16, "qtargetb16", 768, "wgrad.hip: workgroups a bf16-stora
 DCN_KNOB(g_wg_target_small_b16, "qsmallb16", 512, "wgrad.hip: the same for its 1x1 / stride-2 layers (<= 0 = default)", [](int v) { return v > 0 ? v : 512; });
 int dispatch_wgrad(const WgradParams& p, int tm, int tn, int grid, int batch, hipStream_t stream);
 
-Plan make_plan(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
+// The tile of wgrad_kernel a layer runs on and its split-K plan.  esize 2 (bf16 storage): always the 128 x 128 one-plane tile with bf16
+// loads (narrower layers leave part of it empty: those launches are bound by their 9-fold gather, not by the matrix pipe).
+Plan make_plan(int esize, int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   Plan pl;
-  const int pad = (ksize - 1) / 2;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
-  pl.M = n * ho * wo;
-  const bool c4 = cin == 4;
+  const bool in16 = esize == 2;
+  const ConvShape g(h, wd, ksize, stride);
+  pl.M = n * g.ho * g.wo;
+  const bool c4 = !in16 && cin == 4;
   const int ci_axis = c4 ? 64 : cin;
   pl.tm = cout >= 128 ? 128 : (cout >= 64 ? 64 : 32);
   pl.tn = ci_axis >= 128 ? 128 : (ci_axis >= 64 ? 64 : 32);
   // one side at 64 channels: the 128x128 tile, half empty, has the f16-split build (the narrow tiles run on the fp32 pipe)
-  if (g_wide64 && !c4 && cout >= 64 && ci_axis >= 64 && (cout >= 128 || ci_axis >= 128)) pl.tm = pl.tn = 128;
+  if (in16 || (g_wide64 && !c4 && cout >= 64 && ci_axis >= 64 && (cout >= 128 || ci_axis >= 128))) pl.tm = pl.tn = 128;
   pl.tiles_co = cdiv(cout, pl.tm); pl.tiles_ci = cdiv(ci_axis, pl.tn);
-  pl.T = c4 ? 1 : ksize * ksize;
+  pl.T = c4 ? 1 : g.T;
   pl.ld_out = c4 ? 64 : pl.T * cin;
-  const int base = pl.tiles_co * pl.tiles_ci * pl.T;
-  // Workgroup count = base * splits.  256 CUs x 2 resident workgroups = 512 slots: aim for at most 1024
-  // workgroups (two full rounds) and never for "a round plus a few" — 1026 workgroups cost a third round
-  // for 2 of them (measured: -20 % on the 3x3 layers with the naive ceil(1024/base) choice).
-  const int max_splits = pl.M / 256 > 0 ? pl.M / 256 : 1;   // at least 8 K-steps per split
-  // 1x1 and stride-2 layers on the 128x128 tile (2 workgroups per CU = 512 slots) have few tiles, so the slab traffic of many
+  // Workgroup count = base * splits.  256 CUs x 2 resident workgroups = 512 slots: aim for at most 1024 workgroups (two full rounds),
+  // with at least 8 K-steps per split.
+  // fp32: 1x1 and stride-2 layers on the 128x128 tile (2 workgroups per CU = 512 slots) have few tiles, so the slab traffic of many
   // splits (splits x |W| written and read again) outweighs the finer balance: one full round of 512 workgroups beats 1024 by
   // 5-20 % there (256->128 @52: 0.105 -> 0.088 ms, 1024->512 @13: 0.079 -> 0.064), 256 loses again; the 3x3 stride-1 layers
   // lose 15-90 % at 512, and the narrow tiles of the 32/64-channel layers (more workgroups per CU, 11 M pixels) want all 1024.
-  const int target = ((ksize == 1 || stride == 2) && pl.tm == 128 && pl.tn == 128) ? g_wg_target_small : g_wg_target;
-  int splits = target / base;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  for (;;) {
-    pl.kchunk = cdiv(cdiv(pl.M, splits), 32) * 32;
-    pl.splits = cdiv(pl.M, pl.kchunk);
-    if (base * pl.splits <= target || splits == 1 || base > target) break;
-    --splits;
-  }
+  // bf16 storage, 3x3 stride-1 layers: with one MFMA per product the kernel is twice as fast as the f16-split tile while a slab costs the
+  // same, so fewer, longer splits win — tools/bench_b16.py --ab qtargetb16=..., N = 64: 1024 -> 768 workgroups 128->256 @52 0.169 -> 0.146 ms,
+  // 512->512 @52 1.25 -> 1.02, 64->128 @104 0.311 -> 0.243; 512 loses again on the 13-wide maps; the 1x1 / stride-2 layers keep 512: 256
+  // costs 15-70 %.  Its 1x1 / stride-2 layers: one full round of 768 as well once the launch is large — 1024->512 @52 0.303 -> 0.249 ms,
+  // 128->256 s2 @104 0.177 -> 0.151 —, 512 for the small residual 1x1 layers, whose slabs weigh more: 256->128 @52 0.048 vs 0.052.
+  const bool small_cls = ksize == 1 || stride == 2;
+  const int target = in16 ? (small_cls ? (2.0 * pl.M * (double)cin * cout * pl.T >= 3e10 ? g_wg_target_b16 : g_wg_target_small_b16) : g_wg_target_b16)
+                          : (small_cls && pl.tm == 128 && pl.tn == 128 ? g_wg_target_small : g_wg_target);
+  const SplitK sk = split_k(pl.M, pl.tiles_co * pl.tiles_ci * pl.T, target, 32, true);
+  pl.splits = sk.splits; pl.kchunk = sk.kchunk;
   return pl;
 }
 
@@ -776,7 +774,6 @@ int wgrad_reduce_slabs(const float* ws, float* dw, int64_t n4, int splits, hipSt
   DCN_CHECK_LAUNCH("reduce_slabs");
   return DCN_OK;
 }
-int wgrad_split_mode() { return g_wsplit; }
 
 // C[b][m][n] (+)= row_scale[b][m] * sum_k A[b][k][m] * B[b][k][n]   ("TN" GEMM: K is the strided dim of
 // both operands).  A may be loaded up to column m_ld (zero padded by its producer).  No split-K.
@@ -799,18 +796,6 @@ int tn_gemm_batched(const float* A, int lda, long long a_bs, const float* B, int
   return dispatch_wgrad(p, tm, tn, p.tiles_co * p.tiles_ci, batch, stream);
 }
 
-// wgrad3.hip: 3x3 stride-1 layers, one filter row per workgroup (f16 split)
-bool wgrad3_shape_ok(int n, int h, int wd, int cin, int cout, int ksize, int stride);
-int64_t wgrad3_ws(int n, int h, int wd, int cin, int cout);
-int wgrad3_launch(const float* x, int ldx, const float* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout,
-                  const uint32_t* amax_x, const uint32_t* amax_dy, int np, hipStream_t stream);
-
-// wgrad9.hip: the 3x3 layers with 32 input channels and 64 filters, nine taps per workgroup (f16 split)
-bool wgrad9_shape_ok(int n, int h, int wd, int cin, int cout, int ksize, int stride);
-int64_t wgrad9_ws(int n, int h, int wd, int cin, int cout, int stride);
-int wgrad9_launch(const float* x, int ldx, const float* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout, int stride,
-                  const uint32_t* amax_x, const uint32_t* amax_dy, const DcnPreAct* pre, hipStream_t stream);
-
 // wgrad1x_kernel: which layers, and its split-K plan
 DCN_KNOB(g_w1x, "Y1wide", 1, "wgrad.hip: 1x1 stride-1 weight gradients on the 256-wide tile (0 = 128x128 tile; n > 1 = workgroups a launch aims for)");
 struct Plan1x { int mi, tiles_co, tiles_ci, splits, kchunk; };
@@ -824,26 +809,20 @@ static Plan1x plan1x(int m, int cin, int cout) {
   Plan1x pl;
   pl.mi = cout <= 128 ? 2 : 4;
   pl.tiles_co = cdiv(cout, 64 * pl.mi); pl.tiles_ci = cdiv(cin, 256);
-  const int base = pl.tiles_co * pl.tiles_ci;
-  const int target = g_w1x > 1 ? g_w1x : 256;            // one workgroup (eight waves) per CU
-  int splits = target / base;
-  const int max_splits = m / 256 > 0 ? m / 256 : 1;       // at least 16 K-steps per split
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  pl.kchunk = cdiv(cdiv(m, splits), 16) * 16;
-  pl.splits = cdiv(m, pl.kchunk);
+  // one workgroup (eight waves) per CU, at least 16 K-steps per split
+  const SplitK sk = split_k(m, pl.tiles_co * pl.tiles_ci, g_w1x > 1 ? g_w1x : 256, 16, false);
+  pl.splits = sk.splits; pl.kchunk = sk.kchunk;
   return pl;
 }
 static int wgrad1x_launch(const float* x, int ldx, const float* dy, int lddy, float* dw, float* ws, uint32_t* counters, int m, int cin, int cout,
                           const uint32_t* amax_x, const uint32_t* amax_dy, hipStream_t stream) {
   const Plan1x pl = plan1x(m, cin, cout);
-  DCN_CHECK_ARG(pl.splits == 1 || ws, "conv2d_bwd_weight: workspace required (%d splits)", pl.splits);
+  SlabPath sp;
+  if (const int rc = slab_path(sp, wgrad_entry(4), dw, ws, counters, pl.tiles_co * pl.tiles_ci, pl.splits, 64LL * pl.mi * 256 * 4)) return rc;
   WgradParams p{};
-  p.x = x; p.dy = dy; p.out = pl.splits > 1 ? ws : dw;
+  p.x = x; p.dy = dy; p.out = sp.out; p.fold = sp.fold;
   p.Ci = cin; p.ldx = ldx; p.Co = cout; p.lddy = lddy; p.M = m; p.kchunk = pl.kchunk; p.splits = pl.splits;
   p.tiles_co = pl.tiles_co; p.tiles_ci = pl.tiles_ci; p.ld_out = cin; p.amax_x = amax_x; p.amax_dy = amax_dy;
-  const bool fold = slab_fold_ok(counters, pl.tiles_co * pl.tiles_ci, pl.splits, 64LL * pl.mi * 256 * 4, g_slab_fold);
-  if (fold) p.fold = SlabFold{counters, dw};
   const int grid = pl.tiles_co * pl.tiles_ci * pl.splits;
   const size_t lds4 = (size_t)2 * (2 * 2 * 4096 + 2 * 2 * 4096), lds2 = (size_t)2 * (2 * 1 * 4096 + 2 * 2 * 4096);
   static DcnPerDeviceFlag attr_once;
@@ -856,27 +835,99 @@ static int wgrad1x_launch(const float* x, int ldx, const float* dy, int lddy, fl
   else hipLaunchKernelGGL(wgrad1x_kernel<2>, dim3(grid), dim3(512), lds2, stream, p);
   prof_end(pid, stream);
   DCN_CHECK_LAUNCH("wgrad1x");
-  if (pl.splits > 1 && !fold) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * cin / 4, pl.splits, stream);
-  return DCN_OK;
+  return slab_sum(sp, dw, (int64_t)cout * cin, pl.splits, stream);
+}
+
+// the per-tap tile of wgrad_kernel: every layer no other kernel takes
+static int wgrad_tile_launch(int esize, const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, const uint32_t* geom,
+                             int n, int h, int wd, int cin, int cout, int ksize, int stride, const uint32_t* amax_x, const uint32_t* amax_dy,
+                             hipStream_t stream) {
+  const bool in16 = esize == 2;
+  const Plan pl = make_plan(esize, n, h, wd, cin, cout, ksize, stride);
+  DCN_CHECK_ARG(!in16 || pl.M >= 16, "conv2d_bwd_weight_b16: fewer than 16 output pixels");
+  const int groups = pl.tiles_co * pl.tiles_ci * pl.T;
+  SlabPath sp;
+  if (const int rc = slab_path(sp, wgrad_entry(esize), dw, ws, counters, groups, pl.splits, (long long)pl.tm * pl.tn * 4)) return rc;
+  const ConvShape g(h, wd, ksize, stride);
+  WgradParams p{};
+  p.x = (const float*)x; p.dy = (const float*)dy; p.out = sp.out; p.fold = sp.fold;
+  p.N = n; p.H = h; p.W = wd; p.Ci = cin; p.ldx = ldx;
+  p.ksize = ksize; p.stride = stride; p.pad = g.pad; p.T = pl.T;
+  p.Ho = g.ho; p.Wo = g.wo;
+  p.Co = cout; p.lddy = lddy;
+  p.M = pl.M; p.kchunk = pl.kchunk; p.splits = pl.splits;
+  p.tiles_co = pl.tiles_co; p.tiles_ci = pl.tiles_ci; p.c4 = !in16 && cin == 4; p.ld_out = pl.ld_out;
+  p.Co_ld = cout; p.geom = geom; p.amax_x = amax_x; p.amax_dy = amax_dy;
+  const int rc = in16 ? launch_wgrad<128, 128, true, 0, 1, true>(p, groups * pl.splits, 1, stream)
+                      : dispatch_wgrad(p, pl.tm, pl.tn, groups * pl.splits, 1, stream);
+  if (rc != DCN_OK) return rc;
+  return slab_sum(sp, dw, (int64_t)cout * pl.ld_out, pl.splits, stream);
+}
+
+DCN_KNOB(g_w3_b16, "w3b16", 0, "wgrad.hip: 1 = bf16-storage 3x3 stride-1 weight gradients by filter rows (wgrad3.hip)");
+// w3b16 measured
+// (tools/bench_b16.py --set w3b16=0 --ab w3b16=1, N = 64): it LOSES to the per-tap tile here — 128->256 @52 0.170 -> 0.207 ms,
+// 256->512 @26 0.167 -> 0.204, 512->512 @52 1.22 -> 1.50: with one MFMA per product both are bound by the bytes they stage per
+// FLOP (DESIGN.md section 4, round 4), and the filter-row form stages more (a 16-position step per 3 x 8 MFMAs); off
+DCN_KNOB(g_w9_b16, "9b16", 1, "wgrad.hip: the 32 -> 64 / 64 -> 128 3x3 layers of the bf16-storage mode on wgrad9.hip (0 = per-tap tile)");
+
+// ---- routes ---------------------------------------------------------------------------------------------------------------------------
+// The kernels whose SHAPE test a layer passes, in dispatch order, with the slab floats each would write; the per-tap tile, which takes
+// every layer, comes last.  The launch and the workspace size both walk this list.  Which route runs is known only at the launch (the
+// abs-max words, the pixel strides, "wsplit", "w3b16", "9b16"), so the workspace is sized for all of them: the buffer is shared scratch
+// that only grows, and a slab past its end would land in whatever follows.
+enum WgradKernel { W_NINE, W_ROWS, W_WIDE, W_TILE };
+struct WgradRoute { WgradKernel kernel; int64_t ws; };
+static int wgrad_routes(WgradRoute* r, int esize, int n, int h, int wd, int cin, int cout, int ksize, int stride) {
+  int k = 0;
+  // the 32 -> 64 (either stride) and 64 -> 128 (stride 1) 3x3 layers: all nine taps per workgroup (wgrad9.hip), dY and X read once
+  if (wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride)) r[k++] = {W_NINE, wgrad9_ws(n, h, wd, cin, cout, stride)};
+  // 3x3 stride-1 layers with >= 128 channels on a side: one filter row per workgroup (wgrad3.hip), the dY tile staged once for three taps
+  if (esize == 2 ? wgrad3_b16_ok(n, h, wd, cin, cout, ksize, stride) : wgrad3_shape_ok(n, h, wd, cin, cout, ksize, stride))
+    r[k++] = {W_ROWS, wgrad3_ws(n, h, wd, cin, cout)};
+  if (esize == 4 && wgrad1x_shape_ok(n, h, wd, cin, cout, ksize, stride))
+    r[k++] = {W_WIDE, slab_floats(plan1x(n * h * wd, cin, cout).splits, (int64_t)cout * cin)};
+  const Plan pl = make_plan(esize, n, h, wd, cin, cout, ksize, stride);
+  r[k++] = {W_TILE, slab_floats(pl.splits, (int64_t)cout * pl.ld_out)};
+  return k;
+}
+static int64_t wgrad_ws(int esize, int n, int h, int wd, int cin, int cout, int ksize, int stride) {
+  WgradRoute r[4];
+  int64_t ws = 0;
+  for (int i = 0, k = wgrad_routes(r, esize, n, h, wd, cin, cout, ksize, stride); i < k; ++i)
+    if (r[i].ws > ws) ws = r[i].ws;
+  return ws;
+}
+// lx, ly: pixel strides in elements.  esize 4: amax_x / amax_dy may be null; 2: they are.
+static int wgrad_launch(int esize, const void* x, int lx, const void* dy, int ly, float* dw, float* ws, uint32_t* counters, const uint32_t* geom,
+                        int n, int h, int wd, int cin, int cout, int ksize, int stride, const uint32_t* amax_x, const uint32_t* amax_dy,
+                        hipStream_t stream) {
+  const bool in16 = esize == 2;
+  const bool f16 = !in16 && g_wsplit == 4 && amax_x && amax_dy, b16 = !in16 && g_wsplit == 2;      // (2: the bf16- and fp8-operand modes)
+  const bool fast32 = !g_abl && lx % 4 == 0 && ly % 4 == 0;      // what every shortcut of the fp32 entry asks for
+  const long long npix = (long long)n * h * wd;
+  const bool off32 = npix * lx * esize < 0x7FFFFFF0LL && npix * ly * esize < 0x7FFFFFF0LL;       // 32-bit byte offsets from the tensor bases
+  WgradRoute r[4];
+  for (int i = 0, k = wgrad_routes(r, esize, n, h, wd, cin, cout, ksize, stride); i < k; ++i) switch (r[i].kernel) {
+    case W_NINE:
+      if (in16 ? g_w9_b16 != 0 : f16 && fast32)
+        return wgrad9_launch(esize, x, lx, dy, ly, dw, ws, n, h, wd, cin, cout, stride, amax_x, amax_dy, nullptr, stream);
+      break;
+    case W_ROWS:
+      if ((in16 ? g_w3_b16 != 0 : (f16 || b16) && fast32) && off32)
+        return wgrad3_launch(esize, x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, amax_x, amax_dy, f16 ? 2 : 1, stream);
+      break;
+    case W_WIDE:
+      if (f16 && fast32 && off32)
+        return wgrad1x_launch((const float*)x, lx, (const float*)dy, ly, dw, ws, counters, (int)npix, cin, cout, amax_x, amax_dy, stream);
+      break;
+    case W_TILE: break;
+  }
+  return wgrad_tile_launch(esize, x, lx, dy, ly, dw, ws, counters, geom, n, h, wd, cin, cout, ksize, stride, amax_x, amax_dy, stream);
 }
 
 extern "C" int64_t dcn_conv2d_bwd_weight_ws(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
-  const Plan pl = make_plan(n, h, wd, cin, cout, ksize, stride);
-  int64_t ws = pl.splits > 1 ? (int64_t)pl.splits * cout * pl.ld_out : 0;
-  if (wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride)) {
-    const int64_t w9 = wgrad9_ws(n, h, wd, cin, cout, stride);
-    if (w9 > ws) ws = w9;
-  }
-  if (wgrad3_shape_ok(n, h, wd, cin, cout, ksize, stride)) {       // (which kernel runs depends on the abs-max words: size for both)
-    const int64_t w3 = wgrad3_ws(n, h, wd, cin, cout);
-    if (w3 > ws) ws = w3;
-  }
-  if (wgrad1x_shape_ok(n, h, wd, cin, cout, ksize, stride)) {
-    const Plan1x p1 = plan1x(n * h * wd, cin, cout);
-    const int64_t w1 = p1.splits > 1 ? (int64_t)p1.splits * cout * cin : 0;
-    if (w1 > ws) ws = w1;
-  }
-  return ws;
+  return wgrad_ws(4, n, h, wd, cin, cout, ksize, stride);
 }
 
 // Weight gradient of a convolution whose input is the RAW output of the conv + BatchNorm layer in front (dcn_conv2d_fwd_pre): the
@@ -892,27 +943,25 @@ extern "C" int dcn_conv2d_bwd_weight_pre(const float* x, int ldx, const float* d
   const int lx = ldx > 0 ? ldx : cin, ly = lddy > 0 ? lddy : cout;
   DCN_CHECK_ARG(lx % 4 == 0 && ly % 4 == 0, "conv2d_bwd_weight_pre: pixel strides must be multiples of 4 floats");
   const DcnPreAct pre{pre_scale, pre_shift, pre_act, pre_slope};
-  return wgrad9_launch(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, stride, amax_x, amax_dy, &pre, (hipStream_t)stream_);
+  return wgrad9_launch(4, x, lx, dy, ly, dw, ws, n, h, wd, cin, cout, stride, amax_x, amax_dy, &pre, (hipStream_t)stream_);
 }
 extern "C" int dcn_conv2d_bwd_weight_pre_supported(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   return (g_wsplit == 4 && !g_abl && cin == 32 && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride)) ? 1 : 0;
 }
 
 extern "C" int64_t dcn_conv2d_geom_size(int n, int h, int wd, int ksize, int stride) {
-  const int pad = (ksize - 1) / 2;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
-  return (int64_t)n * ho * wo + GEOM_SLACK;
+  const ConvShape g(h, wd, ksize, stride);
+  return (int64_t)n * g.ho * g.wo + GEOM_SLACK;
 }
 
 extern "C" int dcn_conv2d_geom(uint32_t* table, int n, int h, int wd, int ksize, int stride, void* stream_) {
   DCN_CHECK_ARG(table && n > 0 && h > 0 && wd > 0, "conv2d_geom: bad argument");
   DCN_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "conv2d_geom: ksize=%d stride=%d", ksize, stride);
   DCN_CHECK_ARG((int64_t)n * h * wd < (1LL << 27), "conv2d_geom: %lld input pixels exceed the 27-bit index", (long long)n * h * wd);
-  const int pad = (ksize - 1) / 2;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
-  const int M = n * ho * wo;
+  const ConvShape g(h, wd, ksize, stride);
+  const int M = n * g.ho * g.wo;
   hipLaunchKernelGGL(geom_kernel, dim3(cdiv(M + GEOM_SLACK, 256)), dim3(256), 0, (hipStream_t)stream_,
-                     table, n, h, wd, ho, wo, stride, pad, M);
+                     table, n, h, wd, g.ho, g.wo, stride, g.pad, M);
   DCN_CHECK_LAUNCH("conv2d_geom");
   return DCN_OK;
 }
@@ -921,134 +970,28 @@ extern "C" int dcn_conv2d_bwd_weight(const float* x, int ldx, const float* dy, i
                                      const uint32_t* geom,
                                      int n, int h, int wd, int cin, int cout, int ksize, int stride,
                                      const uint32_t* amax_x, const uint32_t* amax_dy, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   DCN_CHECK_ARG(ksize == 1 || ksize == 3, "conv2d_bwd_weight: ksize=%d", ksize);
   DCN_CHECK_ARG(stride == 1 || stride == 2, "conv2d_bwd_weight: stride=%d", stride);
   DCN_CHECK_ARG(cin == 4 || cin % 4 == 0, "conv2d_bwd_weight: cin=%d must be a multiple of 4", cin);
   DCN_CHECK_ARG(cin != 4 || (ksize == 3 && stride == 1), "conv2d_bwd_weight: cin=4 path is the 3x3 stride-1 stem only");
   DCN_CHECK_ARG(cout % 4 == 0, "conv2d_bwd_weight: cout=%d must be a multiple of 4", cout);
   DCN_CHECK_ARG(x && dy && dw && geom, "conv2d_bwd_weight: null pointer (geom = table of dcn_conv2d_geom for this geometry)");
-  {
-    const int lx = ldx > 0 ? ldx : cin, ly = lddy > 0 ? lddy : cout;
-    const long long npix = (long long)n * h * wd;
-    const bool f16 = g_wsplit == 4 && amax_x && amax_dy, b16 = g_wsplit == 2;      // (2: the bf16- and fp8-operand modes)
-    if (f16 && !g_abl && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride) && lx % 4 == 0 && ly % 4 == 0)
-      return wgrad9_launch(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, stride, amax_x, amax_dy, nullptr, stream);
-    if ((f16 || b16) && !g_abl && wgrad3_shape_ok(n, h, wd, cin, cout, ksize, stride) &&
-        npix * lx * 4 < 0x7FFFFFF0LL && npix * ly * 4 < 0x7FFFFFF0LL && lx % 4 == 0 && ly % 4 == 0)
-      return wgrad3_launch(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, amax_x, amax_dy, f16 ? 2 : 1, stream);
-    if (f16 && !g_abl && wgrad1x_shape_ok(n, h, wd, cin, cout, ksize, stride) && lx % 4 == 0 && ly % 4 == 0 &&
-        npix * lx * 4 < 0x7FFFFFF0LL && npix * ly * 4 < 0x7FFFFFF0LL)
-      return wgrad1x_launch(x, lx, dy, ly, dw, ws, counters, (int)npix, cin, cout, amax_x, amax_dy, stream);
-  }
-  const Plan pl = make_plan(n, h, wd, cin, cout, ksize, stride);
-  DCN_CHECK_ARG(pl.splits == 1 || ws, "conv2d_bwd_weight: workspace required (%d splits)", pl.splits);
-  WgradParams p{};
-  p.x = x; p.dy = dy; p.out = pl.splits > 1 ? ws : dw;
-  p.N = n; p.H = h; p.W = wd; p.Ci = cin; p.ldx = ldx > 0 ? ldx : cin;
-  p.ksize = ksize; p.stride = stride; p.pad = (ksize - 1) / 2; p.T = pl.T;
-  p.Ho = (h + 2 * p.pad - ksize) / stride + 1; p.Wo = (wd + 2 * p.pad - ksize) / stride + 1;
-  p.Co = cout; p.lddy = lddy > 0 ? lddy : cout;
-  p.M = pl.M; p.kchunk = pl.kchunk; p.splits = pl.splits;
-  p.tiles_co = pl.tiles_co; p.tiles_ci = pl.tiles_ci; p.c4 = cin == 4; p.ld_out = pl.ld_out;
-  p.Co_ld = cout; p.geom = geom; p.amax_x = amax_x; p.amax_dy = amax_dy;
-  const bool fold = slab_fold_ok(counters, pl.tiles_co * pl.tiles_ci * pl.T, pl.splits, (long long)pl.tm * pl.tn * 4, g_slab_fold);
-  if (fold) p.fold = SlabFold{counters, dw};
-  const int grid = pl.tiles_co * pl.tiles_ci * pl.T * pl.splits;
-  int rc = dispatch_wgrad(p, pl.tm, pl.tn, grid, 1, stream);
-  if (rc != DCN_OK) return rc;
-  if (pl.splits > 1 && !fold) {
-    return wgrad_reduce_slabs(ws, dw, (int64_t)cout * pl.ld_out / 4, pl.splits, stream);
-  }
-  return DCN_OK;
+  return wgrad_launch(4, x, ldx > 0 ? ldx : cin, dy, lddy > 0 ? lddy : cout, dw, ws, counters, geom, n, h, wd, cin, cout, ksize, stride,
+                      amax_x, amax_dy, (hipStream_t)stream_);
 }
 
-// ---- bf16 storage: x and dy are bf16 NHWC tensors, dw is fp32 [Cout][k][k][Cin] --------------------------------------------------
-// Always the 128 x 128 one-plane tile of wgrad_kernel with bf16 loads (narrower layers leave part of it empty: those launches are
-// bound by their 9-fold gather, not by the matrix pipe).  Split-K over the pixels into fp32 slabs, summed in a fixed order.
-namespace {
-Plan make_plan_b16(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
-  Plan pl;
-  const int pad = (ksize - 1) / 2;
-  const int ho = (h + 2 * pad - ksize) / stride + 1, wo = (wd + 2 * pad - ksize) / stride + 1;
-  pl.M = n * ho * wo; pl.tm = pl.tn = 128;
-  pl.tiles_co = cdiv(cout, 128); pl.tiles_ci = cdiv(cin, 128);
-  pl.T = ksize * ksize; pl.ld_out = pl.T * cin;
-  const int base = pl.tiles_co * pl.tiles_ci * pl.T;
-  const int max_splits = pl.M / 256 > 0 ? pl.M / 256 : 1;
-  // (3x3 stride-1 layers: with one MFMA per product the kernel is twice as fast as the f16-split tile while a slab costs the same, so fewer,
-  //  longer splits win — tools/bench_b16.py --ab qtargetb16=..., N = 64: 1024 -> 768 workgroups 128->256 @52 0.169 -> 0.146 ms, 512->512 @52
-  //  1.25 -> 1.02, 64->128 @104 0.311 -> 0.243; 512 loses again on the 13-wide maps; the 1x1 / stride-2 layers keep 512: 256 costs 15-70 %)
-  // (1x1 / stride-2 layers: one full round of 768 as well once the launch is large — 1024->512 @52 0.303 -> 0.249 ms, 128->256 s2 @104
-  //  0.177 -> 0.151 —, 512 for the small residual 1x1 layers, whose slabs weigh more: 256->128 @52 0.048 vs 0.052)
-  const bool small_cls = ksize == 1 || stride == 2;
-  const int target = small_cls ? (2.0 * pl.M * (double)cin * cout * pl.T >= 3e10 ? g_wg_target_b16 : g_wg_target_small_b16) : g_wg_target_b16;
-  int splits = target / base;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  for (;;) {
-    pl.kchunk = cdiv(cdiv(pl.M, splits), 32) * 32;
-    pl.splits = cdiv(pl.M, pl.kchunk);
-    if (base * pl.splits <= target || splits == 1 || base > target) break;
-    --splits;
-  }
-  return pl;
-}
-}  // namespace
-
-bool wgrad3_b16_ok(int n, int h, int wd, int cin, int cout, int ksize, int stride);
-int wgrad3_launch_b16(const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout,
-                      hipStream_t stream);
-DCN_KNOB(g_w3_b16, "w3b16", 0, "wgrad.hip: 1 = bf16-storage 3x3 stride-1 weight gradients by filter rows (wgrad3.hip)");
-// w3b16 measured
-// (tools/bench_b16.py --set w3b16=0 --ab w3b16=1, N = 64): it LOSES to the per-tap tile here — 128->256 @52 0.170 -> 0.207 ms,
-// 256->512 @26 0.167 -> 0.204, 512->512 @52 1.22 -> 1.50: with one MFMA per product both are bound by the bytes they stage per
-// FLOP (DESIGN.md section 4, round 4), and the filter-row form stages more (a 16-position step per 3 x 8 MFMAs); off
-
-int wgrad9_launch_b16(const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout, int stride,
-                      hipStream_t stream);
-DCN_KNOB(g_w9_b16, "9b16", 1, "wgrad.hip: the 32 -> 64 / 64 -> 128 3x3 layers of the bf16-storage mode on wgrad9.hip (0 = per-tap tile)");
-
+// bf16 storage: x and dy are bf16 NHWC tensors, dw is fp32 [Cout][k][k][Cin]; split-K over the pixels into fp32 slabs, summed in a fixed order
 extern "C" int64_t dcn_conv2d_bwd_weight_ws_b16(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
-  const Plan pl = make_plan_b16(n, h, wd, cin, cout, ksize, stride);
-  int64_t ws = pl.splits > 1 ? (int64_t)pl.splits * cout * pl.ld_out : 0;
-  if (wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride)) { const int64_t w9 = wgrad9_ws(n, h, wd, cin, cout, stride); if (w9 > ws) ws = w9; }
-  if (wgrad3_b16_ok(n, h, wd, cin, cout, ksize, stride)) { const int64_t w3 = wgrad3_ws(n, h, wd, cin, cout); if (w3 > ws) ws = w3; }
-  return ws;
+  return wgrad_ws(2, n, h, wd, cin, cout, ksize, stride);
 }
 
 extern "C" int dcn_conv2d_bwd_weight_b16(const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, const uint32_t* geom,
                                          int n, int h, int wd, int cin, int cout, int ksize, int stride, void* stream_) {
-  hipStream_t stream = (hipStream_t)stream_;
   DCN_CHECK_ARG((ksize == 1 || ksize == 3) && (stride == 1 || stride == 2), "conv2d_bwd_weight_b16: ksize=%d stride=%d", ksize, stride);
   DCN_CHECK_ARG(cin % 8 == 0 && cout % 8 == 0, "conv2d_bwd_weight_b16: cin=%d / cout=%d must be multiples of 8", cin, cout);
   DCN_CHECK_ARG(x && dy && dw && geom, "conv2d_bwd_weight_b16: null pointer (geom = table of dcn_conv2d_geom for this geometry)");
   const int lx = ldx > 0 ? ldx : cin, ly = lddy > 0 ? lddy : cout;
   DCN_CHECK_ARG(lx % 8 == 0 && ly % 8 == 0, "conv2d_bwd_weight_b16: pixel strides must be multiples of 8 elements");
-  // the 32 -> 64 (either stride) and 64 -> 128 (stride 1) 3x3 layers: all nine taps per workgroup (wgrad9.hip), dY and X read once
-  if (g_w9_b16 && wgrad9_shape_ok(n, h, wd, cin, cout, ksize, stride))
-    return wgrad9_launch_b16(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, stride, stream);
-  // 3x3 stride-1 layers with >= 128 channels on a side: one filter row per workgroup (wgrad3.hip), the dY tile staged once for three taps
-  if (g_w3_b16 && wgrad3_b16_ok(n, h, wd, cin, cout, ksize, stride) && (long long)n * h * wd * lx * 2 < 0x7FFFFFF0LL &&
-      (long long)n * h * wd * ly * 2 < 0x7FFFFFF0LL)
-    return wgrad3_launch_b16(x, lx, dy, ly, dw, ws, counters, n, h, wd, cin, cout, stream);
-  const Plan pl = make_plan_b16(n, h, wd, cin, cout, ksize, stride);
-  DCN_CHECK_ARG(pl.M >= 16, "conv2d_bwd_weight_b16: fewer than 16 output pixels");
-  DCN_CHECK_ARG(pl.splits == 1 || ws, "conv2d_bwd_weight_b16: workspace required (%d splits)", pl.splits);
-  WgradParams p{};
-  p.x = (const float*)x; p.dy = (const float*)dy; p.out = pl.splits > 1 ? ws : dw;
-  p.N = n; p.H = h; p.W = wd; p.Ci = cin; p.ldx = lx;
-  p.ksize = ksize; p.stride = stride; p.pad = (ksize - 1) / 2; p.T = pl.T;
-  p.Ho = (h + 2 * p.pad - ksize) / stride + 1; p.Wo = (wd + 2 * p.pad - ksize) / stride + 1;
-  p.Co = cout; p.lddy = ly;
-  p.M = pl.M; p.kchunk = pl.kchunk; p.splits = pl.splits;
-  p.tiles_co = pl.tiles_co; p.tiles_ci = pl.tiles_ci; p.c4 = 0; p.ld_out = pl.ld_out;
-  p.Co_ld = cout; p.geom = geom;
-  const bool fold = slab_fold_ok(counters, pl.tiles_co * pl.tiles_ci * pl.T, pl.splits, (long long)pl.tm * pl.tn * 4, g_slab_fold);
-  if (fold) p.fold = SlabFold{counters, dw};
-  const int grid = pl.tiles_co * pl.tiles_ci * pl.T * pl.splits;
-  int rc = launch_wgrad<128, 128, true, 0, 1, true>(p, grid, 1, stream);
-  if (rc != DCN_OK) return rc;
-  if (pl.splits > 1 && !fold) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * pl.ld_out / 4, pl.splits, stream);
-  return DCN_OK;
+  return wgrad_launch(2, x, lx, dy, ly, dw, ws, counters, geom, n, h, wd, cin, cout, ksize, stride, nullptr, nullptr, (hipStream_t)stream_);
 }
+

@@ -16,12 +16,9 @@
 // the MFMA operands come from ds_read_b64_tr_b16, as in wgrad.hip; the B fragment of tap s is the same read one row lower.
 // 8 waves: wave (wm, wn) owns 64 filters x 32 channels x 3 taps (96 accumulator registers).  Split-K over padded positions
 // into slabs summed in a fixed order (wgrad.hip reduce_slabs_kernel): bitwise reproducible.  Roofline: MFMA, 838.9 TFLOP/s.
-#include "common.h"
+#include "wgrad.h"
 #include "prof.h"
-#include "slabsum.h"
 #include <type_traits>
-
-int wgrad_reduce_slabs(const float* ws, float* dw, int64_t n4, int splits, hipStream_t stream);
 
 namespace {
 
@@ -527,17 +524,9 @@ DCN_KNOB(g_w3_target, "v3target", 512, "wgrad3.hip: workgroups a launch aims for
 
 struct Plan3 { int tiles_co, tiles_ci, splits, kchunk, Mp; };
 Plan3 plan3(int n, int h, int wd, int cin, int cout) {
-  Plan3 pl;
-  pl.tiles_co = cdiv(cout, 128); pl.tiles_ci = cdiv(cin, 128);
-  pl.Mp = n * h * (wd + 1);
-  const int base = pl.tiles_co * pl.tiles_ci * 3;
-  const int max_splits = pl.Mp / 256 > 0 ? pl.Mp / 256 : 1;
-  int splits = g_w3_target / base;
-  if (splits > max_splits) splits = max_splits;
-  if (splits < 1) splits = 1;
-  pl.kchunk = cdiv(cdiv(pl.Mp, splits), 16) * 16;
-  pl.splits = cdiv(pl.Mp, pl.kchunk);
-  return pl;
+  const int tiles_co = cdiv(cout, 128), tiles_ci = cdiv(cin, 128), Mp = n * h * (wd + 1);
+  const SplitK sk = split_k(Mp, tiles_co * tiles_ci * 3, g_w3_target, 16, false);
+  return {tiles_co, tiles_ci, sk.splits, sk.kchunk, Mp};
 }
 
 }  // namespace
@@ -552,69 +541,43 @@ bool wgrad3_shape_ok(int n, int h, int wd, int cin, int cout, int ksize, int str
   if ((long long)n * h * (wd + 1) >= 0x7FFFFFF0LL || npix < 1024) return false;
   return true;
 }
-int64_t wgrad3_ws(int n, int h, int wd, int cin, int cout) {
-  const Plan3 pl = plan3(n, h, wd, cin, cout);
-  return pl.splits > 1 ? (int64_t)pl.splits * cout * 9 * cin : 0;
-}
-
-// bf16 storage: x, dy bf16 tensors (strides in elements), dw / slabs fp32
-int wgrad_slab_fold();
-int wgrad3_launch_b16(const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout,
-                      hipStream_t stream) {
-  const Plan3 pl = plan3(n, h, wd, cin, cout);
-  DCN_CHECK_ARG(pl.splits == 1 || ws, "conv2d_bwd_weight_b16: workspace required (%d splits)", pl.splits);
-  W3Params p{};
-  p.x = (const float*)x; p.dy = (const float*)dy; p.out = pl.splits > 1 ? ws : dw;
-  p.N = n; p.H = h; p.W = wd; p.Ci = cin; p.ldx = ldx; p.Co = cout; p.lddy = lddy;
-  p.Mp = pl.Mp; p.kchunk = pl.kchunk; p.splits = pl.splits;
-  p.tiles_co = pl.tiles_co; p.tiles_ci = pl.tiles_ci; p.ld_out = 9 * cin;
-  const bool fold = slab_fold_ok(counters, pl.tiles_co * pl.tiles_ci * 3, pl.splits, 128LL * 3 * 128 * 4, wgrad_slab_fold());
-  if (fold) p.fold = SlabFold{counters, dw};
-  size_t lds = (size_t)2 * (A_PLANE + B_PLANE);
-  static DcnPerDeviceFlag attr_once;
-  if (attr_once.first())
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-  const int grid = pl.tiles_co * pl.tiles_ci * 3 * pl.splits;
-  const int pid = prof_begin(46, 2.0 * (double)n * h * wd * cout * 9.0 * cin, stream);
-  hipLaunchKernelGGL((wgrad3_kernel<1, true>), dim3(grid), dim3(512), lds, stream, p);
-  prof_end(pid, stream);
-  DCN_CHECK_LAUNCH("wgrad3 b16");
-  if (pl.splits > 1 && !fold) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * 9 * cin / 4, pl.splits, stream);
-  return DCN_OK;
-}
 bool wgrad3_b16_ok(int n, int h, int wd, int cin, int cout, int ksize, int stride) {
   return wgrad3_shape_ok(n, h, wd, cin, cout, ksize, stride) && cin % 8 == 0 && cout % 8 == 0;
 }
+int64_t wgrad3_ws(int n, int h, int wd, int cin, int cout) {
+  return slab_floats(plan3(n, h, wd, cin, cout).splits, (int64_t)cout * 9 * cin);
+}
 
-int wgrad3_launch(const float* x, int ldx, const float* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin, int cout,
-                  const uint32_t* amax_x, const uint32_t* amax_dy, int np, hipStream_t stream) {
+// esize 2 (bf16 storage): x, dy bf16 tensors, np = 1, no abs-max words; dw / slabs fp32 either way
+int wgrad3_launch(int esize, const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* counters, int n, int h, int wd, int cin,
+                  int cout, const uint32_t* amax_x, const uint32_t* amax_dy, int np, hipStream_t stream) {
+  const bool in16 = esize == 2;
   const Plan3 pl = plan3(n, h, wd, cin, cout);
-  DCN_CHECK_ARG(pl.splits == 1 || ws, "conv2d_bwd_weight: workspace required (%d splits)", pl.splits);
+  SlabPath sp;
+  if (const int rc = slab_path(sp, wgrad_entry(esize), dw, ws, counters, pl.tiles_co * pl.tiles_ci * 3, pl.splits, 128LL * 3 * 128 * 4)) return rc;
   W3Params p{};
-  p.x = x; p.dy = dy; p.out = pl.splits > 1 ? ws : dw;
+  p.x = (const float*)x; p.dy = (const float*)dy; p.out = sp.out; p.fold = sp.fold;
   p.N = n; p.H = h; p.W = wd; p.Ci = cin; p.ldx = ldx; p.Co = cout; p.lddy = lddy;
   p.Mp = pl.Mp; p.kchunk = pl.kchunk; p.splits = pl.splits;
   p.tiles_co = pl.tiles_co; p.tiles_ci = pl.tiles_ci; p.ld_out = 9 * cin;
-  const bool fold = slab_fold_ok(counters, pl.tiles_co * pl.tiles_ci * 3, pl.splits, 128LL * 3 * 128 * 4, wgrad_slab_fold());
-  if (fold) p.fold = SlabFold{counters, dw};
   p.amax_dy = amax_dy; p.amax_x = amax_x;
-  const size_t lds = (size_t)2 * np * (A_PLANE + B_PLANE);
+  const size_t lds = (size_t)2 * np * (A_PLANE + B_PLANE), ldsx = (size_t)2 * (2 * AX_PLANE + 2 * BX_PLANE);
   static DcnPerDeviceFlag attr_once;
   if (attr_once.first()) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * 2 * (A_PLANE + B_PLANE));
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (A_PLANE + B_PLANE));
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3_kernel<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * (A_PLANE + B_PLANE));
   }
+  static DcnPerDeviceFlag attr_x;
+  if (np == 2 && g_w3x && attr_x.first())
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx);
   const int grid = pl.tiles_co * pl.tiles_ci * 3 * pl.splits;
-  const int pid = prof_begin(np == 2 ? 32 : 20, 2.0 * (double)n * h * wd * cout * 9.0 * cin, stream);
-  if (np == 2 && g_w3x) {
-    const size_t ldsx = (size_t)2 * (2 * AX_PLANE + 2 * BX_PLANE);
-    static DcnPerDeviceFlag attr_x;
-    if (attr_x.first()) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&wgrad3x_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsx);
-    hipLaunchKernelGGL(wgrad3x_kernel, dim3(grid), dim3(512), ldsx, stream, p);
-  } else if (np == 2) hipLaunchKernelGGL(wgrad3_kernel<2>, dim3(grid), dim3(512), lds, stream, p);
+  const int pid = prof_begin(in16 ? 46 : np == 2 ? 32 : 20, 2.0 * (double)n * h * wd * cout * 9.0 * cin, stream);
+  if (in16) hipLaunchKernelGGL((wgrad3_kernel<1, true>), dim3(grid), dim3(512), lds, stream, p);
+  else if (np == 2 && g_w3x) hipLaunchKernelGGL(wgrad3x_kernel, dim3(grid), dim3(512), ldsx, stream, p);
+  else if (np == 2) hipLaunchKernelGGL(wgrad3_kernel<2>, dim3(grid), dim3(512), lds, stream, p);
   else hipLaunchKernelGGL(wgrad3_kernel<1>, dim3(grid), dim3(512), lds, stream, p);
   prof_end(pid, stream);
-  DCN_CHECK_LAUNCH("wgrad3");
-  if (pl.splits > 1 && !fold) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * 9 * cin / 4, pl.splits, stream);
-  return DCN_OK;
+  DCN_CHECK_LAUNCH(in16 ? "wgrad3 b16" : "wgrad3");
+  return slab_sum(sp, dw, (int64_t)cout * 9 * cin, pl.splits, stream);
 }

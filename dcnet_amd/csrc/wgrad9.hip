@@ -14,10 +14,8 @@
 // planes, so that every tap reads consecutive rows); both are split into f16 pieces on the way to LDS and the MFMA operands come
 // from ds_read_b64_tr_b16 (wgrad.hip).  Split-K over positions into slabs summed in a fixed order (reduce_slabs_kernel):
 // bitwise reproducible.  Roofline: HBM (dY + X once: 1.06 / 2.13 GB per launch at N = 64) — the MFMA work is 0.12 ms at 838.9.
-#include "igemm.h"
+#include "wgrad.h"
 #include "prof.h"
-
-int wgrad_reduce_slabs(const float* ws, float* dw, int64_t n4, int splits, hipStream_t stream);
 
 namespace {
 
@@ -313,14 +311,9 @@ DCN_KNOB(g_w9_target, "9target", 512, "wgrad9.hip: workgroups (= split-K slabs) 
 
 struct Plan9 { int splits, kchunk, Mp; };
 Plan9 plan9(int n, int ho, int wo) {
-  Plan9 pl;
-  pl.Mp = n * ho * (wo + 1);
-  int splits = g_w9_target;
-  const int max_splits = pl.Mp / 256 > 0 ? pl.Mp / 256 : 1;
-  if (splits > max_splits) splits = max_splits;
-  pl.kchunk = cdiv(cdiv(pl.Mp, splits), KS) * KS;
-  pl.splits = cdiv(pl.Mp, pl.kchunk);
-  return pl;
+  const int Mp = n * ho * (wo + 1);
+  const SplitK sk = split_k(Mp, 1, g_w9_target, KS, false);        // one tile: every workgroup is a split
+  return {sk.splits, sk.kchunk, Mp};
 }
 
 template <int S, int CO, int CI> size_t lds9() { return (size_t)2 * G9<S, CO, CI>::BUF; }
@@ -353,20 +346,23 @@ bool wgrad9_shape_ok(int n, int h, int wd, int cin, int cout, int ksize, int str
   return true;
 }
 int64_t wgrad9_ws(int n, int h, int wd, int cin, int cout, int stride) {
-  const Plan9 pl = plan9(n, h / stride, wd / stride);
-  return pl.splits > 1 ? (int64_t)pl.splits * cout * 9 * cin : 0;
+  return slab_floats(plan9(n, h / stride, wd / stride).splits, (int64_t)cout * 9 * cin);
 }
 
-int wgrad9_launch(const float* x, int ldx, const float* dy, int lddy, float* dw, float* ws, uint32_t* /*counters: one tile, 512 splits — a second launch sums them (slabsum.h)*/, int n, int h, int wd, int cin, int cout, int stride,
+// esize 2: the same layer forms on bf16 tensors (x, dy bf16 NHWC; dw fp32 [Cout][3][3][Cin]); the per-tap tile of wgrad.hip reads dY
+// and X nine times for them (32 -> 64 @208: 0.85 ms against 0.11 ms of HBM traffic).  One tile, 512 splits: never folded (slabsum.h).
+int wgrad9_launch(int esize, const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, int n, int h, int wd, int cin, int cout, int stride,
                   const uint32_t* amax_x, const uint32_t* amax_dy, const DcnPreAct* pre, hipStream_t stream) {
+  const bool in16 = esize == 2;
   const int ho = h / stride, wo = wd / stride;
   const Plan9 pl = plan9(n, ho, wo);
-  DCN_CHECK_ARG(pl.splits == 1 || ws, "conv2d_bwd_weight: workspace required (%d splits)", pl.splits);
-  DCN_CHECK_ARG((long long)n * ho * wo * lddy * 4 < 0x7FFFFFF0LL && (long long)n * h * wd * ldx * 4 < 0x7FFFFFF0LL,
-                "conv2d_bwd_weight: a sliced operand of %lld bytes exceeds the 32-bit byte offsets of the nine-tap kernel",
-                (long long)n * h * wd * ldx * 4);
+  SlabPath sp;
+  if (const int rc = slab_path(sp, wgrad_entry(esize), dw, ws, nullptr, 1, pl.splits, 0)) return rc;
+  DCN_CHECK_ARG((long long)n * ho * wo * lddy * esize < 0x7FFFFFF0LL && (long long)n * h * wd * ldx * esize < 0x7FFFFFF0LL,
+                "%s: a sliced operand of %lld bytes exceeds the 32-bit byte offsets of the nine-tap kernel", wgrad_entry(esize),
+                (long long)n * h * wd * ldx * esize);
   W9Params p{};
-  p.x = x; p.dy = dy; p.out = pl.splits > 1 ? ws : dw;
+  p.x = (const float*)x; p.dy = (const float*)dy; p.out = sp.out;
   p.N = n; p.H = h; p.W = wd; p.Ho = ho; p.Wo = wo; p.ldx = ldx; p.lddy = lddy;
   p.Mp = pl.Mp; p.kchunk = pl.kchunk; p.splits = pl.splits;
   p.amax_dy = amax_dy; p.amax_x = amax_x;
@@ -376,36 +372,16 @@ int wgrad9_launch(const float* x, int ldx, const float* dy, int lddy, float* dw,
     p.pre_scale = pre->scale; p.pre_shift = pre->shift; p.pre_act = pre->act; p.pre_slope = pre->slope;
   }
   // HBM-priced: dY and X once, the slabs written
-  const double bytes = 4.0 * ((double)n * ho * wo * cout + (double)n * h * wd * cin + (double)pl.splits * cout * 9 * cin);
+  const double bytes = (double)esize * ((double)n * ho * wo * cout + (double)n * h * wd * cin) + 4.0 * (double)pl.splits * cout * 9 * cin;
   const int pid = prof_begin(36, 2.0 * (double)n * ho * wo * cout * 9.0 * cin, stream, bytes);
-  if (cin == 32 && pre) { if (stride == 1) launch9<1, 64, 32, true>(p, pl.splits, stream); else launch9<2, 64, 32, true>(p, pl.splits, stream); }
+  if (in16) {
+    if (cin == 32) { if (stride == 1) launch9<1, 64, 32, false, true>(p, pl.splits, stream); else launch9<2, 64, 32, false, true>(p, pl.splits, stream); }
+    else { if (stride == 1) launch9<1, 128, 64, false, true>(p, pl.splits, stream); else launch9<2, 128, 64, false, true>(p, pl.splits, stream); }
+  }
+  else if (cin == 32 && pre) { if (stride == 1) launch9<1, 64, 32, true>(p, pl.splits, stream); else launch9<2, 64, 32, true>(p, pl.splits, stream); }
   else if (cin == 32) { if (stride == 1) launch9<1, 64, 32>(p, pl.splits, stream); else launch9<2, 64, 32>(p, pl.splits, stream); }
   else { if (stride == 1) launch9<1, 128, 64>(p, pl.splits, stream); else launch9<2, 128, 64>(p, pl.splits, stream); }
   prof_end(pid, stream);
-  DCN_CHECK_LAUNCH("wgrad9");
-  if (pl.splits > 1) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * 9 * cin / 4, pl.splits, stream);
-  return DCN_OK;
-}
-
-// bf16 storage: the same two layer forms on bf16 tensors (x, dy bf16 NHWC; dw fp32 [Cout][3][3][Cin]); the per-tap tile of wgrad.hip reads
-// dY and X nine times for them (32 -> 64 @208: 0.85 ms against 0.11 ms of HBM traffic).
-int wgrad9_launch_b16(const void* x, int ldx, const void* dy, int lddy, float* dw, float* ws, uint32_t* /*counters*/, int n, int h, int wd, int cin, int cout, int stride,
-                      hipStream_t stream) {
-  const int ho = h / stride, wo = wd / stride;
-  const Plan9 pl = plan9(n, ho, wo);
-  DCN_CHECK_ARG(pl.splits == 1 || ws, "conv2d_bwd_weight_b16: workspace required (%d splits)", pl.splits);
-  DCN_CHECK_ARG((long long)n * ho * wo * lddy * 2 < 0x7FFFFFF0LL && (long long)n * h * wd * ldx * 2 < 0x7FFFFFF0LL,
-                "conv2d_bwd_weight_b16: a sliced operand exceeds the 32-bit byte offsets of the nine-tap kernel");
-  W9Params p{};
-  p.x = (const float*)x; p.dy = (const float*)dy; p.out = pl.splits > 1 ? ws : dw;
-  p.N = n; p.H = h; p.W = wd; p.Ho = ho; p.Wo = wo; p.ldx = ldx; p.lddy = lddy;
-  p.Mp = pl.Mp; p.kchunk = pl.kchunk; p.splits = pl.splits;
-  const double bytes = 2.0 * ((double)n * ho * wo * cout + (double)n * h * wd * cin) + 4.0 * (double)pl.splits * cout * 9 * cin;
-  const int pid = prof_begin(36, 2.0 * (double)n * ho * wo * cout * 9.0 * cin, stream, bytes);
-  if (cin == 32) { if (stride == 1) launch9<1, 64, 32, false, true>(p, pl.splits, stream); else launch9<2, 64, 32, false, true>(p, pl.splits, stream); }
-  else { if (stride == 1) launch9<1, 128, 64, false, true>(p, pl.splits, stream); else launch9<2, 128, 64, false, true>(p, pl.splits, stream); }
-  prof_end(pid, stream);
-  DCN_CHECK_LAUNCH("wgrad9 (bf16)");
-  if (pl.splits > 1) return wgrad_reduce_slabs(ws, dw, (int64_t)cout * 9 * cin / 4, pl.splits, stream);
-  return DCN_OK;
+  DCN_CHECK_LAUNCH(in16 ? "wgrad9 (bf16)" : "wgrad9");
+  return slab_sum(sp, dw, (int64_t)cout * 9 * cin, pl.splits, stream);
 }

@@ -1590,3 +1590,84 @@ def test_slab_fold_is_bitwise_the_separate_pass(dev, case):
     assert int(ops.slab_counters(dev, 0).abs().sum()) == 0
     nws = lib().conv2d_bwd_weight_ws(n, h, w, cin, cout, k, s)
     assert nws > 0, "the case has one split: nothing was folded"
+
+
+WS_CASES = [
+    # n, h, w, cin, cout, k, stride  — the smallest shape of every route of dcn_conv2d_bwd_weight / _b16 that splits K
+    (2, 16, 20, 64, 32, 1, 1),           # narrow fp32-pipe tile
+    (1, 32, 32, 4, 32, 3, 1),            # stem layout (c4)
+    (8, 54, 58, 64, 128, 3, 2),          # 128 x 128 tile, stride 2
+    (8, 13, 13, 128, 256, 3, 1),         # filter rows (wgrad3.hip)
+    (2, 33, 31, 136, 160, 3, 1),         # ... ragged channel tiles
+    (7, 25, 27, 384, 192, 1, 1),         # wide 1x1 tile
+    (1, 64, 64, 32, 64, 3, 1),           # nine taps (wgrad9.hip)
+    (2, 64, 64, 32, 64, 3, 2),           # ... stride 2
+    (2, 64, 64, 64, 128, 3, 1),          # ... 64 -> 128
+]
+# every split-K target at its default, at the smallest value the tests of its kernel use, and at its largest
+WS_TARGETS = [{},
+              {"9target": 1, "v3target": 96, "Y1wide": 64, "xwgtarget": 1, "zwgsmall": 1, "qtargetb16": 1, "qsmallb16": 1},
+              {"9target": 4096, "v3target": 4096, "Y1wide": 1024, "xwgtarget": 4096, "zwgsmall": 4096, "qtargetb16": 4096, "qsmallb16": 4096}]
+
+
+@pytest.mark.parametrize("case", WS_CASES)
+def test_wgrad_workspace_covers_every_slab(dev, case):
+    """dcn_conv2d_bwd_weight_ws / _ws_b16 size a buffer that is shared scratch and only grows: a size that falls behind the kernel a
+    launch picks lets the slabs run into whatever follows.  Here the entry points are called on a workspace of exactly the size asked
+    for, with guard words behind it and on both sides of dw: the guards must survive, and dw must be what ops returns — for the fp32
+    entry with both abs-max words and with none (another route: against fp64), for the bf16 entry with its shortcut routes off and on,
+    at three settings of the split-K targets, slabs summed behind the launch and by the last workgroup."""
+    from dcnet_amd import ops
+    from dcnet_amd.lib import lib
+    n, h, w, cin, cout, k, s = case
+    G = 4096
+    x = _rand(n, h, w, cin, seed=71).to(dev)
+    xd = x.permute(0, 3, 1, 2).double().cpu()
+    wgt = torch.zeros(cout, cin, k, k, dtype=torch.float64, requires_grad=True)
+    y = F.conv2d(xd, wgt, padding=(k - 1) // 2, stride=s)
+    dy = (_rand(n, y.shape[2], y.shape[3], cout, seed=72) / 8).to(dev)
+    y.backward(dy.permute(0, 3, 1, 2).double().cpu())
+    ref = wgt.grad.permute(0, 2, 3, 1)                                         # OHWI
+    ax, ay = ops.absmax(x), ops.absmax(dy)
+    geom, cnt = ops.conv_geom(dev, n, h, w, k, s), ops.slab_counters(dev, 0)
+    numel = cout * 64 if cin == 4 else cout * k * k * cin
+    pattern = lambda nfloats: torch.full((nfloats,), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    bits = lambda t: t.reshape(-1).view(torch.int32)
+    args = (n, h, w, cin, cout, k, s)
+
+    def guarded(size_fn, launch):
+        """launch(dw_ptr, ws_ptr) on a workspace of size_fn(...) floats and a dw, each between guard words; returns dw"""
+        nws = size_fn(*args)
+        wsbuf, dwbuf = pattern(nws + G), pattern(G + numel + G)
+        launch(dwbuf[G:].data_ptr(), wsbuf.data_ptr())
+        torch.cuda.synchronize()
+        for name, guard in (("behind the workspace", wsbuf[nws:]), ("in front of dw", dwbuf[:G]), ("behind dw", dwbuf[G + numel:])):
+            assert bool((guard == 0x5A5A5A5A).all()), f"{case}: the launch wrote {name} (workspace of {nws} floats)"
+        assert int(cnt.abs().sum()) == 0
+        return dwbuf[G:G + numel].view(torch.float32)
+
+    def fp32(amax_x, amax_dy):
+        return lambda dw, ws: lib().conv2d_bwd_weight(x.data_ptr(), x.stride(2), dy.data_ptr(), dy.stride(2), dw, ws, cnt.data_ptr(), geom.data_ptr(),
+                                                      *args, amax_x, amax_dy, torch.cuda.current_stream().cuda_stream)
+
+    b16 = cin % 8 == 0 and cout % 8 == 0
+    if b16:
+        xb, dyb = x.to(torch.bfloat16), dy.to(torch.bfloat16)
+        bf16 = lambda dw, ws: lib().conv2d_bwd_weight_b16(xb.data_ptr(), xb.stride(2), dyb.data_ptr(), dyb.stride(2), dw, ws, cnt.data_ptr(),
+                                                          geom.data_ptr(), *args, torch.cuda.current_stream().cuda_stream)
+    for targets in WS_TARGETS:
+        for fold in (0, 1 << 20):
+            with tuning(targets) as tune:
+                tune({"Slabfold": fold})
+                tag = f"{case} {targets} Slabfold {fold}"
+                got = guarded(lib().conv2d_bwd_weight_ws, fp32(ax.data_ptr(), ay.data_ptr()))
+                assert torch.equal(bits(got), bits(ops.conv2d_bwd_weight(x, dy, k, s, amax_x=ax, amax_dy=ay))), tag
+                got = guarded(lib().conv2d_bwd_weight_ws, fp32(0, 0))
+                if cin == 4:
+                    _close(got.view(cout, 64)[:, :36].reshape(cout, 3, 3, 4), ref, 3e-5, tag + " no abs-max words")
+                else:
+                    _close(got.view(ref.shape), ref, 3e-5, tag + " no abs-max words")
+                for on in (0, 1) if b16 else ():
+                    tune({"w3b16": on, "9b16": on})
+                    got = guarded(lib().conv2d_bwd_weight_ws_b16, bf16)
+                    assert torch.equal(bits(got), bits(ops.conv2d_bwd_weight_b16(xb, dyb, k, s))), f"{tag} bf16 storage, shortcuts {on}"
